@@ -2,6 +2,19 @@
 """Benchmark of the a-trous hot path: Mpix/s, roofline fraction, CPU baseline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|cfg2|cfg3|cfg5]
+                    [--full] [--dump-outputs DIR]
+
+A plain run (N = 1) sets up, warms up, times K steps and prints the line: metric, value, unit,
+ms_per_step (one timed step), dtype, the workload, the whole-path HBM fraction of the timed steps.
+--full adds everything that takes work of its own: the per-step spread, the per-kernel table and
+the roofline entry (profiled steps after the timed ones), the PCIe-inclusive rates, the sequence
+and first-call entries, the CPU baseline, and - for the headline - the entries listed below.
+(N > 1 lines always carry their per-pass table, the overlap / placement A/B that chooses their
+value, the halo self-check and the replica datum; --full changes nothing there.)
+--dump-outputs DIR: after the timed steps, what the last one computed goes to DIR/*.npy
+(dump_outputs: coefficient planes and reconstruction, sampled above 2^20 pixels; cfg3 / cfg5 also
+the noise estimate; N > 1: rank 0's strip).  The inputs are seeded: the same arguments give the
+same inputs every run.
 
 --config headline (default; BASELINE.json `metric`)
     N = 1 : 8192 x 8192 float32 N(0,1), B3spline, 6 scales: decompose (7 planes materialised in
@@ -25,11 +38,12 @@
 
 One step = one pass of the hot path over the image.  Rank 0 prints ONE JSON line.
 
-The default invocation (N = 1, --config headline) additionally times cfg2, cfg3 and cfg5 after the
+With --full, the N = 1 headline run additionally times cfg2, cfg3 and cfg5 after the
 headline and appends them to the same line as `"configs": {"cfg2": {...}, "cfg3": {...}, "cfg5":
 {...}}` (value, ms_per_step, SURVEY 8(d) bytes per pixel and fraction, PMC-based achieved-HBM
-fraction, dominant kernel), so that every BASELINE.json configuration is timed by whoever runs the
-benchmark; --no-configs skips them.
+fraction, dominant kernel), so that every BASELINE.json configuration is timed in one run;
+--no-configs skips them.  It also adds n1_same_image, odd_width, float64, float64_cfg3 and
+float64_cfg5.
 
 Two HBM fractions are reported, and they are different things:
   `frac` / `frac_of_hbm_peak`   SURVEY 8(d) ALGORITHMIC bytes (a property of the problem statement)
@@ -147,6 +161,38 @@ def step_spread(samples):
     med = v[n // 2] if n % 2 else 0.5 * (v[n // 2 - 1] + v[n // 2])
     return {"ms_per_step_median": round(med, 4), "ms_per_step_min": round(v[0], 4), "ms_per_step_max": round(v[-1], 4),
             "ms_per_step_samples": n}
+
+
+DUMP_SAMPLE = 1 << 20      # --dump-outputs: pixel positions kept per array of a larger image
+DUMP_SEED = 20261016
+
+
+def dump_outputs(dirname, plan, nplanes, scalars=None):
+    """--dump-outputs: what the last timed step left on `plan` - the coefficient planes 0 .. nplanes-1 and the
+    reconstruction (PLANE_OUT), the arrays the caller of the path receives - as DIR/coefficients.npy and
+    DIR/reconstruction.npy, float32.  An image of at most DUMP_SAMPLE pixels is written whole ((nplanes, H, W) and
+    (H, W)); a larger one at the same DUMP_SAMPLE pixel positions in every array (flat indices drawn with
+    np.random.default_rng(DUMP_SEED).integers(0, H * W), sorted): (nplanes, DUMP_SAMPLE) and (DUMP_SAMPLE,).
+    scalars: {name: value}, each written as a 1-element float64 array."""
+    import numpy as np
+    from wavelets_amd._lib import PLANE_OUT
+    os.makedirs(dirname, exist_ok=True)
+    buf = plan.download(0)
+    npix = buf.size
+    idx = None
+    if npix > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, npix, size=DUMP_SAMPLE))
+
+    def pick(a):
+        return np.ravel(a)[idx] if idx is not None else np.array(a, dtype=np.float32)
+    coeffs = [pick(buf)]
+    for s in range(1, nplanes):
+        coeffs.append(pick(plan.download(s, out=buf)))
+    np.save(os.path.join(dirname, "coefficients.npy"), np.stack(coeffs).astype(np.float32, copy=False))
+    del coeffs
+    np.save(os.path.join(dirname, "reconstruction.npy"), pick(plan.download(PLANE_OUT, out=buf)).astype(np.float32, copy=False))
+    for name, v in (scalars or {}).items():
+        np.save(os.path.join(dirname, name + ".npy"), np.array([v], dtype=np.float64))
 
 
 def scaling_text(world, H, W):
@@ -351,13 +397,13 @@ def main():
     ap.add_argument("--two-call", action="store_true",
                     help="decompose and plane sum as two calls (the sum re-reads the planes) "
                          "instead of wt_decompose_sum")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--no-build", action="store_true",
                     help="do not run __graft_entry__.build() (profiled runs: no child process "
                          "under the profiler's preload)")
     ap.add_argument("--brief", action="store_true", help="one short line (tuning sweeps)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="headline only: do not append cfg2 / cfg3 / cfg5 to the line")
+                    help="--full, headline only: do not append cfg2 / cfg3 / cfg5 to the line")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the launcher plumbing (gloo rendezvous, RCCL communicator) even "
                          "with one rank (plumbing check on a 1-GPU box)")
@@ -379,6 +425,13 @@ def main():
                          "behind the overlapped order would never run there)")
     ap.add_argument("--no-scatter-ab", action="store_true",
                     help="multi-rank runs: skip the A/B of the strip planes' placement (plain hipMalloc only)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: everything beyond the headline figure - per-step spread, per-kernel table and roofline, "
+                         "PCIe-inclusive rates, sequence, first call, CPU baseline, and (headline) the other configs, "
+                         "n1_same_image, odd widths and the float64 engine")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 planes; "
+                         "a fixed, seeded sample of pixels above 2^20 pixels per plane)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -483,9 +536,10 @@ def main():
     traffic_db, traffic_stale = load_traffic()                    # from rocprofv3 --pmc passes
     traffic_meta = traffic_db.get("_meta") or {}
 
-    def run_workload(config, steps, warmup, full):
+    def run_workload(config, steps, warmup, own_line):
         """Time `steps` steps of BASELINE configuration `config`; returns the JSON object (rank 0)
-        or None.  full: PCIe-inclusive rate and CPU baseline too (the line's own configuration)."""
+        or None.  own_line: the configuration the line is about (--dump-outputs writes its outputs;
+        with --full it gets the PCIe-inclusive rates and the longer CPU baseline too)."""
         side, family, level, what = CONFIGS[config]
         if config == "headline" and world > 1:
             side = 32768
@@ -574,9 +628,10 @@ def main():
                 elapsed = float(group.allreduce(elapsed, max))
             return elapsed, dev_ms
 
-        def measure(step, nsteps, spin=True):
-            """spin-up, warm-up, the timed region, then `nprof` more steps under the live per-kernel
-            profiler (HIP events on the launch streams)"""
+        def measure(step, nsteps, spin=True, after_timed=None):
+            """spin-up, warm-up, the timed region, `after_timed()` (if given), then - with --full, or with
+            more than one rank - per-step samples and `nprof` more steps under the live per-kernel profiler
+            (HIP events on the launch streams)"""
             # Untimed spin-up: the GPU idles at 94 MHz and its clocks ramp over the first milliseconds of
             # work; W = 3 warm-up steps are only 2.5 ms.  Run the same step for a quarter of a second so
             # that the timed region starts at steady clocks (measured: K = 5 reads 4 % low otherwise).
@@ -594,6 +649,10 @@ def main():
             for _ in range(warmup):
                 step()
             elapsed, dev_ms = timed(step, nsteps)
+            if after_timed is not None:
+                after_timed()
+            if world == 1 and not args.full:
+                return {"elapsed": elapsed, "dev_ms": dev_ms, "steps": nsteps, "prof_raw": {}, "nprof": 0, "samples": []}
             # the spread of the step, from one HIP-event pair per step on the launch stream (>= 20 samples;
             # the batch above stays the line's `value`: its steps run back to back, these are fenced one by one)
             samples = []
@@ -780,7 +839,7 @@ def main():
                 whole["hbm_achieved_GBs"] = round(step_traffic / (ms_per_step * 1e-3) / 1e9, 1)
                 whole["hbm_achieved"] = round(step_traffic / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
                 whole["hbm_traffic_source"] = "profiles/traffic.json (PMC passes, not re-measured here)"
-            elif traffic_stale and world == 1:
+            elif traffic_stale and world == 1 and nprof:
                 whole["hbm_achieved"] = None
                 whole["traffic_stale"] = True
             data = ("np.random.default_rng(0).standard_normal + 3*sin(x/50) along the columns (noise on a smooth "
@@ -809,6 +868,8 @@ def main():
                 "roofline": roofline,
                 "kernels": kernels,
             }
+            if not nprof:                             # (a lean N = 1 run profiles no kernels: nothing to report)
+                del out["roofline"], out["kernels"]
             if world > 1:
                 out["launcher"] = {"plumbing": args.launcher,
                                    "torch_imported_in_ranks": "torch" in sys.modules,
@@ -859,7 +920,14 @@ def main():
 
         plan = make_plan()
         step, coefficients = make_step(plan)
-        m = measure(step, steps)
+        dumped = []
+
+        def dump():                                   # (the first timed region only: what its last step computed)
+            if args.dump_outputs and own_line and rank == 0 and not dumped:
+                dump_outputs(args.dump_outputs, plan, level + 1,
+                             {"noise": float(coefficients.noise)} if getattr(coefficients, "noise", None) is not None else None)
+                dumped.append(True)
+        m = measure(step, steps, after_timed=dump)
         out = report(m)
         if world > 1 and out is not None:
             state["result"] = dict(out)               # a stall in a later phase reports at least this line
@@ -870,7 +938,7 @@ def main():
             pl.close()
 
         if world == 1:
-            if out is not None and full and config in ("headline", "cfg2") and not args.brief:
+            if out is not None and args.full and own_line and config in ("headline", "cfg2") and not args.brief:
                 # (not under --brief: the PMC passes of tools/profile_round.sh average per dispatch, and
                 #  the pipelined host call launches the same kernels on row blocks)
                 # PCIe-inclusive rate (host numpy in, reconstruction out as a numpy array) - never
@@ -957,9 +1025,9 @@ def main():
                                                           "context_ms": got_b.get(ctx_key), "first_ms": calls_b[0]}}
                     except Exception as e:
                         out["first_call"] = {"error": repr(e)}
-            if out is not None and not args.no_cpu and not args.brief:
+            if out is not None and args.full and not args.no_cpu and not args.brief:
                 out["cpu_baseline"] = cpu_baseline(config, side, family, level,
-                                                   budget=15.0 if full else 5.0)
+                                                   budget=15.0 if own_line else 5.0)
             release(plan, coefficients)
             return out
 
@@ -1172,8 +1240,8 @@ def main():
         _lib.set_option("overlap_reserve", 16)
         return out
 
-    out = run_workload(args.config, args.steps, args.warmup, full=True)
-    if (out is not None and args.config == "headline" and world == 1 and not args.no_configs
+    out = run_workload(args.config, args.steps, args.warmup, own_line=True)
+    if (out is not None and args.full and args.config == "headline" and world == 1 and not args.no_configs
             and not args.size and not args.rows and not args.unfused and not args.two_call
             and not args.brief):
         # every other single-GPU BASELINE.json configuration, timed in the same run
@@ -1183,7 +1251,7 @@ def main():
                 # (cfg2's step is 0.18 ms: 20 steps are a 3.6 ms timed region, which read 0.170-0.202 ms
                 #  across boxes and runs; 100 steps average over clock / power-state noise)
                 nst = {"cfg2": max(100, args.steps), "cfg3": max(5, min(args.steps, 20)), "cfg5": 5}[cfg]
-                o = run_workload(cfg, nst, args.warmup, full=False)
+                o = run_workload(cfg, nst, args.warmup, own_line=False)
             except Exception as e:          # never lose the headline line over an extra configuration
                 extra[cfg] = {"error": repr(e)}
                 continue

@@ -169,10 +169,10 @@ def test_bench_self_launches_four_ranks_on_the_shared_gpu():
 
 
 def test_bench_default_line_carries_every_config():
-    """`python bench.py` (the driver's command, shortened): ONE JSON line with the headline plus
+    """`python bench.py --full` (shortened): ONE JSON line with the headline plus
     cfg2 / cfg3 / cfg5 under "configs", both HBM fractions, and the labelled traffic source."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "1",
                         "--no-cpu", "--spinup", "0.05"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

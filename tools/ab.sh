@@ -2,5 +2,5 @@
 libs=(); args=()
 while [ $# -gt 0 ]; do if [ "$1" = "--" ]; then shift; args=("$@"); break; fi; libs+=("$1"); shift; done
 for rep in 1 2 3; do for l in "${libs[@]}"; do
-  echo "$(basename $l): $(WATROO_HIP_LIB=$PWD/$l python bench.py --no-cpu --brief --steps 30 "${args[@]}")"
+  echo "$(basename $l): $(WATROO_HIP_LIB=$PWD/$l python bench.py --full --no-cpu --brief --steps 30 "${args[@]}")"
 done; done

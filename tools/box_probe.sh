@@ -6,7 +6,7 @@ cd $R; mkdir -p gpurun_out/probe; O=gpurun_out/probe/probe.txt; : > $O
 rocm-smi --showuniqueid 2>/dev/null | grep -i unique | head -1 >> $O
 hipcc -O3 --offload-arch=gfx950 -o /tmp/membench tools/membench.hip 2>> $O
 /tmp/membench 8192 2>&1 | sort -t: -k2 -n | awk '{k=$1" "$2; if (!(k in seen)) {seen[k]=1; print}}' >> $O
-for i in 1 2; do python bench.py --brief --steps 30 --no-build --no-cpu >> $O 2>&1; done
+for i in 1 2; do python bench.py --full --brief --steps 30 --no-build --no-cpu >> $O 2>&1; done
 D=$(ls -d /sys/class/drm/card*/device 2>/dev/null | head -1)
 python bench.py --steps 20000 --no-build --no-cpu --brief > /tmp/long.txt 2>&1 &
 BP=$!

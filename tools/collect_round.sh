@@ -1,11 +1,11 @@
 #!/bin/bash
-# After `gpurun -- bash tools/profile_round.sh` has merged gpurun_out/final back: copy the summaries
+# After tools/profile_round.sh has filled $OUT (the same OUT, default profile_out): copy the summaries
 # the judge reads into profiles/<tag>_* and rebuild profiles/traffic.json (PMC bytes per launch, tied
-# to the kernel sources' digest).     usage: bash tools/collect_round.sh r04_a
+# to the kernel sources' digest).     usage: [OUT=dir] bash tools/collect_round.sh r04_a
 set -e
 cd "$(dirname "$0")/.."
 tag=${1:?tag}
-F=gpurun_out/final
+F=${OUT:-profile_out}
 cp $F/bench.json profiles/${tag}_bench.json
 cp $F/pytest_gpu.log profiles/${tag}_pytest_gpu.log
 for c in headline cfg2 cfg3 cfg5; do
