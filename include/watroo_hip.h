@@ -575,6 +575,45 @@ int wt64_fft_apply(wt_plan64 *plan, int src, int dst, int conj);
 int wt64_anscombe(wt_plan64 *plan, int src, int dst, double alpha, double g, double sigma,
                   int inverse);
 
+/* ---- batches of same-shape frames (float32) ------------------------------------------------
+ * A wt_batch holds the planes of N frames of one H x W shape back to back (frame f at f * frame_stride
+ * floats, rows of the pitch a wt_plan of that width has): every fused pass of the schedule runs over the
+ * active frames in ONE launch (the frame is a grid dimension), pointwise steps run once over the stack.
+ * A frame's result is bit-identical to the per-frame call on a wt_plan.  Only schedules whose passes are
+ * all fused (wt_plan_fused_ok) run here; built-in families only.  Every operation takes the number of
+ * ACTIVE frames nf (frames 0 .. nf-1; the last chunk of a stack may be shorter than the batch).
+ * Planes: 0..max_level, WT_PLANE_INPUT, WT_PLANE_OUT, WT_PLANE_SCRATCH(0/1) (scratch used internally). */
+typedef struct wt_batch wt_batch;
+int wt_batch_create(wt_ctx *ctx, int n, int H, int W, int family, int max_level, wt_batch **batch);
+int wt_batch_destroy(wt_batch *batch);
+/* info[7] = {n, H, W, pitch, frame_stride, max_level, family} */
+int wt_batch_info(wt_batch *batch, int64_t *info);
+/* frames [f0, f0+nf) of a plane <- / -> host frames of H x W contiguous floats, host_frame_stride floats apart
+ * (0 = H * W: a C-contiguous (nf, H, W) block, np.stack of the frames) */
+int wt_batch_upload(wt_batch *batch, int plane, int f0, int nf, const float *host, int64_t host_frame_stride);
+int wt_batch_download(wt_batch *batch, int plane, int f0, int nf, float *host, int64_t host_frame_stride);
+/* device pointer of frame 0 of a plane (allocated on first use) and the frame stride in floats */
+int wt_batch_plane_ptr(wt_batch *batch, int plane, void **ptr, int64_t *frame_stride);
+/* wt_decompose per frame (watroo/wavelets.py:408-444 via AtrousTransform.__call__, ref:307-328); flags bit0 */
+int wt_batch_decompose(wt_batch *batch, int nf, int src, int level, int flags);
+/* wt_decompose_sum per frame: planes + np.sum(planes, axis=0) (watroo/utils.py:98) in the same passes */
+int wt_batch_decompose_sum(wt_batch *batch, int nf, int src, int level, int dst, int flags);
+/* wt_decompose_pass / wt_decompose_pass_sum per frame (utils.denoise, watroo/utils.py:95-98, interleaved) */
+int wt_batch_decompose_pass(wt_batch *batch, int nf, int cur, int nxt, int s0, int ns, int flags);
+int wt_batch_decompose_pass_sum(wt_batch *batch, int nf, int cur, int nxt, int s0, int ns, int flags,
+                                int sum_plane, int first, int last);
+/* np.median(np.abs(data[0])) of every active frame (watroo/wavelets.py:127): medians[nf], exact, one
+ * host round trip; a frame that holds NaN is an error naming the frame */
+int wt_batch_abs_median(wt_batch *batch, int nf, int plane, float *medians);
+/* wt_denoise_sum per frame (Coefficients.denoise + np.sum, watroo/wavelets.py:145-149, utils.py:97-98):
+ * planes 0..count-1, the first n_den thresholded at tau[frame * n_den + k] (<= 0: significance one),
+ * weights wgt[k] shared by the frames; scalar noise only */
+int wt_batch_denoise_sum(wt_batch *batch, int nf, int count, int dst, int n_den, const double *tau,
+                         const double *wgt, int soft, int write_back);
+/* generalized_anscombe over the active frames (watroo/utils.py:93-94, 99-100; as wt_anscombe) */
+int wt_batch_anscombe(wt_batch *batch, int nf, int src, int dst, float alpha, float g, float sigma,
+                      int inverse);
+
 #ifdef __cplusplus
 }
 #endif

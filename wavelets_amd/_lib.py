@@ -195,6 +195,23 @@ SIGNATURES = {
                                  _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "wt64_mrs_update": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int,
                                    _c.c_int, _c.c_double]),
+    # batches of same-shape frames (wt_batch)
+    "wt_batch_create": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_vp)]),
+    "wt_batch_destroy": (_c.c_int, [_vp]),
+    "wt_batch_info": (_c.c_int, [_vp, _c.POINTER(_i64)]),
+    "wt_batch_upload": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _fp, _i64]),
+    "wt_batch_download": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _fp, _i64]),
+    "wt_batch_plane_ptr": (_c.c_int, [_vp, _c.c_int, _c.POINTER(_vp), _c.POINTER(_i64)]),
+    "wt_batch_decompose": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch_decompose_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch_decompose_pass": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch_decompose_pass_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                               _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch_abs_median": (_c.c_int, [_vp, _c.c_int, _c.c_int, _fp]),
+    "wt_batch_denoise_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
+                                        _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
+    "wt_batch_anscombe": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float,
+                                     _c.c_int]),
 }
 
 _lib = None
@@ -375,7 +392,7 @@ def _shutdown():
     otherwise destroys planes after the runtime's own static destructors ran)."""
     _host_pool.close()
     objs = list(_live)
-    for kind in ((Plan, Plan64), (Context,)):
+    for kind in ((Plan, Plan64, BatchPlan), (Context,)):
         for o in objs:
             if isinstance(o, kind):
                 try:
@@ -385,6 +402,7 @@ def _shutdown():
     _default_ctx.clear()
     _lane_ctx.clear()
     del _pool[:]
+    _batch_cache.clear()
 
 
 _tls = threading.local()          # .ctx: the context the API calls of THIS thread run on (use_context)
@@ -864,6 +882,139 @@ class Plan:
 
     def anscombe(self, src, dst, alpha=1.0, g=0.0, sigma=0.0, inverse=False):
         check(load().wt_anscombe(self._h, src, dst, alpha, g, sigma, int(inverse)))
+
+
+# ------------------------------------------------------------------------------------------
+# batches of same-shape frames (wt_batch): every fused pass runs over all frames in one launch
+# ------------------------------------------------------------------------------------------
+BATCH_MAX_FRAMES = 65535                  # grid z of the fused launches (one frame per z slice)
+BATCH_BYTES = int(os.environ.get("WATROO_HIP_BATCH_BYTES", str(4 << 30)))   # device bytes of one chunk of frames
+
+
+def batch_frame_bytes(H, W, level):
+    """device bytes one frame of a batch takes: planes 0..level, input, output and two scratch planes at the
+    plan pitch (host logic, wt_batch_create)"""
+    return (level + 5) * H * ((W + 3) // 4 * 4) * 4
+
+
+def batch_chunks(n, H, W, level, budget=None, max_frames=BATCH_MAX_FRAMES):
+    """[(first frame, frames)] of a stack of `n` frames: as many frames per chunk as `budget` bytes of planes
+    (default BATCH_BYTES; at least one frame) and the grid allow, the last chunk the remainder."""
+    if n < 0:
+        raise ValueError("negative frame count")
+    budget = BATCH_BYTES if budget is None else budget
+    per = max(1, min(int(budget // batch_frame_bytes(H, W, level)), int(max_frames)))
+    return [(f0, min(per, n - f0)) for f0 in range(0, n, per)]
+
+
+class BatchPlan:
+    """Device planes of up to `n` frames of one H x W shape (wt_batch).  Operations take the number of
+    active frames `nf` (frames 0 .. nf-1); upload / download move a C-contiguous (nf, H, W) block."""
+
+    def __init__(self, ctx, n, H, W, family, max_level):
+        self._h = _vp()
+        self.ctx = ctx
+        check(load().wt_batch_create(ctx._h, n, H, W, family, max_level, _c.byref(self._h)))
+        info = (_i64 * 7)()
+        check(load().wt_batch_info(self._h, info))
+        (self.n, self.H, self.W, self.pitch, self.frame_stride, self.max_level, self.family) = [int(v) for v in info]
+        _live.add(self)
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, _vp()
+            check(load().wt_batch_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def upload(self, plane, frames, f0=0):
+        a = np.ascontiguousarray(frames, dtype=np.float32)
+        if a.ndim != 3 or a.shape[1:] != (self.H, self.W):
+            raise ValueError(f"frames of shape {a.shape[1:]} != batch frame shape {(self.H, self.W)}")
+        check(load().wt_batch_upload(self._h, plane, f0, a.shape[0], a.ctypes.data_as(_fp), 0))
+
+    def download(self, plane, nf, out=None, f0=0):
+        """(nf, H, W) float32; `out` may be any (nf, H, W) view whose frames are C-contiguous (e.g. cube[:, s] of
+        an (N, L, H, W) array): the frames land in place, page-locked result blocks by default (host_empty)"""
+        if out is None:
+            out = host_empty((nf, self.H, self.W), self.ctx)
+        assert out.dtype == np.float32 and out.shape == (nf, self.H, self.W) and out.flags.writeable
+        assert out.strides[1:] == (self.W * 4, 4) and out.strides[0] % 4 == 0 and out.strides[0] >= self.H * self.W * 4
+        check(load().wt_batch_download(self._h, plane, f0, nf, out.ctypes.data_as(_fp), out.strides[0] // 4))
+        return out
+
+    def plane_ptr(self, plane):
+        """(device pointer of frame 0, frame stride in floats)"""
+        p, st = _vp(), _i64()
+        check(load().wt_batch_plane_ptr(self._h, plane, _c.byref(p), _c.byref(st)))
+        return p.value, int(st.value)
+
+    def decompose(self, nf, src, level, flags=FLAG_FUSED):
+        check(load().wt_batch_decompose(self._h, nf, src, level, flags))
+
+    def decompose_sum(self, nf, src, level, dst=PLANE_OUT, flags=FLAG_FUSED):
+        check(load().wt_batch_decompose_sum(self._h, nf, src, level, dst, flags))
+
+    def decompose_pass(self, nf, cur, nxt, s0, ns, flags=FLAG_FUSED):
+        check(load().wt_batch_decompose_pass(self._h, nf, cur, nxt, s0, ns, flags))
+
+    def decompose_pass_sum(self, nf, cur, nxt, s0, ns, flags, sum_plane, first, last):
+        check(load().wt_batch_decompose_pass_sum(self._h, nf, cur, nxt, s0, ns, flags, sum_plane, int(first), int(last)))
+
+    def abs_median(self, nf, plane):
+        """np.median(np.abs(frame)) of `plane` for frames 0 .. nf-1 (np.float32 each)"""
+        m = (_c.c_float * nf)()
+        check(load().wt_batch_abs_median(self._h, nf, plane, m))
+        return [np.float32(v) for v in m]
+
+    def denoise_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT):
+        """`taus`: one row of thresholds per active frame (all rows of one length n_den)"""
+        n = len(wgts)
+        if len(taus) != nf or any(len(t) != n for t in taus):
+            raise ValueError("denoise_sum: one row of len(wgts) thresholds per frame")
+        ta = (_c.c_double * max(nf * n, 1))(*[float(t) for row in taus for t in row])
+        wa = (_c.c_double * max(n, 1))(*[float(w) for w in wgts])
+        check(load().wt_batch_denoise_sum(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back)))
+
+    def anscombe(self, nf, src, dst, alpha=1.0, g=0.0, sigma=0.0, inverse=False):
+        check(load().wt_batch_anscombe(self._h, nf, src, dst, alpha, g, sigma, int(inverse)))
+
+
+_batch_cache = {}        # id(ctx) -> [BatchPlan], most recently used last (its own small cache: not the plan pool)
+_BATCH_CACHE_MAX = 2
+
+
+def acquire_batch(ctx, n, H, W, family, max_level):
+    """A BatchPlan of at least `n` frames of (H, W, family, max_level) on `ctx`: cached if available, else new."""
+    with _pool_lock:
+        lst = _batch_cache.setdefault(id(ctx), [])
+        for i, b in enumerate(lst):
+            if b._h and b.ctx is ctx and (b.H, b.W, b.family, b.max_level) == (H, W, family, max_level) and b.n >= n:
+                return lst.pop(i)
+    return BatchPlan(ctx, n, H, W, family, max_level)
+
+
+def trim_batches():
+    """Release the device memory of every cached BatchPlan (the cache keeps at most two per context)."""
+    with _pool_lock:
+        lst = [b for v in _batch_cache.values() for b in v]
+        _batch_cache.clear()
+    for b in lst:
+        b.close()
+
+
+def release_batch(b):
+    if b is None or not b._h:
+        return
+    with _pool_lock:
+        lst = _batch_cache.setdefault(id(b.ctx), [])
+        lst.append(b)
+        while len(lst) > _BATCH_CACHE_MAX:
+            lst.pop(0).close()
 
 
 # ------------------------------------------------------------------------------------------

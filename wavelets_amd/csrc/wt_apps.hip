@@ -258,14 +258,19 @@ extern "C" int wt_anscombe(wt_plan *p, int src, int dst, float alpha, float g, f
     float *s = nullptr, *d = nullptr;
     WT_TRY(plane_base(p, src, &s));
     WT_TRY(plane_base(p, dst, &d));
+    return launch_anscombe(p->ctx, s, d, plan_n4(p), alpha, g, sigma, inverse);
+}
+
+// (wt_anscombe and wt_batch_anscombe: n4 float4 groups of contiguous planes)
+int launch_anscombe(wt_ctx *c, const float *s, float *d, int64_t n4, float alpha, float g, float sigma, int inverse)
+{
     // scalar terms are formed in double like the python floats of wavelets.py:17,19
     const double a = alpha, gg = g, sg = sigma;
     float c1, c2, c3;
     if (inverse) { c1 = (float)(a * gg); c2 = (float)(sg * sg); c3 = (float)(3.0 * a / 8.0); }
     else { c1 = (float)(3.0 * a * a / 8.0); c2 = (float)(sg * sg); c3 = (float)(a * gg); }
-    const int64_t n4 = plan_n4(p);
-    ProfScope ps(p->ctx, "wt_anscombe_kernel");
-    hipLaunchKernelGGL(wt_anscombe_kernel, dim3(flat_grid(n4)), dim3(256), 0, p->ctx->stream, s, d, n4, alpha, c1, c2, c3, inverse);
+    ProfScope ps(c, "wt_anscombe_kernel");
+    hipLaunchKernelGGL(wt_anscombe_kernel, dim3(flat_grid(n4)), dim3(256), 0, c->stream, s, d, n4, alpha, c1, c2, c3, inverse);
     WT_HIP(hipGetLastError());
     return 0;
 }

@@ -1,0 +1,487 @@
+// Batched float32 engine (wt_batch): N frames of the same H x W go through each fused pass in ONE launch,
+// the frame index a grid dimension (blockIdx.z, wt_fused.h), instead of one API call per frame.
+//
+// Layout: every plane of the batch is one allocation of N frames back to back, frame f at f * H * P floats
+// (P = the pitch of a wt_plan of the same width).  A plane is therefore also ONE tall image of N * H rows:
+// pointwise work (transfers, Anscombe, the fused thresholds + plane sum) runs once over the whole stack.
+// Only the fused passes see frames: each frame is its own image there (row reflection at the frame's
+// borders), so a frame's bits are those of the per-frame call on a wt_plan of the same shape.
+// The MAD median is a per-frame radix select (three histogram levels, 11 + 10 + 10 bits of |x|, the
+// levels of wt_abs_median) over all frames at once, two ranks per frame for the upper median of an
+// even pixel count: N medians for one host round trip.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "wt_host.h"
+#include "wt_fused_decl.h"
+#include "wt_unit_probe.h"
+
+WT_UNIT_PROBE_DEFINE
+
+struct WtBatchSel {                 // select state of one rank of one frame
+    unsigned long long k;           // rank still to find among the keys matching `prefix`
+    uint32_t prefix;                // key bits fixed so far
+    uint32_t nan;                   // NaN pixels of the frame (counted by the first level)
+};
+
+struct wt_batch {
+    wt_ctx *ctx = nullptr;
+    wt_plan geo;                    // ONE frame's geometry, context and family: what the fused launches read (no planes)
+    int n = 0, max_level = 0;
+    int64_t fstride = 0;            // floats from one frame to the next (H * P)
+    std::vector<float *> coef;      // planes 0 .. max_level
+    float *input = nullptr, *out = nullptr, *scr[2] = {nullptr, nullptr};
+    uint32_t *d_hist = nullptr;     // [n][2 ranks][WT_HIST_BINS]
+    WtBatchSel *d_sel = nullptr;    // [n][2 ranks]
+    WtBatchSel *h_sel = nullptr;    // pinned copy
+    double *d_tau = nullptr;        // [n][WT_MAX_SUM_PLANES] thresholds of wt_batch_denoise_sum
+    double *h_tau = nullptr;        // pinned staging of the table
+};
+
+// ------------------------------------------------------------------------------------------------ kernels
+// One radix level of the per-frame select: bins of (key >> shift) & bmask over the keys of frame blockIdx.y
+// that match a rank's prefix (key = magnitude bits of a float: their order is the order of |x|).
+__global__ __launch_bounds__(256) void wt_batch_hist_kernel(const float *p, int H, int P, int W, int64_t fstride, uint32_t mask, int shift,
+                                                            uint32_t bmask, WtBatchSel *st, uint32_t *hist)
+{
+    __shared__ uint32_t lh[2][WT_HIST_BINS];
+    __shared__ uint32_t lnan;
+    const int f = blockIdx.y;
+    for (int i = threadIdx.x; i < 2 * WT_HIST_BINS; i += 256) lh[i / WT_HIST_BINS][i % WT_HIST_BINS] = 0;
+    if (threadIdx.x == 0) lnan = 0;
+    __syncthreads();
+    const uint32_t pre0 = st[2 * f].prefix, pre1 = st[2 * f + 1].prefix;
+    const float *fp = p + (int64_t)f * fstride;
+    const int W4 = (W + 3) / 4;
+    const int64_t items = (int64_t)H * W4;
+    uint32_t nan = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (int64_t)gridDim.x * 256) {
+        const int row = (int)(i / W4), c4 = (int)(i % W4);
+        const float4 v = *reinterpret_cast<const float4 *>(fp + (int64_t)row * P + 4 * c4);
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (4 * c4 + j >= W) continue;
+            const uint32_t key = __float_as_uint(e[j]) & 0x7fffffffu;
+            nan += key > 0x7f800000u;
+            if ((key & mask) == pre0) atomicAdd(&lh[0][(key >> shift) & bmask], 1u);
+            if ((key & mask) == pre1) atomicAdd(&lh[1][(key >> shift) & bmask], 1u);
+        }
+    }
+    if (nan) atomicAdd(&lnan, nan);
+    __syncthreads();
+    uint32_t *gh = hist + (int64_t)f * 2 * WT_HIST_BINS;
+    for (int i = threadIdx.x; i < 2 * WT_HIST_BINS; i += 256) {
+        const uint32_t c = lh[i / WT_HIST_BINS][i % WT_HIST_BINS];
+        if (c) atomicAdd(&gh[i], c);
+    }
+    if (threadIdx.x == 0 && lnan && shift == 20) atomicAdd(&st[2 * f].nan, lnan);
+}
+
+// The bin of one rank (block = frame * 2 + rank): fixes bmask's bits of the prefix, leaves the bins cleared.
+__global__ __launch_bounds__(256) void wt_batch_select_kernel(uint32_t *hist, WtBatchSel *st, int nbins, int shift)
+{
+    __shared__ unsigned long long part[256];
+    __shared__ int sel_t;
+    __shared__ unsigned long long sel_before;
+    uint32_t *h = hist + (int64_t)blockIdx.x * WT_HIST_BINS;
+    const int per = nbins / 256;
+    unsigned long long s = 0;
+    for (int i = 0; i < per; ++i) s += h[threadIdx.x * per + i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    WtBatchSel &S = st[blockIdx.x];
+    if (threadIdx.x == 0) {
+        unsigned long long cum = 0;
+        int t = 255;
+        for (int i = 0; i < 256; ++i) {
+            if (cum + part[i] > S.k) { t = i; break; }
+            cum += part[i];
+        }
+        sel_t = t;
+        sel_before = cum;
+    }
+    __syncthreads();
+    if (threadIdx.x == sel_t) {
+        unsigned long long cum = sel_before;
+        int b = threadIdx.x * per + per - 1;
+        for (int i = 0; i < per; ++i) {
+            const uint32_t c = h[threadIdx.x * per + i];
+            if (cum + c > S.k) { b = threadIdx.x * per + i; break; }
+            cum += c;
+        }
+        S.prefix |= (uint32_t)b << shift;
+        S.k -= cum;
+    }
+    __syncthreads();
+    for (int i = 0; i < per; ++i) h[threadIdx.x * per + i] = 0;
+}
+
+// wt_denoise_sum_kernel (wt_kernels_apps.h) with one threshold row per frame: tau[frame * n_den + k], the frame
+// from the flat index.  Same arithmetic (no noise plane: nn = 1), contraction off: the bits of the per-frame call.
+struct BatchDenoiseArgs {
+    float *p[WT_MAX_SUM_PLANES];
+    float wgt[WT_MAX_SUM_PLANES];
+    int n, n_den, soft, write_back;
+};
+__global__ __launch_bounds__(256) void wt_batch_denoise_sum_kernel(BatchDenoiseArgs a, const double *tau, float *out, int64_t n4, int64_t f4)
+{
+#pragma clang fp contract(off)
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const double *ft = tau + (i / f4) * a.n_den;
+        const float nn[4] = {1.f, 1.f, 1.f, 1.f};
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < a.n; ++k) {
+            const float4 v = reinterpret_cast<const float4 *>(a.p[k])[i];
+            float c[4] = {v.x, v.y, v.z, v.w};
+            if (k < a.n_den) {
+                const double t = ft[k];
+                const float tauf = (float)t;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float sgn = t > 0.0 ? wt_sig(c[j], tauf * nn[j], t * (double)nn[j], a.soft) : 1.f;
+                    c[j] = c[j] * (a.wgt[k] * sgn);
+                }
+                if (a.write_back) reinterpret_cast<float4 *>(a.p[k])[i] = make_float4(c[0], c[1], c[2], c[3]);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = k == 0 ? c[j] : acc[j] + c[j];
+        }
+        reinterpret_cast<float4 *>(out)[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+static int bplane(wt_batch *b, int id, float **out)
+{
+    float **slot = nullptr;
+    if (id >= 0 && id <= b->max_level) slot = &b->coef[id];
+    else if (id == WT_PLANE_INPUT) slot = &b->input;
+    else if (id == WT_PLANE_OUT) slot = &b->out;
+    else if (id == WT_PLANE_SCRATCH(0)) slot = &b->scr[0];
+    else if (id == WT_PLANE_SCRATCH(1)) slot = &b->scr[1];
+    if (!slot) WT_FAIL("wt_batch: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1)", id, b->max_level);
+    if (!*slot) WT_HIP(hipMalloc((void **)slot, (size_t)b->n * (size_t)b->fstride * sizeof(float)));
+    *out = *slot;
+    return 0;
+}
+
+static int check_frames(const wt_batch *b, int nf, const char *who)
+{
+    if (!b) WT_FAIL("%s: null batch", who);
+    if (nf < 1 || nf > b->n) WT_FAIL("%s: %d active frames (batch of %d)", who, nf, b->n);
+    return 0;
+}
+
+// the fused schedule of `level` scales, or an error: a batch runs fused passes only
+static int batch_schedule(wt_batch *b, int level, int32_t *tr, int *np, const char *who)
+{
+    if (level < 1 || level > b->max_level) WT_FAIL("%s: level %d outside [1, %d]", who, level, b->max_level);
+    WT_TRY(wt_schedule(b->geo.family, level, 1, tr, 32, np));
+    for (int i = 0; i < *np; ++i)
+        if (!wt_fused_has_pass(tr[3 * i], tr[3 * i + 1], b->geo.family))
+            WT_FAIL("%s: %d scales have no all-fused schedule (wt_plan_fused_ok): not a batch case", who, level);
+    return 0;
+}
+
+static int batch_pass(wt_batch *b, int nf, int cur, int nxt, int s0, int ns, int acc, int sum_plane, bool first)
+{
+    if (ns < 1 || ns > WT_FUSED_MAX_SCALES || s0 < 0 || s0 + ns - 1 > b->max_level)
+        WT_FAIL("wt_batch_decompose_pass: scales [%d,%d) outside the batch (max_level %d)", s0, s0 + ns, b->max_level);
+    if (cur == nxt || (cur >= s0 && cur < s0 + ns) || (nxt >= s0 && nxt < s0 + ns))
+        WT_FAIL("wt_batch_decompose_pass: input/output planes alias the detail planes of the pass");
+    if (!wt_fused_has_pass(s0, ns, b->geo.family)) WT_FAIL("wt_batch_decompose_pass: no fused kernel for first scale %d x %d scales", s0, ns);
+    if (acc && first != (s0 == 0))
+        WT_FAIL("wt_batch_decompose_pass_sum: first must be set for the pass that starts at scale 0 and only for it (got first=%d, s0=%d)", (int)first, s0);
+    float *in = nullptr, *oc = nullptr, *ps = nullptr;
+    WT_TRY(bplane(b, cur, &in));
+    WT_TRY(bplane(b, nxt, &oc));
+    float *ow[WT_FUSED_MAX_SCALES] = {nullptr};
+    for (int k = 0; k < ns; ++k) WT_TRY(bplane(b, s0 + k, &ow[k]));
+    if (acc) {
+        if (sum_plane == cur || sum_plane == nxt || (sum_plane >= s0 && sum_plane < s0 + ns))
+            WT_FAIL("wt_batch_decompose_pass_sum: the sum plane aliases a plane of the pass");
+        WT_TRY(bplane(b, sum_plane, &ps));
+    }
+    FusedRows rows;
+    rows.frames = nf;
+    rows.fstride = b->fstride;
+    return wt_fused_launch(&b->geo, in, oc, ow, s0, ns, acc, first ? nullptr : ps, ps, rows);
+}
+
+static int batch_schedule_run(wt_batch *b, int nf, int src, int level, bool with_sum, int dst, const char *who)
+{
+    if (src >= 0 && src <= level) WT_FAIL("%s: src plane %d is one of the output planes", who, src);
+    if (src == WT_PLANE_SCRATCH(0) || src == WT_PLANE_SCRATCH(1)) WT_FAIL("%s: scratch planes 0/1 are used internally", who);
+    if (with_sum && ((dst >= 0 && dst <= level) || dst == src || dst == WT_PLANE_SCRATCH(0) || dst == WT_PLANE_SCRATCH(1)))
+        WT_FAIL("%s: dst plane %d is an input / output / internal plane of the transform", who, dst);
+    int32_t tr[3 * 32];
+    int np = 0;
+    WT_TRY(batch_schedule(b, level, tr, &np, who));
+    int cur = src;
+    for (int i = 0; i < np; ++i) {
+        const int s0 = tr[3 * i], ns = tr[3 * i + 1];
+        const bool last = s0 + ns == level;
+        const int nxt = last ? level : WT_PLANE_SCRATCH(i & 1);
+        WT_TRY(batch_pass(b, nf, cur, nxt, s0, ns, with_sum ? (last ? 2 : 1) : 0, dst, i == 0));
+        cur = nxt;
+    }
+    return 0;
+}
+
+extern "C" int wt_batch_create(wt_ctx *ctx, int n, int H, int W, int family, int max_level, wt_batch **out)
+{
+    WtGuard guard_(ctx);
+    if (!ctx || !out) WT_FAIL("wt_batch_create: null pointer");
+    *out = nullptr;
+    if (n < 1 || n > 65535) WT_FAIL("wt_batch_create: %d frames (1..65535 per batch)", n);
+    if (H < 1 || W < 1) WT_FAIL("wt_batch_create: frame %d x %d", H, W);
+    if (family != WT_B3SPLINE && family != WT_TRIANGLE) WT_FAIL("wt_batch_create: family %d (built-in families only)", family);
+    if (max_level < 0 || max_level > 30) WT_FAIL("wt_batch_create: max_level %d", max_level);
+    wt_batch *b = new wt_batch;
+    b->ctx = ctx;
+    b->n = n;
+    b->max_level = max_level;
+    b->geo.ctx = ctx;
+    b->geo.family = family;
+    b->geo.max_level = max_level;
+    b->geo.g = Geo{W, (W + 3) / 4 * 4, H, 0, H, 0, 0};
+    b->fstride = (int64_t)H * b->geo.g.P;
+    b->coef.assign(max_level + 1, nullptr);
+    if (!wt_fused_supported(&b->geo)) {
+        delete b;
+        WT_FAIL("wt_batch_create: rows of %d pixels are too wide for the fused passes", W);
+    }
+    auto fail = [&](hipError_t e) -> int {
+        (void)hipFree(b->d_hist);
+        (void)hipFree(b->d_sel);
+        (void)hipFree(b->d_tau);
+        (void)hipHostFree(b->h_sel);
+        (void)hipHostFree(b->h_tau);
+        delete b;
+        wt_set_error("wt_batch_create: HIP error %d (%s)", (int)e, hipGetErrorString(e));
+        return 2;
+    };
+    hipError_t e = hipMalloc((void **)&b->d_hist, (size_t)n * 2 * WT_HIST_BINS * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_sel, (size_t)n * 2 * sizeof(WtBatchSel));
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_tau, (size_t)n * WT_MAX_SUM_PLANES * sizeof(double));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_sel, (size_t)n * 2 * sizeof(WtBatchSel), 0);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_tau, (size_t)n * WT_MAX_SUM_PLANES * sizeof(double), 0);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_hist, 0, (size_t)n * 2 * WT_HIST_BINS * sizeof(uint32_t), ctx->stream);
+    if (e != hipSuccess) return fail(e);
+    *out = b;
+    return 0;
+}
+
+extern "C" int wt_batch_destroy(wt_batch *b)
+{
+    if (!b) return 0;
+    WtGuard guard_(b->ctx);
+    (void)hipStreamSynchronize(b->ctx->stream);
+    int bad = 0;
+    auto f = [&](void *q) { if (q && hipFree(q) != hipSuccess) bad = 1; };
+    for (float *q : b->coef) f(q);
+    f(b->input);
+    f(b->out);
+    f(b->scr[0]);
+    f(b->scr[1]);
+    f(b->d_hist);
+    f(b->d_sel);
+    f(b->d_tau);
+    if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) bad = 1;
+    if (b->h_tau && hipHostFree(b->h_tau) != hipSuccess) bad = 1;
+    delete b;
+    if (bad) WT_FAIL("wt_batch_destroy: a device buffer could not be released");
+    return 0;
+}
+
+extern "C" int wt_batch_info(wt_batch *b, int64_t *info)
+{
+    if (!b || !info) WT_FAIL("wt_batch_info: null pointer");
+    const Geo &g = b->geo.g;
+    const int64_t v[7] = {b->n, g.H, g.W, g.P, b->fstride, b->max_level, b->geo.family};
+    memcpy(info, v, sizeof v);
+    return 0;
+}
+
+extern "C" int wt_batch_plane_ptr(wt_batch *b, int plane, void **ptr, int64_t *frame_stride)
+{
+    if (!b || !ptr || !frame_stride) WT_FAIL("wt_batch_plane_ptr: null pointer");
+    WtGuard guard_(b->ctx);
+    float *q = nullptr;
+    WT_TRY(bplane(b, plane, &q));
+    *ptr = q;
+    *frame_stride = b->fstride;
+    return 0;
+}
+
+// frames [f0, f0 + nf) of a plane <-> host frames `hstride` floats apart (rows of W floats back to back within a frame)
+static int batch_copy(wt_batch *b, int plane, int f0, int nf, float *host, int64_t hstride, bool up, const char *who)
+{
+    if (!b || !host) WT_FAIL("%s: null pointer", who);
+    if (f0 < 0 || nf < 1 || f0 + nf > b->n) WT_FAIL("%s: frames [%d, %d) outside the batch of %d", who, f0, f0 + nf, b->n);
+    const Geo &g = b->geo.g;
+    const int64_t fpx = (int64_t)g.H * g.W;
+    if (hstride == 0) hstride = fpx;
+    if (hstride < fpx) WT_FAIL("%s: host frame stride %lld below the %lld pixels of a frame", who, (long long)hstride, (long long)fpx);
+    WtGuard guard_(b->ctx);
+    WT_TRY(wt_side_join(b->ctx));
+    float *q = nullptr;
+    WT_TRY(bplane(b, plane, &q));
+    float *dev = q + (int64_t)f0 * b->fstride;
+    const size_t span = ((size_t)(nf - 1) * (size_t)hstride + (size_t)fpx) * 4;
+    const bool pinned = try_pin(host, span);     // (no-op for page-locked blocks: _lib.host_empty)
+    hipError_t e = hipSuccess;
+    // contiguous frames are one tall image of nf * H rows; else one 2-D copy per frame
+    const int pieces = hstride == fpx ? 1 : nf;
+    const size_t rows = (size_t)g.H * (size_t)(hstride == fpx ? nf : 1);
+    for (int i = 0; i < pieces && e == hipSuccess; ++i) {
+        float *d = dev + (int64_t)i * b->fstride, *h = host + (int64_t)i * hstride;
+        e = up ? hipMemcpy2DAsync(d, (size_t)g.P * 4, h, (size_t)g.W * 4, (size_t)g.W * 4, rows, hipMemcpyHostToDevice, b->ctx->stream)
+               : hipMemcpy2DAsync(h, (size_t)g.W * 4, d, (size_t)g.P * 4, (size_t)g.W * 4, rows, hipMemcpyDeviceToHost, b->ctx->stream);
+    }
+    hipError_t e2 = hipStreamSynchronize(b->ctx->stream);
+    if (e == hipSuccess) e = e2;
+    if (pinned) (void)hipHostUnregister(host);
+    WT_HIP(e);
+    return 0;
+}
+
+extern "C" int wt_batch_upload(wt_batch *b, int plane, int f0, int nf, const float *host, int64_t host_frame_stride)
+{
+    return batch_copy(b, plane, f0, nf, const_cast<float *>(host), host_frame_stride, true, "wt_batch_upload");
+}
+
+extern "C" int wt_batch_download(wt_batch *b, int plane, int f0, int nf, float *host, int64_t host_frame_stride)
+{
+    return batch_copy(b, plane, f0, nf, host, host_frame_stride, false, "wt_batch_download");
+}
+
+extern "C" int wt_batch_decompose(wt_batch *b, int nf, int src, int level, int flags)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_decompose"));
+    WtGuard guard_(b->ctx);
+    if (!(flags & 1)) WT_FAIL("wt_batch_decompose: a batch runs the fused passes (flags bit0)");
+    if (level == 0) {
+        float *s = nullptr, *d = nullptr;
+        if (src == 0) WT_FAIL("wt_batch_decompose: src plane 0 is the output plane");
+        WT_TRY(bplane(b, src, &s));
+        WT_TRY(bplane(b, 0, &d));
+        WT_HIP(hipMemcpyAsync(d, s, (size_t)nf * (size_t)b->fstride * 4, hipMemcpyDeviceToDevice, b->ctx->stream));
+        return 0;
+    }
+    return batch_schedule_run(b, nf, src, level, false, WT_PLANE_NONE, "wt_batch_decompose");
+}
+
+extern "C" int wt_batch_decompose_sum(wt_batch *b, int nf, int src, int level, int dst, int flags)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_decompose_sum"));
+    WtGuard guard_(b->ctx);
+    if (!(flags & 1)) WT_FAIL("wt_batch_decompose_sum: a batch runs the fused passes (flags bit0)");
+    return batch_schedule_run(b, nf, src, level, true, dst, "wt_batch_decompose_sum");
+}
+
+extern "C" int wt_batch_decompose_pass(wt_batch *b, int nf, int cur, int nxt, int s0, int ns, int flags)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_decompose_pass"));
+    WtGuard guard_(b->ctx);
+    if (!(flags & 1)) WT_FAIL("wt_batch_decompose_pass: a batch runs the fused passes (flags bit0)");
+    return batch_pass(b, nf, cur, nxt, s0, ns, 0, WT_PLANE_NONE, false);
+}
+
+extern "C" int wt_batch_decompose_pass_sum(wt_batch *b, int nf, int cur, int nxt, int s0, int ns, int flags, int sum_plane, int first,
+                                           int last)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_decompose_pass_sum"));
+    WtGuard guard_(b->ctx);
+    if (!(flags & 1)) WT_FAIL("wt_batch_decompose_pass_sum: a batch runs the fused passes (flags bit0)");
+    return batch_pass(b, nf, cur, nxt, s0, ns, last ? 2 : 1, sum_plane, first != 0);
+}
+
+extern "C" int wt_batch_abs_median(wt_batch *b, int nf, int plane, float *medians)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_abs_median"));
+    if (!medians) WT_FAIL("wt_batch_abs_median: null pointer");
+    WtGuard guard_(b->ctx);
+    wt_ctx *c = b->ctx;
+    float *q = nullptr;
+    WT_TRY(bplane(b, plane, &q));
+    const Geo &g = b->geo.g;
+    const int64_t N = (int64_t)g.H * g.W;
+    const unsigned long long klo = (unsigned long long)((N - 1) / 2);
+    for (int f = 0; f < nf; ++f)
+        for (int r = 0; r < 2; ++r) b->h_sel[2 * f + r] = WtBatchSel{klo + ((N & 1) == 0 && r == 1 ? 1ull : 0ull), 0u, 0u};
+    WT_HIP(hipMemcpyAsync(b->d_sel, b->h_sel, (size_t)nf * 2 * sizeof(WtBatchSel), hipMemcpyHostToDevice, c->stream));
+    const int64_t items = (int64_t)g.H * ((g.W + 3) / 4);
+    const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((items + 2047) / 2048, std::max(1, 8 * c->num_cus / nf)));
+    const uint32_t masks[3] = {0u, 0x7ff00000u, 0x7ffffc00u};
+    const int shifts[3] = {20, 10, 0};
+    const uint32_t bmasks[3] = {0x7ffu, 0x3ffu, 0x3ffu};
+    for (int lv = 0; lv < 3; ++lv) {
+        {
+            ProfScope ps(c, "wt_batch_hist_kernel");
+            hipLaunchKernelGGL(wt_batch_hist_kernel, dim3(bx, nf), dim3(256), 0, c->stream, (const float *)q, g.H, g.P, g.W, b->fstride, masks[lv],
+                               shifts[lv], bmasks[lv], b->d_sel, b->d_hist);
+        }
+        {
+            ProfScope ps(c, "wt_batch_select_kernel");
+            hipLaunchKernelGGL(wt_batch_select_kernel, dim3(2 * nf), dim3(256), 0, c->stream, b->d_hist, b->d_sel, (int)bmasks[lv] + 1, shifts[lv]);
+        }
+        WT_HIP(hipGetLastError());
+    }
+    WT_HIP(hipMemcpyAsync(b->h_sel, b->d_sel, (size_t)nf * 2 * sizeof(WtBatchSel), hipMemcpyDeviceToHost, c->stream));
+    WT_HIP(hipStreamSynchronize(c->stream));               // the one host round trip for all nf medians
+    for (int f = 0; f < nf; ++f)
+        if (b->h_sel[2 * f].nan) WT_FAIL("wt_batch_abs_median: frame %d holds %u NaN pixels", f, b->h_sel[2 * f].nan);
+    for (int f = 0; f < nf; ++f) {
+        float lo, hi;
+        memcpy(&lo, &b->h_sel[2 * f].prefix, 4);
+        memcpy(&hi, &b->h_sel[2 * f + 1].prefix, 4);
+        // np.median on float32: mean of the two middle values in float32 (as wt_abs_median)
+        medians[f] = (N & 1) ? lo : (lo + hi) / 2.0f;
+    }
+    return 0;
+}
+
+extern "C" int wt_batch_denoise_sum(wt_batch *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
+                                    int write_back)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_denoise_sum"));
+    WtGuard guard_(b->ctx);
+    if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > b->max_level)
+        WT_FAIL("wt_batch_denoise_sum: count %d out of range [1,%d]", count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
+    if (n_den < 0 || n_den > count) WT_FAIL("wt_batch_denoise_sum: n_den %d outside [0,%d]", n_den, count);
+    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("wt_batch_denoise_sum: null tau/wgt");
+    if (dst >= 0 && dst < count) WT_FAIL("wt_batch_denoise_sum: dst plane %d is one of the summed planes", dst);
+    BatchDenoiseArgs a{};
+    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
+    for (int i = 0; i < count; ++i) {
+        WT_TRY(bplane(b, i, &a.p[i]));
+        a.wgt[i] = i < n_den ? (float)wgt[i] : 1.f;
+    }
+    float *o = nullptr;
+    WT_TRY(bplane(b, dst, &o));
+    const int nt = std::max(n_den, 1);
+    // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
+    WT_HIP(hipStreamSynchronize(b->ctx->stream));
+    for (int i = 0; i < nf * nt; ++i) b->h_tau[i] = n_den ? tau[i] : 0.0;
+    WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * nt * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    const int64_t n4 = (int64_t)nf * b->fstride / 4;
+    ProfScope ps(b->ctx, "wt_batch_denoise_sum_kernel");
+    hipLaunchKernelGGL(wt_batch_denoise_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, b->ctx->stream, a, (const double *)b->d_tau,
+                       o, n4, b->fstride / 4);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch_anscombe(wt_batch *b, int nf, int src, int dst, float alpha, float g, float sigma, int inverse)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_anscombe"));
+    WtGuard guard_(b->ctx);
+    if (alpha == 0.f) WT_FAIL("wt_batch_anscombe: alpha must be non-zero");
+    float *s = nullptr, *d = nullptr;
+    WT_TRY(bplane(b, src, &s));
+    WT_TRY(bplane(b, dst, &d));
+    return launch_anscombe(b->ctx, s, d, (int64_t)nf * b->fstride / 4, alpha, g, sigma, inverse);
+}

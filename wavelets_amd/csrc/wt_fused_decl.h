@@ -40,6 +40,9 @@ struct FusedArgsT {
     // clamp((bits >> 10 [float] or 41 [double]) - *hist_base, 0, 2047): 2046 bins of 21- / 22-bit resolution
     // around a predicted median (wt_median_window_kernel), everything below / above in bins 0 / 2047
     const uint32_t *hist_base;
+    // batch of same-shape frames (wt_batch, wt_fused_batch_kernel): every plane of frame f = blockIdx.z starts
+    // f * fstride elements after frame 0's (the image kernel does not read it)
+    int64_t fstride;
 };
 typedef FusedArgsT<float> FusedArgs;
 
@@ -59,6 +62,8 @@ struct FusedRows {
     int lo[2] = {0, 0}, hi[2] = {0, 0};
     int reserve = 0;
     int part = 0;      // profiling label of a split pass (multi-GPU): 1 = "/interior", 2 = "/edge"
+    int frames = 1;    // frames of a batch (wt_batch) in this launch, fstride elements apart (whole passes only)
+    int64_t fstride = 0;
 };
 
 static inline bool wt_fused_has_pass(int s0, int ns, int family = WT_B3SPLINE)
@@ -76,6 +81,12 @@ static inline bool wt_fused_has_pass(int s0, int ns, int family = WT_B3SPLINE)
     int wt_fused_tu_f32_k##K##_acc##ACC(wt_plan *p, const FusedArgs &a, int s0, int ns, const FusedRows &rows);
 WT_FUSED_TU_DECL(5, 0) WT_FUSED_TU_DECL(5, 1) WT_FUSED_TU_DECL(5, 2) WT_FUSED_TU_DECL(5, 3)
 WT_FUSED_TU_DECL(3, 0) WT_FUSED_TU_DECL(3, 1) WT_FUSED_TU_DECL(3, 2) WT_FUSED_TU_DECL(3, 3)
+#undef WT_FUSED_TU_DECL
+// the batched float32 passes (wt_batch: rows.frames > 1), units of their own
+#define WT_FUSED_TU_DECL(K, ACC)                                                                                       \
+    int wt_fused_tu_f32_k##K##_batch_acc##ACC(wt_plan *p, const FusedArgs &a, int s0, int ns, const FusedRows &rows);
+WT_FUSED_TU_DECL(5, 0) WT_FUSED_TU_DECL(5, 1) WT_FUSED_TU_DECL(5, 2)
+WT_FUSED_TU_DECL(3, 0) WT_FUSED_TU_DECL(3, 1) WT_FUSED_TU_DECL(3, 2)
 #undef WT_FUSED_TU_DECL
 #define WT_FUSED_TU_DECL(K, ACC)                                                                                       \
     int wt_fused_tu_f64_k##K##_acc##ACC(wt_plan64 *p, const FusedArgsT<double> &a, int s0, int ns, const FusedRows &rows);
@@ -99,6 +110,12 @@ static int wt_fused_launch(wt_plan *p, const float *in, float *out_c, float **ou
     a.hist = hist;
     a.hist_base = hist_base;
     const bool b3 = p->family == WT_B3SPLINE;
+    if (rows.frames != 1 && (acc == 3 || rows.n)) WT_FAIL("fused pass: a batch of frames takes whole plain / accumulate passes");
+    if (rows.frames != 1) {
+        if (acc == 1) return b3 ? wt_fused_tu_f32_k5_batch_acc1(p, a, s0, ns, rows) : wt_fused_tu_f32_k3_batch_acc1(p, a, s0, ns, rows);
+        if (acc == 2) return b3 ? wt_fused_tu_f32_k5_batch_acc2(p, a, s0, ns, rows) : wt_fused_tu_f32_k3_batch_acc2(p, a, s0, ns, rows);
+        return b3 ? wt_fused_tu_f32_k5_batch_acc0(p, a, s0, ns, rows) : wt_fused_tu_f32_k3_batch_acc0(p, a, s0, ns, rows);
+    }
     if (acc == 3) return b3 ? wt_fused_tu_f32_k5_acc3(p, a, s0, ns, rows) : wt_fused_tu_f32_k3_acc3(p, a, s0, ns, rows);
     if (acc == 1) return b3 ? wt_fused_tu_f32_k5_acc1(p, a, s0, ns, rows) : wt_fused_tu_f32_k3_acc1(p, a, s0, ns, rows);
     if (acc == 2) return b3 ? wt_fused_tu_f32_k5_acc2(p, a, s0, ns, rows) : wt_fused_tu_f32_k3_acc2(p, a, s0, ns, rows);

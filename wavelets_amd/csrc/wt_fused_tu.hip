@@ -1,6 +1,7 @@
 // One instantiation group of the fused passes per translation unit (see wt_fused_decl.h).  Compiled
 // by __graft_entry__.build() once per (WT_TU_F64, WT_TU_K, WT_TU_ACC):
 //     hipcc -c wt_fused_tu.hip -DWT_TU_F64=0 -DWT_TU_K=5 -DWT_TU_ACC=1 -o _build/fused_f32_k5_acc1.o
+// and, for the batched float32 passes (wt_batch), once per (WT_TU_K, WT_TU_ACC < 3) with -DWT_TU_BATCH=1
 #include "wt_fused.h"
 #include "wt_unit_probe.h"
 
@@ -19,7 +20,12 @@ int WT_TU_CAT(wt_fused_tu_f64_k, WT_TU_K, _acc, WT_TU_ACC)(wt_plan64 *p, const F
     return wt_fused64_dispatch_acc<WT_TU_K, WT_TU_ACC>(p, a, s0, ns, rows);
 }
 #else
+#if WT_TU_BATCH
+// the batched passes (wt_batch): -DWT_TU_BATCH=1, float32, acc 0..2
+int WT_TU_CAT(wt_fused_tu_f32_k, WT_TU_K, _batch_acc, WT_TU_ACC)(wt_plan *p, const FusedArgs &a, int s0, int ns, const FusedRows &rows)
+#else
 int WT_TU_CAT(wt_fused_tu_f32_k, WT_TU_K, _acc, WT_TU_ACC)(wt_plan *p, const FusedArgs &a, int s0, int ns, const FusedRows &rows)
+#endif
 {
     return wt_fused_dispatch_acc<WT_TU_K, WT_TU_ACC>(p, a, s0, ns, rows);
 }

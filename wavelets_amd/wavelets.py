@@ -561,6 +561,38 @@ def atrous_convolution(image, kernel, bilateral_variance=None, s=0, mode="symmet
 # ------------------------------------------------------------------------------------------
 # Coefficients (ref:108-149) - device-resident planes with a lazily materialised host mirror
 # ------------------------------------------------------------------------------------------
+def _noise_from_median(median, sigma_e):
+    """MAD noise estimate from the device's np.median(np.abs(w_0)) (ref:126-127; numpy's promotion)"""
+    return median / 0.6745 / sigma_e[0]
+
+
+def _scalar_tau(sigma, noise, sigma_e_scale, soft=True):
+    """Coefficients._tau for a non-zero sigma and a scalar noise level: (tau, PLANE_NONE), or None when
+    the significance is identically one (noise == 0, ref:133-135; a negative hard threshold)"""
+    if noise == 0:
+        return None
+    tau = float(sigma * noise * sigma_e_scale)
+    if tau < 0:
+        # ref:137-141 with a negative threshold: erf(|w / tau|) is erf(|w| / |tau|), and
+        # |w| > tau is always true (significance one)
+        return (-tau, PLANE_NONE) if soft else None
+    return tau, PLANE_NONE
+
+
+def _interleave_split(sched, level, sigma, weights):
+    """(entries, k, covered): the (scale, sigma, weight) entries Coefficients.denoise visits (zip truncation,
+    ref:148), and where the threshold step goes in the fused schedule `sched` - after its first k passes,
+    which produce planes 0 .. covered-1.  k == 0 (no schedule) or k == len(sched): no interleaving, the
+    transform runs whole and the threshold step follows it."""
+    entries = list(zip(range(level + 1), sigma, weights))
+    n_den = max([scl + 1 for scl, sig, wgt in entries if sig != 0 or wgt != 1], default=0)
+    k, covered = 0, 0
+    while k < len(sched) and (covered < n_den or k == 0):
+        covered += sched[k][1]
+        k += 1
+    return entries, k, covered
+
+
 class Coefficients:
     """``level+1`` coefficient planes: 0..level-1 detail, ``level`` the final smooth.
 
@@ -726,7 +758,7 @@ class Coefficients:
         return self._noise_from_device()
 
     def _noise_from_device(self):
-        return self._plan.abs_median(0) / 0.6745 / self.sigma_e[0]
+        return _noise_from_median(self._plan.abs_median(0), self.sigma_e)
 
     def _tau(self, sigma, scale, soft=True):
         """(tau, noise_plane) or None when the significance is identically one
@@ -737,14 +769,7 @@ class Coefficients:
         if self.noise is None:
             self.noise = self._noise_from_device()                        # ref:131-132 (lazy)
         if type(self.noise) is not np.ndarray:
-            if self.noise == 0:
-                return None
-            tau = float(sigma * self.noise * self.sigma_e[scale])
-            if tau < 0:
-                # ref:137-141 with a negative threshold: erf(|w / tau|) is erf(|w| / |tau|), and
-                # |w| > tau is always true (significance one)
-                return (-tau, PLANE_NONE) if soft else None
-            return tau, PLANE_NONE
+            return _scalar_tau(sigma, self.noise, self.sigma_e[scale], soft)
         plan = self._plan
         if self._noise_uploaded is not self.noise:
             plan.upload(_NOISE_PLANE, np.broadcast_to(
@@ -858,16 +883,11 @@ def _decompose_denoise_sum(transform, plan, level, coefficients, sigma, weights=
     thresholded.  Result in PLANE_OUT; ``write_back`` also stores the thresholded planes."""
     if weights is None:
         weights = (1,) * len(sigma)
-    entries = list(zip(range(level + 1), sigma, weights))                 # zip truncation, ref:148
-    n_den = max([scl + 1 for scl, sig, wgt in entries if sig != 0 or wgt != 1], default=0)
     # (float64 plans: the fused passes serve the built-in families' taps, wt64_decompose_pass)
     fam = plan.fused_family if isinstance(plan, Plan64) else (None if plan.custom else plan.family)
-    sched = _lib.schedule(fam, level, True) if fam is not None else []
-    k, covered = 0, 0
-    if transform.bilateral is None and fam is not None and level > 0 and plan.fused_ok(level):
-        while k < len(sched) and (covered < n_den or k == 0):
-            covered += sched[k][1]
-            k += 1
+    fused = transform.bilateral is None and fam is not None and level > 0 and plan.fused_ok(level)
+    sched = _lib.schedule(fam, level, True) if fused else []
+    entries, k, covered = _interleave_split(sched, level, sigma, weights)
     if k == 0 or k == len(sched) or coefficients._lazy_noise_after_rescale(sigma, weights):
         transform._run(plan, level)
         coefficients._denoise_sum(sigma, weights, soft_threshold, write_back)
