@@ -579,10 +579,12 @@ int wt64_anscombe(wt_plan64 *plan, int src, int dst, double alpha, double g, dou
  * A wt_batch holds the planes of N frames of one H x W shape back to back (frame f at f * frame_stride
  * floats, rows of the pitch a wt_plan of that width has): every fused pass of the schedule runs over the
  * active frames in ONE launch (the frame is a grid dimension), pointwise steps run once over the stack.
- * A frame's result is bit-identical to the per-frame call on a wt_plan.  Only schedules whose passes are
- * all fused (wt_plan_fused_ok) run here; built-in families only.  Every operation takes the number of
+ * A frame's result is bit-identical to the per-frame call on a wt_plan.  Passes that carry a sum run only
+ * on all-fused schedules (wt_plan_fused_ok); built-in families only.  Every operation takes the number of
  * ACTIVE frames nf (frames 0 .. nf-1; the last chunk of a stack may be shorter than the batch).
- * Planes: 0..max_level, WT_PLANE_INPUT, WT_PLANE_OUT, WT_PLANE_SCRATCH(0/1) (scratch used internally). */
+ * Planes: 0..max_level, WT_PLANE_INPUT, WT_PLANE_OUT, WT_PLANE_SCRATCH(0/1) (scratch used internally) and the
+ * two planes of wow (WT_PLANE_SCRATCH(3/4), below).  wt_batch_decompose runs a single-scale pass that has no fused
+ * kernel on the batched per-scale stencil (levels >= 9); the other passes are fused. */
 typedef struct wt_batch wt_batch;
 int wt_batch_create(wt_ctx *ctx, int n, int H, int W, int family, int max_level, wt_batch **batch);
 int wt_batch_destroy(wt_batch *batch);
@@ -613,6 +615,29 @@ int wt_batch_denoise_sum(wt_batch *batch, int nf, int count, int dst, int n_den,
 /* generalized_anscombe over the active frames (watroo/utils.py:93-94, 99-100; as wt_anscombe) */
 int wt_batch_anscombe(wt_batch *batch, int nf, int src, int dst, float alpha, float g, float sigma,
                       int inverse);
+/* ---- wow over a batch (watroo/utils.py:105-219, utils.wow per frame).  Extra planes: WT_PLANE_SCRATCH(3), the
+ * output plane of wt_batch_wow_scale, and WT_PLANE_SCRATCH(4), wow's gamma accumulator.  Per-frame parameters are
+ * arrays of nf entries; every frame gets the bits of the per-frame call on a wt_plan. */
+/* plane <- value over the active frames (gamma_scaled = zeros, watroo/utils.py:157-158; as wt_fill_plane) */
+int wt_batch_fill(wt_batch *batch, int nf, int plane, float value);
+/* wt_wow_update per frame without a power plane or noise map (watroo/utils.py:185-191 with local_power = 1, 199-203):
+ * wow's last plane, whitening=False and h >= 1; tau[f] <= 0: significance one; gamma_plane may be WT_PLANE_NONE */
+int wt_batch_wow_update(wt_batch *batch, int nf, int plane, const double *tau, int soft, const float *factor,
+                        int gamma_plane);
+/* wt_wow_scale per frame, scalar noise (watroo/utils.py:192-203): local power conv_s(c^2), significance, gamma sum
+ * and whitening of plane `plane` at scale s in one batched stencil launch; the result goes to WT_PLANE_SCRATCH(3)
+ * and the two planes' buffers are swapped */
+int wt_batch_wow_scale(wt_batch *batch, int nf, int plane, int s, const double *tau, int soft, const float *factor,
+                       int gamma_plane);
+/* wt_reduce per frame ({sum, sumsq, min, max}, fp64, the per-frame call's doubles; np.std / np.mean(c**2) of
+ * watroo/utils.py:178-189, gamma_scaled.min / max of utils.py:208-211): out[4 * nf], one host round trip */
+int wt_batch_reduce(wt_batch *batch, int nf, int plane, double *out);
+/* wt_gamma_blend per frame (watroo/utils.py:212-217) with the frame's gmin[f] / gmax[f] */
+int wt_batch_gamma_blend(wt_batch *batch, int nf, int recon, int gamma_plane, const float *gmin, const float *gmax,
+                         float inv_gamma, float h);
+/* wt_plane_sum per frame: dst = planes [first, first + count) summed in plane order (np.sum(coefficients, axis=0),
+ * watroo/utils.py:205) */
+int wt_batch_plane_sum(wt_batch *batch, int nf, int first, int count, int dst);
 
 #ifdef __cplusplus
 }

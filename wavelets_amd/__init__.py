@@ -11,6 +11,6 @@ from .wavelets import atrous_convolution, sdev_loc, AbstractScalingFunction  # n
 from .utils import *  # noqa: F401,F403
 from .sequence import map_frames, denoise_many, wow_many, transform_many  # noqa: F401  (sequences of frames: double-buffered over PCIe)
 
-from .batch import transform_stack, denoise_stack  # noqa: F401  (stacks of same-shape frames: one launch per pass)
+from .batch import transform_stack, denoise_stack, wow_stack  # noqa: F401  (stacks of same-shape frames: one launch per pass)
 
 __version__ = '0.1.0'

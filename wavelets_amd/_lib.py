@@ -212,6 +212,13 @@ SIGNATURES = {
                                         _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
     "wt_batch_anscombe": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float,
                                      _c.c_int]),
+    "wt_batch_fill": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_float]),
+    "wt_batch_wow_update": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _fp, _c.c_int]),
+    "wt_batch_wow_scale": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _fp,
+                                      _c.c_int]),
+    "wt_batch_reduce": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double)]),
+    "wt_batch_gamma_blend": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _fp, _fp, _c.c_float, _c.c_float]),
+    "wt_batch_plane_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
 }
 
 _lib = None
@@ -897,13 +904,17 @@ def batch_frame_bytes(H, W, level):
     return (level + 5) * H * ((W + 3) // 4 * 4) * 4
 
 
-def batch_chunks(n, H, W, level, budget=None, max_frames=BATCH_MAX_FRAMES):
+def batch_chunks(n, H, W, level, budget=None, max_frames=BATCH_MAX_FRAMES, extra_planes=0):
     """[(first frame, frames)] of a stack of `n` frames: as many frames per chunk as `budget` bytes of planes
-    (default BATCH_BYTES; at least one frame) and the grid allow, the last chunk the remainder."""
+    (default BATCH_BYTES; at least one frame) and the grid allow, the last chunk the remainder.  `extra_planes`:
+    planes per frame beyond batch_frame_bytes' (wow's spare and gamma planes)."""
     if n < 0:
         raise ValueError("negative frame count")
+    if extra_planes < 0:
+        raise ValueError("negative extra plane count")
     budget = BATCH_BYTES if budget is None else budget
-    per = max(1, min(int(budget // batch_frame_bytes(H, W, level)), int(max_frames)))
+    frame = batch_frame_bytes(H, W, level) + int(extra_planes) * H * ((W + 3) // 4 * 4) * 4
+    per = max(1, min(int(budget // frame), int(max_frames)))
     return [(f0, min(per, n - f0)) for f0 in range(0, n, per)]
 
 
@@ -982,6 +993,42 @@ class BatchPlan:
 
     def anscombe(self, nf, src, dst, alpha=1.0, g=0.0, sigma=0.0, inverse=False):
         check(load().wt_batch_anscombe(self._h, nf, src, dst, alpha, g, sigma, int(inverse)))
+
+    # -- wow (wt_batch_wow_*): per-frame parameters are sequences of nf values
+    @staticmethod
+    def _per_frame(values, nf, ctype, what):
+        if len(values) != nf:
+            raise ValueError(f"{what}: one value per active frame ({nf} frames, {len(values)} values)")
+        return (ctype * nf)(*[float(v) for v in values])
+
+    def fill(self, nf, plane, value):
+        check(load().wt_batch_fill(self._h, nf, plane, value))
+
+    def wow_update(self, nf, plane, taus, soft, factors, gamma_plane=PLANE_NONE):
+        """Plan.wow_update per frame without power plane or noise map: taus[f] (0.0: significance one), factors[f]"""
+        t = self._per_frame(taus, nf, _c.c_double, "wow_update taus")
+        f = self._per_frame(factors, nf, _c.c_float, "wow_update factors")
+        check(load().wt_batch_wow_update(self._h, nf, plane, t, int(soft), f, gamma_plane))
+
+    def wow_scale(self, nf, plane, s, taus, soft, factors, gamma_plane=PLANE_NONE):
+        """Plan.wow_scale per frame (scalar noise): local power, significance, gamma sum and whitening, in place"""
+        t = self._per_frame(taus, nf, _c.c_double, "wow_scale taus")
+        f = self._per_frame(factors, nf, _c.c_float, "wow_scale factors")
+        check(load().wt_batch_wow_scale(self._h, nf, plane, s, t, int(soft), f, gamma_plane))
+
+    def reduce(self, nf, plane):
+        """[(sum, sumsq, min, max)] of every active frame, fp64 (Plan.reduce's doubles)"""
+        out = (_c.c_double * (4 * nf))()
+        check(load().wt_batch_reduce(self._h, nf, plane, out))
+        return [tuple(out[4 * f:4 * f + 4]) for f in range(nf)]
+
+    def gamma_blend(self, nf, recon, gamma_plane, gmins, gmaxs, inv_gamma, h):
+        lo = self._per_frame(gmins, nf, _c.c_float, "gamma_blend gmins")
+        hi = self._per_frame(gmaxs, nf, _c.c_float, "gamma_blend gmaxs")
+        check(load().wt_batch_gamma_blend(self._h, nf, recon, gamma_plane, lo, hi, inv_gamma, h))
+
+    def plane_sum(self, nf, first, count, dst=PLANE_OUT):
+        check(load().wt_batch_plane_sum(self._h, nf, first, count, dst))
 
 
 _batch_cache = {}        # id(ctx) -> [BatchPlan], most recently used last (its own small cache: not the plan pool)

@@ -4,19 +4,21 @@ back in one host round trip, and the pointwise steps run once over the stack.
 
     transform_stack(frames, level)      == np.stack([AtrousTransform(sf)(f, level).data for f in frames])
     denoise_stack(frames, weights)      == np.stack([denoise(f, weights, sf, noise_i, ...) for f in frames])
+    wow_stack(frames, ...)              == np.stack([wow(f, ..., noise=noise_i, ...)[0] for f in frames])
 
 bit for bit.  The sequence of operations per frame is the per-frame path's own (wavelets._interleave_split,
-_scalar_tau, _noise_from_median).  Inputs the batched engine does not cover run the per-frame loop
-(batch_eligible says which)."""
+_scalar_tau, _noise_from_median; utils._wow_lists, _wow_factor, _gamma_range).  Inputs the batched engine does
+not cover run the per-frame loop (batch_eligible / wow_eligible say which)."""
 import numpy as np
 
 from . import _lib
-from ._lib import PLANE_INPUT, PLANE_OUT, PLANE_SCRATCH, FLAG_FUSED
+from ._lib import PLANE_INPUT, PLANE_OUT, PLANE_NONE, PLANE_SCRATCH, FLAG_FUSED
 from .wavelets import (AtrousTransform, B3spline, _family_of, _needs_generic, _interleave_split, _scalar_tau,
                        _noise_from_median)
-from .utils import denoise
+from .utils import (denoise, wow, _GAMMA_PLANE, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments,
+                    _wow_factor, _gamma_range)
 
-__all__ = ['transform_stack', 'denoise_stack', 'batch_eligible']
+__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'batch_eligible', 'wow_eligible']
 
 # levels whose fused schedule has a kernel for every pass (wt_plan_fused_ok), both built-in families: L = 1 is
 # a single-scale pass, and from 9 scales on the schedules hold single-scale passes at D >= 256 (wt_fused_has_pass)
@@ -58,10 +60,34 @@ def batch_eligible(frames, level, scaling_function=B3spline, bilateral=None, noi
     """True when the batched engine computes this stack (host logic): native float32 frames of one shape in an
     (N, H, W) array, no bilateral filtering, a built-in scaling function with its own taps, a level with an
     all-fused schedule (2..8) and scalar noise levels.  Everything else runs the per-frame loop."""
+    if level not in BATCH_LEVELS:
+        return False
+    return _engine_eligible(frames, scaling_function, bilateral, noise_per_frame)
+
+
+# scales of wow_stack's transform: from 9 scales on, the schedules hold single-scale passes without a fused kernel,
+# which the batch runs on the batched per-scale stencil (wt_batch_decompose); up to the per-scale kernels' limit
+WOW_LEVELS = range(1, 25)
+
+
+def wow_eligible(frames, n_scales, scaling_function=B3spline, bilateral=None, noise_per_frame=()):
+    """True when the batched engine computes wow over this stack (host logic): batch_eligible's conditions for
+    the frames, the scaling function, bilateral filtering and the noise levels - which must also be scalars that
+    are not arrays (utils.wow takes a 0-d array as a noise map) - with n_scales (already resolved) in 1..24.
+    Everything else runs the per-frame loop."""
+    if n_scales not in WOW_LEVELS:
+        return False
+    if noise_per_frame is not None and any(type(n) is np.ndarray for n in noise_per_frame):
+        return False
+    return _engine_eligible(frames, scaling_function, bilateral, noise_per_frame)
+
+
+def _engine_eligible(frames, scaling_function, bilateral, noise_per_frame):
+    """the conditions of batch_eligible / wow_eligible other than the level"""
     if not isinstance(frames, np.ndarray) or frames.ndim != 3 or frames.dtype != np.dtype(np.float32) \
             or not frames.dtype.isnative:
         return False
-    if bilateral is not None or level not in BATCH_LEVELS:
+    if bilateral is not None:
         return False
     if _needs_generic(scaling_function):
         return False
@@ -190,3 +216,97 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
     finally:
         _lib.release_batch(bp)
     return out
+
+
+def _wow_taus(bp, nf, sigma, scale, noises, sigma_e, soft):
+    """(one threshold per frame, the noise levels) of wow's scale `scale` (Coefficients._tau, scalar noise): the
+    frames whose noise is None get their MAD estimate here, where the per-frame call's lazy _tau takes it"""
+    if sigma != 0 and any(n is None for n in noises):
+        med = bp.abs_median(nf, 0)                                               # ref:131-132 (lazy)
+        noises = [_noise_from_median(m, sigma_e) if n is None else n for n, m in zip(noises, med)]
+    return [_taus_of([(scale, sigma, None)], n, sigma_e, soft)[0] for n in noises], noises
+
+
+def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whitening=True, denoise_coefficients=[],
+              noise=None, bilateral=None, bilateral_scaling=False, soft_threshold=True, preserve_variance=False,
+              gamma=3.2, gamma_min=None, gamma_max=None, h=0, out=None, return_coefficients=False):
+    """(N, H, W): the wow image of every frame (utils.wow, ref utils.py:105-219), batched - float32 for the stacks
+    the batch computes, the per-frame dtype otherwise.  `noise`: None (each frame's own MAD estimate), a scalar,
+    or one entry per frame.  return_coefficients: (images, planes), planes (N, n_scales + 1, H, W) = the whitened
+    coefficients of every frame (wow(...)[1].data)."""
+    fr = _as_frames(frames)
+    N = len(fr)
+    nl = _noise_list(noise, N)
+    shape = fr[0].shape
+    kw = dict(weights=weights, whitening=whitening, denoise_coefficients=denoise_coefficients, bilateral=bilateral,
+              bilateral_scaling=bilateral_scaling, soft_threshold=soft_threshold, preserve_variance=preserve_variance,
+              gamma=gamma, gamma_min=gamma_min, gamma_max=gamma_max, h=h)
+    # n_scales once for the shared shape, as wow() resolves it for one frame (ref:121-138)
+    L = _wow_n_scales(shape, scaling_function, n_scales, h, denoise_coefficients)
+    L = _wow_scale_limit(L, scaling_function, 2, bilateral, denoise_coefficients)
+    if not wow_eligible(fr, L, scaling_function, bilateral, nl):
+        per = nl if nl is not None else [noise] * N
+        res = [wow(f, scaling_function, n_scales, noise=n_i, **kw) for f, n_i in zip(fr, per)]
+        images = np.stack([r[0] for r in res])
+        if out is not None:
+            out[...] = images
+            images = out
+        return (images, np.stack([r[1].data for r in res])) if return_coefficients else images
+    _, H, W = fr.shape
+    nplanes = L + 1
+    if out is None:
+        out = _lib.host_empty((N, H, W))                     # page-locked (as wow(): plan.download)
+    elif out.shape != (N, H, W) or out.dtype != np.float32 or not out.flags.c_contiguous:
+        raise ValueError(f"out: float32 array of shape {(N, H, W)} expected")
+    planes = _lib.host_empty((N, nplanes, H, W)) if return_coefficients else None
+    ctx = _lib.default_context()
+    fam = _family_of(scaling_function(2))
+    extra = int(whitening and h < 1) + int(h > 0)            # (the spare plane of the fused update, the gamma plane)
+    chunks = _lib.batch_chunks(N, H, W, L, extra_planes=extra)
+    bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, fam, L)
+    try:
+        for f0, nf in chunks:
+            bp.upload(PLANE_INPUT, fr[f0:f0 + nf])
+            bp.decompose(nf, PLANE_INPUT, L, FLAG_FUSED)                            # ref:148-151
+            _wow_batch_device(bp, nf, nl[f0:f0 + nf], scaling_function, L, weights, whitening, denoise_coefficients,
+                              soft_threshold, preserve_variance, gamma, gamma_min, gamma_max, h)
+            bp.download(PLANE_OUT, nf, out=out[f0:f0 + nf])
+            if return_coefficients:
+                for s in range(nplanes):
+                    bp.download(s, nf, out=planes[f0:f0 + nf, s])
+    finally:
+        _lib.release_batch(bp)
+    return (out, planes) if return_coefficients else out
+
+
+def _wow_batch_device(bp, nf, noises, scaling_function, n_scales, weights, whitening, denoise_coefficients,
+                      soft_threshold, preserve_variance, gamma, gamma_min, gamma_max, h):
+    """The device-resident part of wow (ref:157-217, utils._wow_device / _wow_scales) for frames 0 .. nf-1 of a
+    batch whose planes 0 .. n_scales hold the transform: whitened planes in place, the images in PLANE_OUT.
+    `noises`: one entry per frame (None: its MAD estimate, taken where the per-frame call's lazy _tau takes it)."""
+    sigma_e = scaling_function(2).sigma_e()
+    nplanes = n_scales + 1
+    recomposition_weights, sdc = _wow_lists(weights, denoise_coefficients, n_scales)       # ref:160-170
+    use_gamma = h > 0
+    gplane = _GAMMA_PLANE if use_gamma else PLANE_NONE
+    npix = float(bp.H) * float(bp.W)
+    noises = list(noises)
+    if use_gamma:
+        bp.fill(nf, _GAMMA_PLANE, 0.0)                                              # ref:157-158
+    for s, (_, w, d) in enumerate(zip(range(nplanes), recomposition_weights, sdc)):   # ref:174
+        need = _wow_needs_moments(s, n_scales, preserve_variance, whitening, h)
+        moments = bp.reduce(nf, s) if need else [None] * nf
+        factors = [_wow_factor(s, n_scales, w, m, npix, preserve_variance, whitening, h, np.float32) for m in moments]
+        if s == n_scales:                                                           # ref:185-191, 203
+            bp.wow_update(nf, s, [0.0] * nf, soft_threshold, factors, gplane)
+            continue
+        taus, noises = _wow_taus(bp, nf, d, s, noises, sigma_e, soft_threshold)    # ref:199
+        if whitening and h < 1:                                                     # ref:193-196 + 199-203
+            bp.wow_scale(nf, s, s, taus, soft_threshold, factors, gplane)
+        else:
+            bp.wow_update(nf, s, taus, soft_threshold, factors, gplane)
+    bp.plane_sum(nf, 0, nplanes, PLANE_OUT)                                         # ref:205
+    if use_gamma:                                                                   # ref:207-217
+        need = gamma_min is None or gamma_max is None
+        bounds = [_gamma_range(gamma_min, gamma_max, m) for m in (bp.reduce(nf, _GAMMA_PLANE) if need else [None] * nf)]
+        bp.gamma_blend(nf, PLANE_OUT, _GAMMA_PLANE, [b[0] for b in bounds], [b[1] for b in bounds], 1 / gamma, h)

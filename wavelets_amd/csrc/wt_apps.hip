@@ -23,20 +23,27 @@ extern "C" int wt_plane_sum(wt_plan *p, int first, int count, int dst)
     if (!p) WT_FAIL("wt_plane_sum: null plan");
     if (count < 1 || count > WT_MAX_SUM_PLANES) WT_FAIL("wt_plane_sum: count %d out of range [1,%d]", count, WT_MAX_SUM_PLANES);
     if (first < 0 || first + count - 1 > p->max_level) WT_FAIL("wt_plane_sum: planes [%d,%d) outside [0,%d]", first, first + count, p->max_level);
-    SumArgs a{};
-    a.n = count;
+    const float *planes[WT_MAX_SUM_PLANES];
     for (int i = 0; i < count; ++i) {
         float *b = nullptr;
         WT_TRY(plane_base(p, first + i, &b));
-        a.p[i] = b;
+        planes[i] = b;
     }
     float *o = nullptr;
     WT_TRY(plane_base(p, dst, &o));
-    const int64_t n4 = plan_n4(p);
-    ProfScope ps(p->ctx, "wt_plane_sum_kernel");
+    return launch_plane_sum(p->ctx, planes, count, o, plan_n4(p));
+}
+
+// (wt_plane_sum and wt_batch_plane_sum: n4 float4 groups of contiguous planes, summed in plane order)
+int launch_plane_sum(wt_ctx *c, const float *const *planes, int count, float *out, int64_t n4)
+{
+    SumArgs a{};
+    a.n = count;
+    for (int i = 0; i < count; ++i) a.p[i] = planes[i];
+    ProfScope ps(c, "wt_plane_sum_kernel");
     static const int64_t sum_grid = getenv("WT_SUM_GRID") ? atoll(getenv("WT_SUM_GRID")) : ((int64_t)1 << 30);
     const int grid = (int)std::min<int64_t>((n4 + 255) / 256, sum_grid);
-    hipLaunchKernelGGL(wt_plane_sum_kernel, dim3(grid), dim3(256), 0, p->ctx->stream, a, o, n4);
+    hipLaunchKernelGGL(wt_plane_sum_kernel, dim3(grid), dim3(256), 0, c->stream, a, out, n4);
     WT_HIP(hipGetLastError());
     return 0;
 }

@@ -9,12 +9,18 @@
 // The MAD median is a per-frame radix select (three histogram levels, 11 + 10 + 10 bits of |x|, the
 // levels of wt_abs_median) over all frames at once, two ranks per frame for the upper median of an
 // even pixel count: N medians for one host round trip.
+// wow (watroo/utils.py:105-219) runs on a batch too: its per-scale update is the batched stencil of
+// wt_stencil32_batch.hip (the frame's tau and factor from a small device table), the pointwise update, the
+// {sum, sumsq, min, max} moments (one host round trip for all frames), the gamma blend, the fill and the plane
+// sum run once over the stack, each frame with its own parameters and the bits of the per-frame call.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 #include "wt_host.h"
 #include "wt_fused_decl.h"
+#include "wt_reduce.h"
+#include "wt_stencil_launch.h"
 #include "wt_unit_probe.h"
 
 WT_UNIT_PROBE_DEFINE
@@ -37,6 +43,18 @@ struct wt_batch {
     WtBatchSel *h_sel = nullptr;    // pinned copy
     double *d_tau = nullptr;        // [n][WT_MAX_SUM_PLANES] thresholds of wt_batch_denoise_sum
     double *h_tau = nullptr;        // pinned staging of the table
+    // wow: WT_PLANE_SCRATCH(3) = the output plane of wt_batch_wow_scale (swapped with the coefficient plane, as
+    // wt_wow_scale does), WT_PLANE_SCRATCH(4) = the gamma accumulator (utils.wow's plane ids)
+    float *spare = nullptr, *gamma = nullptr;
+    // per-frame parameter pairs of one launch ({tau, factor}, {gmin, gmax}): a ring of table slots [n][2], pinned
+    // staging + device copy; a slot is refilled only after the copy that last read it has completed (its event)
+    static constexpr int kTabSlots = 16;
+    double *d_ptab = nullptr, *h_ptab = nullptr;
+    hipEvent_t ptab_ev[kTabSlots] = {};
+    int ptab_next = 0;
+    // wt_batch_reduce: [n][red_blocks][4] partials + [n][4] results on the device, [n][4] pinned
+    double *d_red = nullptr, *h_red = nullptr;
+    int red_blocks = 0;
 };
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -152,6 +170,76 @@ __global__ __launch_bounds__(256) void wt_batch_denoise_sum_kernel(BatchDenoiseA
     }
 }
 
+// wt_wow_kernel (wt_kernels_apps.h) with the frame as grid y: no power plane, no noise map, the frame's {tau, factor}
+// (wow's last plane, whitening=False, h >= 1 - watroo/utils.py:185-203).  Same wt_wow_point: the bits of the per-frame call.
+__global__ __launch_bounds__(256) void wt_batch_wow_kernel(float *c, float *gamma, int64_t f4, const double *ptab, int soft)
+{
+    const int f = blockIdx.y;
+    const double tau = ptab[2 * f];
+    const float tauf = (float)tau, factor = (float)ptab[2 * f + 1];
+    float4 *cf = reinterpret_cast<float4 *>(c) + (int64_t)f * f4;
+    float4 *gf = gamma ? reinterpret_cast<float4 *>(gamma) + (int64_t)f * f4 : nullptr;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < f4; i += (int64_t)gridDim.x * blockDim.x) {
+        const float4 v = cf[i];
+        float4 gm = make_float4(0, 0, 0, 0);
+        if (gf) gm = gf[i];
+        float in[4] = {v.x, v.y, v.z, v.w};
+        float gg[4] = {gm.x, gm.y, gm.z, gm.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) in[k] = wt_wow_point(in[k], 1.f, false, 1.f, tau, tauf, soft, factor, gg[k]);
+        cf[i] = make_float4(in[0], in[1], in[2], in[3]);
+        if (gf) gf[i] = make_float4(gg[0], gg[1], gg[2], gg[3]);
+    }
+}
+
+// wt_gamma_kernel (wt_kernels_apps.h, watroo/utils.py:212-217) with the frame as grid y and its own {gmin, gmax}
+__global__ __launch_bounds__(256) void wt_batch_gamma_kernel(float *recon, float *gamma, int64_t f4, const double *ptab, float inv_gamma, float h)
+{
+#pragma clang fp contract(off)
+    const int f = blockIdx.y;
+    const float gmin = (float)ptab[2 * f], gmax = (float)ptab[2 * f + 1];
+    const float range = gmax - gmin;            // (wt_gamma_blend: the same float subtraction on the host)
+    const float omh = 1.f - h;
+    float4 *rf = reinterpret_cast<float4 *>(recon) + (int64_t)f * f4;
+    float4 *gf = reinterpret_cast<float4 *>(gamma) + (int64_t)f * f4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < f4; i += (int64_t)gridDim.x * blockDim.x) {
+        const float4 r = rf[i];
+        const float4 gq = gf[i];
+        const float rr[4] = {r.x, r.y, r.z, r.w};
+        float gg[4] = {gq.x, gq.y, gq.z, gq.w};
+        float o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float t = (gg[k] - gmin) / range;
+            t = t < 0.f ? 0.f : t;
+            t = t > 1.f ? 1.f : t;
+            t = powf(t, inv_gamma);
+            gg[k] = t;
+            o[k] = omh * rr[k] + h * t;
+        }
+        rf[i] = make_float4(o[0], o[1], o[2], o[3]);
+        gf[i] = make_float4(gg[0], gg[1], gg[2], gg[3]);
+    }
+}
+
+__global__ __launch_bounds__(256) void wt_batch_fill_kernel(float *d, int64_t n4, float value)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+        reinterpret_cast<float4 *>(d)[i] = make_float4(value, value, value, value);
+}
+
+// wt_reduce_kernel + wt_reduce_final_kernel per frame (grid y / the final block = the frame): the per-frame
+// work split (gridDim.x blocks) and fold order of wt_reduce.h, i.e. the doubles of the per-frame call
+#define WT_REDUCE_KERNEL_NAME wt_batch_reduce_kernel
+#define WT_REDUCE_KERNEL_BATCH 1
+#include "wt_reduce_rows.h"
+#undef WT_REDUCE_KERNEL_NAME
+#undef WT_REDUCE_KERNEL_BATCH
+__global__ __launch_bounds__(256) void wt_batch_reduce_final_kernel(const double *partials, int nblocks, double *out)
+{
+    wt_reduce_final_block(partials + (int64_t)blockIdx.x * nblocks * 4, nblocks, out + (int64_t)blockIdx.x * 4);
+}
+
 // ------------------------------------------------------------------------------------------------ host
 static int bplane(wt_batch *b, int id, float **out)
 {
@@ -161,7 +249,9 @@ static int bplane(wt_batch *b, int id, float **out)
     else if (id == WT_PLANE_OUT) slot = &b->out;
     else if (id == WT_PLANE_SCRATCH(0)) slot = &b->scr[0];
     else if (id == WT_PLANE_SCRATCH(1)) slot = &b->scr[1];
-    if (!slot) WT_FAIL("wt_batch: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1)", id, b->max_level);
+    else if (id == WT_PLANE_SCRATCH(3)) slot = &b->spare;
+    else if (id == WT_PLANE_SCRATCH(4)) slot = &b->gamma;
+    if (!slot) WT_FAIL("wt_batch: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1/3/4)", id, b->max_level);
     if (!*slot) WT_HIP(hipMalloc((void **)slot, (size_t)b->n * (size_t)b->fstride * sizeof(float)));
     *out = *slot;
     return 0;
@@ -174,15 +264,67 @@ static int check_frames(const wt_batch *b, int nf, const char *who)
     return 0;
 }
 
-// the fused schedule of `level` scales, or an error: a batch runs fused passes only
-static int batch_schedule(wt_batch *b, int level, int32_t *tr, int *np, const char *who)
+// the fused schedule of `level` scales, or an error: the passes with a sum run fused kernels only; `single`: a
+// single-scale pass without a fused kernel runs the batched MODE_DECOMP stencil (as wt_decompose_pass on a plan)
+static int batch_schedule(wt_batch *b, int level, int32_t *tr, int *np, const char *who, bool single = false)
 {
     if (level < 1 || level > b->max_level) WT_FAIL("%s: level %d outside [1, %d]", who, level, b->max_level);
     WT_TRY(wt_schedule(b->geo.family, level, 1, tr, 32, np));
     for (int i = 0; i < *np; ++i)
-        if (!wt_fused_has_pass(tr[3 * i], tr[3 * i + 1], b->geo.family))
+        if (!wt_fused_has_pass(tr[3 * i], tr[3 * i + 1], b->geo.family) && !(single && tr[3 * i + 1] == 1))
             WT_FAIL("%s: %d scales have no all-fused schedule (wt_plan_fused_ok): not a batch case", who, level);
     return 0;
+}
+
+// the frames of a batched stencil launch on the batch's stream
+static StencilCtx batch_stencil_ctx(const wt_batch *b)
+{
+    return StencilCtx{b->ctx, b->ctx->stream, b->geo.g, b->geo.family};
+}
+
+// one single-scale pass of the transform on the batched MODE_DECOMP stencil (decompose_pass_impl's per-scale branch)
+static int batch_stencil_pass(wt_batch *b, int nf, int cur, int nxt, int s0)
+{
+    if (s0 < 0 || s0 > 24 || s0 > b->max_level) WT_FAIL("wt_batch_decompose: scale %d outside the batch (max_level %d)", s0, b->max_level);
+    if (cur == nxt || cur == s0 || nxt == s0) WT_FAIL("wt_batch_decompose: input/output planes alias the detail plane of the pass");
+    float *in = nullptr, *oc = nullptr, *ow = nullptr;
+    WT_TRY(bplane(b, cur, &in));
+    WT_TRY(bplane(b, nxt, &oc));
+    WT_TRY(bplane(b, s0, &ow));
+    ChainArgs a{};
+    a.in = in; a.out_c = oc; a.out_w = ow; a.aux = nullptr;
+    a.f1 = 1.f; a.f2 = 1.f; a.take_sqrt = 0;
+    WtFrames fr;
+    fr.n = nf;
+    fr.fstride = b->fstride;
+    return wt32_stencil_batch_launch(batch_stencil_ctx(b), MODE_DECOMP, a, s0, "wt_chain_batch_kernel<decomp>", fr);
+}
+
+// per-frame parameter pairs (pairs[2 * f], pairs[2 * f + 1]) -> a device table slot, stream-ordered (*dev)
+static int batch_table(wt_batch *b, int nf, const double *pairs, const double **dev)
+{
+    wt_ctx *c = b->ctx;
+    if (!b->d_ptab) {
+        WT_HIP(hipMalloc((void **)&b->d_ptab, (size_t)wt_batch::kTabSlots * b->n * 2 * sizeof(double)));
+        WT_HIP(hipHostMalloc((void **)&b->h_ptab, (size_t)wt_batch::kTabSlots * b->n * 2 * sizeof(double), 0));
+    }
+    const int slot = b->ptab_next;
+    b->ptab_next = (slot + 1) % wt_batch::kTabSlots;
+    if (b->ptab_ev[slot]) WT_HIP(hipEventSynchronize(b->ptab_ev[slot]));    // (the copy of kTabSlots calls ago)
+    else WT_HIP(hipEventCreateWithFlags(&b->ptab_ev[slot], hipEventDisableTiming));
+    double *h = b->h_ptab + (size_t)slot * b->n * 2, *d = b->d_ptab + (size_t)slot * b->n * 2;
+    memcpy(h, pairs, (size_t)nf * 2 * sizeof(double));
+    WT_HIP(hipMemcpyAsync(d, h, (size_t)nf * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    WT_HIP(hipEventRecord(b->ptab_ev[slot], c->stream));
+    *dev = d;
+    return 0;
+}
+
+// x blocks per frame of the batched pointwise kernels (grid y = the frame): about flat_grid's 2048 in all
+static unsigned batch_flat_blocks(const wt_batch *b, int nf)
+{
+    const int64_t f4 = b->fstride / 4;
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((f4 + 255) / 256, (2048 + nf - 1) / nf));
 }
 
 static int batch_pass(wt_batch *b, int nf, int cur, int nxt, int s0, int ns, int acc, int sum_plane, bool first)
@@ -218,13 +360,14 @@ static int batch_schedule_run(wt_batch *b, int nf, int src, int level, bool with
         WT_FAIL("%s: dst plane %d is an input / output / internal plane of the transform", who, dst);
     int32_t tr[3 * 32];
     int np = 0;
-    WT_TRY(batch_schedule(b, level, tr, &np, who));
+    WT_TRY(batch_schedule(b, level, tr, &np, who, !with_sum));
     int cur = src;
     for (int i = 0; i < np; ++i) {
         const int s0 = tr[3 * i], ns = tr[3 * i + 1];
         const bool last = s0 + ns == level;
         const int nxt = last ? level : WT_PLANE_SCRATCH(i & 1);
-        WT_TRY(batch_pass(b, nf, cur, nxt, s0, ns, with_sum ? (last ? 2 : 1) : 0, dst, i == 0));
+        if (!with_sum && ns == 1 && !wt_fused_has_pass(s0, 1, b->geo.family)) WT_TRY(batch_stencil_pass(b, nf, cur, nxt, s0));
+        else WT_TRY(batch_pass(b, nf, cur, nxt, s0, ns, with_sum ? (last ? 2 : 1) : 0, dst, i == 0));
         cur = nxt;
     }
     return 0;
@@ -289,8 +432,16 @@ extern "C" int wt_batch_destroy(wt_batch *b)
     f(b->d_hist);
     f(b->d_sel);
     f(b->d_tau);
+    f(b->spare);
+    f(b->gamma);
+    f(b->d_ptab);
+    f(b->d_red);
     if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) bad = 1;
     if (b->h_tau && hipHostFree(b->h_tau) != hipSuccess) bad = 1;
+    if (b->h_ptab && hipHostFree(b->h_ptab) != hipSuccess) bad = 1;
+    if (b->h_red && hipHostFree(b->h_red) != hipSuccess) bad = 1;
+    for (hipEvent_t e : b->ptab_ev)
+        if (e && hipEventDestroy(e) != hipSuccess) bad = 1;
     delete b;
     if (bad) WT_FAIL("wt_batch_destroy: a device buffer could not be released");
     return 0;
@@ -484,4 +635,146 @@ extern "C" int wt_batch_anscombe(wt_batch *b, int nf, int src, int dst, float al
     WT_TRY(bplane(b, src, &s));
     WT_TRY(bplane(b, dst, &d));
     return launch_anscombe(b->ctx, s, d, (int64_t)nf * b->fstride / 4, alpha, g, sigma, inverse);
+}
+
+// ------------------------------------------------------------------------------------------------ wow
+extern "C" int wt_batch_fill(wt_batch *b, int nf, int plane, float value)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_fill"));
+    WtGuard guard_(b->ctx);
+    float *d = nullptr;
+    WT_TRY(bplane(b, plane, &d));
+    const int64_t n4 = (int64_t)nf * b->fstride / 4;
+    ProfScope ps(b->ctx, "wt_batch_fill_kernel");
+    hipLaunchKernelGGL(wt_batch_fill_kernel, dim3(flat_grid(n4)), dim3(256), 0, b->ctx->stream, d, n4, value);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+static int wow_pairs(wt_batch *b, int nf, const double *tau, const float *factor, const double **dev, const char *who)
+{
+    if (!tau || !factor) WT_FAIL("%s: null tau / factor", who);
+    std::vector<double> pairs((size_t)nf * 2);
+    for (int f = 0; f < nf; ++f) {
+        pairs[2 * f] = tau[f];
+        pairs[2 * f + 1] = (double)factor[f];
+    }
+    return batch_table(b, nf, pairs.data(), dev);
+}
+
+extern "C" int wt_batch_wow_update(wt_batch *b, int nf, int plane, const double *tau, int soft, const float *factor, int gamma_plane)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_wow_update"));
+    WtGuard guard_(b->ctx);
+    if (gamma_plane == plane) WT_FAIL("wt_batch_wow_update: the gamma plane is the updated plane");
+    float *c = nullptr, *gm = nullptr;
+    WT_TRY(bplane(b, plane, &c));
+    if (gamma_plane != WT_PLANE_NONE) WT_TRY(bplane(b, gamma_plane, &gm));
+    const double *dt = nullptr;
+    WT_TRY(wow_pairs(b, nf, tau, factor, &dt, "wt_batch_wow_update"));
+    ProfScope ps(b->ctx, "wt_batch_wow_kernel");
+    hipLaunchKernelGGL(wt_batch_wow_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, c, gm, b->fstride / 4, dt, soft);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch_wow_scale(wt_batch *b, int nf, int plane, int s, const double *tau, int soft, const float *factor, int gamma_plane)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_wow_scale"));
+    WtGuard guard_(b->ctx);
+    if (plane < 0 || plane > b->max_level) WT_FAIL("wt_batch_wow_scale: plane %d is not a coefficient plane", plane);
+    if (s < 0 || s > 24) WT_FAIL("wt_batch_wow_scale: scale %d out of range", s);
+    if (gamma_plane == plane || gamma_plane == WT_PLANE_SCRATCH(3)) WT_FAIL("wt_batch_wow_scale: the gamma plane aliases a plane of the update");
+    float *c = nullptr, *t = nullptr, *gm = nullptr;
+    WT_TRY(bplane(b, plane, &c));
+    WT_TRY(bplane(b, WT_PLANE_SCRATCH(3), &t));
+    if (gamma_plane != WT_PLANE_NONE) WT_TRY(bplane(b, gamma_plane, &gm));
+    const double *dt = nullptr;
+    WT_TRY(wow_pairs(b, nf, tau, factor, &dt, "wt_batch_wow_scale"));
+    // (wt_wow_scale's arguments; tau and factor come from the frame's row of the table)
+    ChainArgs a{};
+    a.in = c; a.out_c = t; a.out_w = nullptr; a.aux = nullptr;
+    a.noise = nullptr; a.gamma = gm; a.soft = soft; a.whiten = 1;
+    WtFrames fr;
+    fr.n = nf;
+    fr.fstride = b->fstride;
+    fr.ftab = dt;
+    WT_TRY(wt32_stencil_batch_launch(batch_stencil_ctx(b), gm ? MODE_WOW_GAMMA : MODE_WOW_PLAIN, a, s, "wt_chain_batch_kernel<wow>", fr));
+    std::swap(b->coef[plane], b->spare);          // (wt_wow_scale: "in place" at pointer level)
+    return 0;
+}
+
+extern "C" int wt_batch_reduce(wt_batch *b, int nf, int plane, double *out)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_reduce"));
+    if (!out) WT_FAIL("wt_batch_reduce: null pointer");
+    WtGuard guard_(b->ctx);
+    wt_ctx *c = b->ctx;
+    float *q = nullptr;
+    WT_TRY(bplane(b, plane, &q));
+    const Geo &g = b->geo.g;
+    // (wt_reduce's work items: (row, chunk of 4096 pixels) pairs over at most partial_blocks blocks, per frame)
+    const int blocks = (int)std::min<int64_t>((int64_t)g.H * ((g.W + 4095) / 4096), c->partial_blocks);
+    if (!b->d_red || b->red_blocks != blocks) {
+        (void)hipFree(b->d_red);
+        (void)hipHostFree(b->h_red);
+        b->d_red = nullptr;
+        b->h_red = nullptr;
+        WT_HIP(hipMalloc((void **)&b->d_red, (size_t)b->n * ((size_t)blocks + 1) * 4 * sizeof(double)));
+        WT_HIP(hipHostMalloc((void **)&b->h_red, (size_t)b->n * 4 * sizeof(double), 0));
+        b->red_blocks = blocks;
+    }
+    double *dout = b->d_red + (size_t)b->n * blocks * 4;
+    {
+        ProfScope ps(c, "wt_batch_reduce_kernel");
+        hipLaunchKernelGGL(wt_batch_reduce_kernel, dim3(blocks, nf), dim3(256), 0, c->stream, (const float *)q, g.H, g.P / 4, g.W, b->fstride, b->d_red);
+        hipLaunchKernelGGL(wt_batch_reduce_final_kernel, dim3(nf), dim3(256), 0, c->stream, (const double *)b->d_red, blocks, dout);
+    }
+    WT_HIP(hipGetLastError());
+    WT_HIP(hipMemcpyAsync(b->h_red, dout, (size_t)nf * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    WT_HIP(hipStreamSynchronize(c->stream));               // the one host round trip for all nf frames
+    memcpy(out, b->h_red, (size_t)nf * 4 * sizeof(double));
+    return 0;
+}
+
+extern "C" int wt_batch_gamma_blend(wt_batch *b, int nf, int recon, int gamma_plane, const float *gmin, const float *gmax, float inv_gamma,
+                                    float h)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_gamma_blend"));
+    if (!gmin || !gmax) WT_FAIL("wt_batch_gamma_blend: null gmin / gmax");
+    WtGuard guard_(b->ctx);
+    if (recon == gamma_plane) WT_FAIL("wt_batch_gamma_blend: recon and gamma planes must differ");
+    float *r = nullptr, *g = nullptr;
+    WT_TRY(bplane(b, recon, &r));
+    WT_TRY(bplane(b, gamma_plane, &g));
+    std::vector<double> pairs((size_t)nf * 2);
+    for (int f = 0; f < nf; ++f) {
+        pairs[2 * f] = gmin[f];
+        pairs[2 * f + 1] = gmax[f];
+    }
+    const double *dt = nullptr;
+    WT_TRY(batch_table(b, nf, pairs.data(), &dt));
+    ProfScope ps(b->ctx, "wt_batch_gamma_kernel");
+    hipLaunchKernelGGL(wt_batch_gamma_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, r, g, b->fstride / 4, dt, inv_gamma, h);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch_plane_sum(wt_batch *b, int nf, int first, int count, int dst)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_plane_sum"));
+    WtGuard guard_(b->ctx);
+    if (count < 1 || count > WT_MAX_SUM_PLANES) WT_FAIL("wt_batch_plane_sum: count %d out of range [1,%d]", count, WT_MAX_SUM_PLANES);
+    if (first < 0 || first + count - 1 > b->max_level) WT_FAIL("wt_batch_plane_sum: planes [%d,%d) outside [0,%d]", first, first + count, b->max_level);
+    if (dst >= first && dst < first + count) WT_FAIL("wt_batch_plane_sum: dst plane %d is one of the summed planes", dst);
+    const float *planes[WT_MAX_SUM_PLANES];
+    for (int i = 0; i < count; ++i) {
+        float *q = nullptr;
+        WT_TRY(bplane(b, first + i, &q));
+        planes[i] = q;
+    }
+    float *o = nullptr;
+    WT_TRY(bplane(b, dst, &o));
+    // the frames back to back are one flat range: wt_plane_sum_kernel over all of them
+    return launch_plane_sum(b->ctx, planes, count, o, (int64_t)nf * b->fstride / 4);
 }

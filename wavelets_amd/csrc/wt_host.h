@@ -118,6 +118,7 @@ static inline uint32_t *hist_base_word(wt_ctx *c) { return c->d_hist + WT_HIST_B
 
 // ------------------------------------------------------------------ applications (wt_apps.hip)
 int launch_anscombe(wt_ctx *c, const float *src, float *dst, int64_t n4, float alpha, float g, float sigma, int inverse);
+int launch_plane_sum(wt_ctx *c, const float *const *planes, int count, float *out, int64_t n4);
 int denoise_sum_rows(wt_plan *p, int count, int dst, int n_den, const double *tau, const double *wgt, int soft, int r0, int r1);
 
 // Tap list of the generic operator on the device: [ntaps x 3 int32 offsets][ntaps x weight]; the

@@ -12,6 +12,7 @@
 #include "wt_internal.h"
 #include "wt_device.h"
 #include "wt_stencil.h"
+#include "wt_reduce.h"
 
 // ---------------------------------------------------------------------------------------------
 // images of another element type, widened (and byte-swapped) on their way into a plane: wt_upload_int /
@@ -371,29 +372,8 @@ static __global__ __launch_bounds__(256) void wt_select_window_step_kernel(uint3
     for (int i = threadIdx.x; i < WT_HIST_BINS; i += 256) hist[i] = 0;
 }
 
-// one 256-thread block: thread t folds partials t, t+256, ... in index order, then a fixed tree
+// one 256-thread block (wt_reduce.h)
 static __global__ __launch_bounds__(256) void wt_reduce_final_kernel(const double *partials, int nblocks, double *out)
 {
-    double s = 0.0, s2 = 0.0, mn = INFINITY, mx = -INFINITY;
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-        s += partials[b * 4 + 0];
-        s2 += partials[b * 4 + 1];
-        mn = fmin(mn, partials[b * 4 + 2]);
-        mx = fmax(mx, partials[b * 4 + 3]);
-    }
-    __shared__ double red[256][4];
-    red[threadIdx.x][0] = s; red[threadIdx.x][1] = s2; red[threadIdx.x][2] = mn; red[threadIdx.x][3] = mx;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            red[threadIdx.x][0] += red[threadIdx.x + off][0];
-            red[threadIdx.x][1] += red[threadIdx.x + off][1];
-            red[threadIdx.x][2] = fmin(red[threadIdx.x][2], red[threadIdx.x + off][2]);
-            red[threadIdx.x][3] = fmax(red[threadIdx.x][3], red[threadIdx.x + off][3]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out[0] = red[0][0]; out[1] = red[0][1]; out[2] = red[0][2]; out[3] = red[0][3];
-    }
+    wt_reduce_final_block(partials, nblocks, out);
 }

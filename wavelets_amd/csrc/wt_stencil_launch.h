@@ -22,6 +22,24 @@ struct StencilCtx {
 
 static inline int wt_family_taps(int family) { return family == WT_B3SPLINE ? 5 : 3; }
 
+// the frames of a batched launch (wt_batch): n frames fstride elements apart, the device table of their
+// {tau, factor} pairs (wow modes).  The launchers below take BATCH = true for them: the same kernel choice and
+// geometry as for one frame, the batched kernel of wt_stencil_march.h, grid z = the frame.
+struct WtFrames {
+    int n = 1;
+    int64_t fstride = 0;
+    const double *ftab = nullptr;
+};
+// hipLaunchKernelGGL of KN##_kernel<targs...>(args), or with BATCH of KN##_batch_kernel<targs...> over fr.n frames
+#define WT_SK_LAUNCH(KN, grid, block, stream, args, ...)                                                                     \
+    do {                                                                                                                   \
+        if constexpr (BATCH)                                                                                               \
+            hipLaunchKernelGGL((KN##_batch_kernel<__VA_ARGS__>), dim3((grid).x, (grid).y, (unsigned)fr.n), (block), 0,    \
+                               (stream), WtFrameArgs<std::decay_t<decltype(args)>>{(args), fr.fstride, fr.ftab});       \
+        else                                                                                                               \
+            hipLaunchKernelGGL((KN##_kernel<__VA_ARGS__>), (grid), (block), 0, (stream), (args));                          \
+    } while (0)
+
 // chunking of the polyphase chains: enough (phase, chunk) items to fill the chip, chunks long
 // enough that the K-1 warm-up rows stay a small fraction.  gx = workgroups (of 64 x 4 lanes) along x.
 template <typename T>
@@ -73,8 +91,8 @@ static int wt_march_geometry(const Geo &g, int s, ChainArgsT<T> &a, dim3 &grid, 
 }
 
 // Row kernel (taps from an LDS copy of the row) where the horizontal halo fits the workgroup.
-template <typename T, int K, int MODE, int NW>
-static int wt_launch_row_t(const StencilCtx &sc, ChainArgsT<T> a, int HX, const char *name)
+template <typename T, int K, int MODE, int NW, bool BATCH = false>
+static int wt_launch_row_t(const StencilCtx &sc, ChainArgsT<T> a, int HX, const char *name, const WtFrames &fr = WtFrames())
 {
     constexpr int PX = WtVec<T>::PX;
     constexpr int NL = NW * 64;
@@ -101,16 +119,17 @@ static int wt_launch_row_t(const StencilCtx &sc, ChainArgsT<T> a, int HX, const 
     if (gy > 65535) WT_FAIL("row kernel: grid too large");
     dim3 grid(nx, (unsigned)gy), block(NL);
     ProfScope ps(sc.ctx, name, sc.stream);
-    if (d < PX) hipLaunchKernelGGL((wt_row_kernel<T, K, MODE, true, NW>), grid, block, 0, sc.stream, ra);
-    else hipLaunchKernelGGL((wt_row_kernel<T, K, MODE, false, NW>), grid, block, 0, sc.stream, ra);
+    if (d < PX) WT_SK_LAUNCH(wt_row, grid, block, sc.stream, ra, T, K, MODE, true, NW);
+    else WT_SK_LAUNCH(wt_row, grid, block, sc.stream, ra, T, K, MODE, false, NW);
     WT_HIP(hipGetLastError());
     return 0;
 }
 
-template <typename T>
+template <typename T, bool BATCH = false>
 static const char *wt_row_name(int mode)
 {
     constexpr bool f64 = sizeof(T) == 8;
+    if (BATCH) return mode == MODE_DECOMP ? "wt_row_batch_kernel<decomp>" : "wt_row_batch_kernel<wow>";
     switch (mode) {
         case MODE_SMOOTH: return f64 ? "wt64_row_kernel<smooth>" : "wt_row_kernel<smooth>";
         case MODE_SMOOTH_SQ: return f64 ? "wt64_row_kernel<smooth_sq>" : "wt_row_kernel<smooth_sq>";
@@ -120,10 +139,11 @@ static const char *wt_row_name(int mode)
     }
 }
 
-template <typename T>
+template <typename T, bool BATCH = false>
 static const char *wt_lattice_name(int mode)
 {
     constexpr bool f64 = sizeof(T) == 8;
+    if (BATCH) return mode == MODE_DECOMP ? "wt_lattice_batch_kernel<decomp>" : "wt_lattice_batch_kernel<wow>";
     switch (mode) {
         case MODE_SMOOTH: return f64 ? "wt64_lattice_kernel<smooth>" : "wt_lattice_kernel<smooth>";
         case MODE_SMOOTH_SQ: return f64 ? "wt64_lattice_kernel<smooth_sq>" : "wt_lattice_kernel<smooth_sq>";
@@ -134,9 +154,10 @@ static const char *wt_lattice_name(int mode)
 }
 
 // One scale of a built-in family: lattice kernel for the large dilations, row kernel where the x halo
-// fits a workgroup, the chain kernel otherwise.  `name`: profiler name of the chain kernel.
-template <typename T, int MODE>
-static int wt_launch_stencil(const StencilCtx &sc, ChainArgsT<T> a, int s, const char *name)
+// fits a workgroup, the chain kernel otherwise.  `name`: profiler name of the chain kernel.  BATCH: the same
+// choice for each of the frames `fr` (wt_batch), one launch.
+template <typename T, int MODE, bool BATCH = false>
+static int wt_launch_stencil(const StencilCtx &sc, ChainArgsT<T> a, int s, const char *name, const WtFrames &fr = WtFrames())
 {
     constexpr int PX = WtVec<T>::PX;
     const bool no_row = !g_opt_row_kernel;
@@ -157,28 +178,30 @@ static int wt_launch_stencil(const StencilCtx &sc, ChainArgsT<T> a, int s, const
         const int J = (g.W + d - 1) / d;                          // lattice columns per phase
         const int tx = ((J + lat_c - 1) / lat_c) * (d / PX);      // threads along x
         WT_TRY(wt_chain_geometry<T>(g, s, a, grid, block, (tx + 63) / 64));
-        ProfScope ps(sc.ctx, wt_lattice_name<T>(MODE), sc.stream);
-        if (b3 && lat_c == 4) hipLaunchKernelGGL((wt_lattice_kernel<T, 5, MODE, 4>), grid, block, 0, sc.stream, a);
-        else if (b3) hipLaunchKernelGGL((wt_lattice_kernel<T, 5, MODE, 2>), grid, block, 0, sc.stream, a);
-        else if (lat_c == 4) hipLaunchKernelGGL((wt_lattice_kernel<T, 3, MODE, 4>), grid, block, 0, sc.stream, a);
-        else hipLaunchKernelGGL((wt_lattice_kernel<T, 3, MODE, 2>), grid, block, 0, sc.stream, a);
+        ProfScope ps(sc.ctx, wt_lattice_name<T, BATCH>(MODE), sc.stream);
+        if (b3 && lat_c == 4) WT_SK_LAUNCH(wt_lattice, grid, block, sc.stream, a, T, 5, MODE, 4);
+        else if (b3) WT_SK_LAUNCH(wt_lattice, grid, block, sc.stream, a, T, 5, MODE, 2);
+        else if (lat_c == 4) WT_SK_LAUNCH(wt_lattice, grid, block, sc.stream, a, T, 3, MODE, 4);
+        else WT_SK_LAUNCH(wt_lattice, grid, block, sc.stream, a, T, 3, MODE, 2);
         WT_HIP(hipGetLastError());
         return 0;
     }
     // (halo lanes on both sides of a workgroup of NW * 64 lanes of PX pixels)
     if (!no_row && 2 * HX <= 64 * PX) {
-        return b3 ? wt_launch_row_t<T, 5, MODE, 4>(sc, a, HX, wt_row_name<T>(MODE)) : wt_launch_row_t<T, 3, MODE, 4>(sc, a, HX, wt_row_name<T>(MODE));
+        return b3 ? wt_launch_row_t<T, 5, MODE, 4, BATCH>(sc, a, HX, wt_row_name<T, BATCH>(MODE), fr)
+                  : wt_launch_row_t<T, 3, MODE, 4, BATCH>(sc, a, HX, wt_row_name<T, BATCH>(MODE), fr);
     }
     if (!no_row && 2 * HX <= 128 * PX) {
-        return b3 ? wt_launch_row_t<T, 5, MODE, 8>(sc, a, HX, wt_row_name<T>(MODE)) : wt_launch_row_t<T, 3, MODE, 8>(sc, a, HX, wt_row_name<T>(MODE));
+        return b3 ? wt_launch_row_t<T, 5, MODE, 8, BATCH>(sc, a, HX, wt_row_name<T, BATCH>(MODE), fr)
+                  : wt_launch_row_t<T, 3, MODE, 8, BATCH>(sc, a, HX, wt_row_name<T, BATCH>(MODE), fr);
     }
     WT_TRY(wt_chain_geometry<T>(g, s, a, grid, block));
     ProfScope ps(sc.ctx, name, sc.stream);
     const bool small = a.d < PX;
-    if (b3 && small) hipLaunchKernelGGL((wt_chain_kernel<T, 5, MODE, true>), grid, block, 0, sc.stream, a);
-    else if (b3) hipLaunchKernelGGL((wt_chain_kernel<T, 5, MODE, false>), grid, block, 0, sc.stream, a);
-    else if (small) hipLaunchKernelGGL((wt_chain_kernel<T, 3, MODE, true>), grid, block, 0, sc.stream, a);
-    else hipLaunchKernelGGL((wt_chain_kernel<T, 3, MODE, false>), grid, block, 0, sc.stream, a);
+    if (b3 && small) WT_SK_LAUNCH(wt_chain, grid, block, sc.stream, a, T, 5, MODE, true);
+    else if (b3) WT_SK_LAUNCH(wt_chain, grid, block, sc.stream, a, T, 5, MODE, false);
+    else if (small) WT_SK_LAUNCH(wt_chain, grid, block, sc.stream, a, T, 3, MODE, true);
+    else WT_SK_LAUNCH(wt_chain, grid, block, sc.stream, a, T, 3, MODE, false);
     WT_HIP(hipGetLastError());
     return 0;
 }
@@ -189,6 +212,9 @@ static int wt_launch_stencil(const StencilCtx &sc, ChainArgsT<T> a, int s, const
 // ---------------------------------------------------------------------------------------------
 // one scale in `mode` (MODE_*) on float planes; `name`: profiler name of the chain kernel
 int wt32_stencil_launch(const StencilCtx &sc, int mode, const ChainArgsT<float> &a, int s, const char *name);
+// one scale in `mode` (MODE_DECOMP, MODE_WOW_PLAIN, MODE_WOW_GAMMA) on the float planes of the frames `fr` of a batch
+// (wt_stencil32_batch.hip): every frame as wt32_stencil_launch would run it alone, one launch
+int wt32_stencil_batch_launch(const StencilCtx &sc, int mode, const ChainArgsT<float> &a, int s, const char *name, const WtFrames &fr);
 // one scale in `mode` (MODE_*) on double planes
 int wt64_stencil_launch(const StencilCtx &sc, int mode, const ChainArgsT<double> &a, int s);
 // the range-weighted dilated filter of one scale (watroo/wavelets.py:74-105) on double planes: the

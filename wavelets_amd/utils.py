@@ -238,12 +238,7 @@ def wow(data,
     if type(data) is np.ndarray:                                          # ref:121-127
         if data.ndim > 3:
             raise ValueError("Unsupported number of dimensions")
-        max_scales = int(np.round(np.log2(min(data.shape))
-                                  - np.log2(len(scaling_function.coefficients_1d))))
-        if n_scales is None:
-            n_scales = max_scales if h < 1 else len(denoise_coefficients)
-        elif n_scales > max_scales:
-            n_scales = max_scales
+        n_scales = _wow_n_scales(data.shape, scaling_function, n_scales, h, denoise_coefficients)
         n_dims = data.ndim
     elif type(data) is Coefficients:                                      # ref:128-131
         n_scales = len(data) - 1
@@ -252,11 +247,7 @@ def wow(data,
     else:
         raise ValueError('Unknown input type')                            # ref:133
 
-    max_scales = len(scaling_function(n_dims).sigma_e(bilateral=bilateral))
-    if len(denoise_coefficients) >= max_scales:                           # ref:136-138
-        warnings.warn('Required number of scales lager then the maximum for scaling '
-                      f'function. Using {max_scales}.')
-        n_scales = max_scales
+    n_scales = _wow_scale_limit(n_scales, scaling_function, n_dims, bilateral, denoise_coefficients)
 
     if bilateral is None:                                                 # ref:140-146
         sigma_bilateral = None
@@ -282,6 +273,78 @@ def wow(data,
     return recon, coefficients
 
 
+def _wow_n_scales(shape, scaling_function, n_scales, h, denoise_coefficients):
+    """n_scales of wow() for an array of `shape` (ref:122-127)"""
+    max_scales = int(np.round(np.log2(min(shape))
+                              - np.log2(len(scaling_function.coefficients_1d))))
+    if n_scales is None:
+        n_scales = max_scales if h < 1 else len(denoise_coefficients)
+    elif n_scales > max_scales:
+        n_scales = max_scales
+    return n_scales
+
+
+def _wow_scale_limit(n_scales, scaling_function, n_dims, bilateral, denoise_coefficients):
+    """n_scales capped by the scaling function's sigma_e table, with the reference's warning (ref:135-138)"""
+    max_scales = len(scaling_function(n_dims).sigma_e(bilateral=bilateral))
+    if len(denoise_coefficients) >= max_scales:                           # ref:136-138
+        warnings.warn('Required number of scales lager then the maximum for scaling '
+                      f'function. Using {max_scales}.')
+        n_scales = max_scales
+    return n_scales
+
+
+def _wow_lists(weights, denoise_coefficients, n_scales):
+    """(recomposition weights, per-scale denoise sigmas) of wow(), both n_scales + 1 long (ref:160-170)"""
+    recomposition_weights = _pad_list(weights, n_scales, 1)               # ref:160-163
+    sdc = copy.copy(denoise_coefficients)                                 # ref:165-170
+    if len(sdc) < n_scales:
+        sdc.extend([0, ] * (n_scales - len(sdc)))
+    if len(sdc) == n_scales:
+        sdc.extend([1, ])
+    return recomposition_weights, sdc
+
+
+def _wow_needs_moments(s, n_scales, preserve_variance, whitening, h):
+    """whether the factor of scale s needs the plane's {sum, sumsq} (np.std / np.mean(power), ref:178-189)"""
+    return preserve_variance or (s == n_scales and whitening and h < 1)
+
+
+def _wow_factor(s, n_scales, w, moments, npix, preserve_variance, whitening, h, ft):
+    """w * power_norm / local_power of scale s (ref:176-191, 203) in the data's compute type `ft`; the per-pixel
+    local power of the detail scales is the kernel's.  moments: plan.reduce(s) where _wow_needs_moments, else None"""
+    if moments is not None:
+        tot, tot2, _, _ = moments
+        mean = tot / npix
+        std = ft(np.sqrt(max(tot2 / npix - mean * mean, 0.0)))
+        rms = ft(np.sqrt(tot2 / npix))
+    if preserve_variance:                                                 # ref:178-184
+        power_norm = std if s == n_scales else rms
+    else:
+        power_norm = 1
+    if s == n_scales:                                                     # ref:185-191
+        if whitening and h < 1:
+            local_power = std
+            if local_power <= 0:
+                local_power = 1e-15
+        else:
+            local_power = 1
+        return ft(w * power_norm / local_power)                           # ref:203
+    return ft(w * power_norm)
+
+
+def _gamma_range(gamma_min, gamma_max, moments):
+    """(gamma_min, gamma_max) of the blend: the given bounds, else the gamma plane's min / max from
+    `moments` = plan.reduce(gamma plane) (ref:208-211)"""
+    if gamma_min is None or gamma_max is None:
+        _, _, lo, hi = moments
+        if gamma_min is None:
+            gamma_min = lo
+        if gamma_max is None:
+            gamma_max = hi
+    return gamma_min, gamma_max
+
+
 def _wow_device(coefficients, n_scales, weights, whitening, denoise_coefficients, soft_threshold,
                 preserve_variance, gamma, gamma_min, gamma_max, h):
     """The device-resident part of wow (ref:157-217): per-scale loop, plane sum, gamma blend.
@@ -295,12 +358,7 @@ def _wow_device(coefficients, n_scales, weights, whitening, denoise_coefficients
     if use_gamma:
         plan.fill(_GAMMA_PLANE, 0.0)                                      # ref:157-158
 
-    recomposition_weights = _pad_list(weights, n_scales, 1)               # ref:160-163
-    sdc = copy.copy(denoise_coefficients)                                 # ref:165-170
-    if len(sdc) < n_scales:
-        sdc.extend([0, ] * (n_scales - len(sdc)))
-    if len(sdc) == n_scales:
-        sdc.extend([1, ])
+    recomposition_weights, sdc = _wow_lists(weights, denoise_coefficients, n_scales)   # ref:160-170
 
     nplanes = len(coefficients)
     gplane = _GAMMA_PLANE if use_gamma else PLANE_NONE
@@ -319,11 +377,7 @@ def _wow_device(coefficients, n_scales, weights, whitening, denoise_coefficients
 
     if use_gamma:                                                         # ref:207-217
         if gamma_min is None or gamma_max is None:
-            _, _, lo, hi = plan.reduce(_GAMMA_PLANE)
-            if gamma_min is None:
-                gamma_min = lo
-            if gamma_max is None:
-                gamma_max = hi
+            gamma_min, gamma_max = _gamma_range(gamma_min, gamma_max, plan.reduce(_GAMMA_PLANE))
         plan.gamma_blend(PLANE_OUT, _GAMMA_PLANE, gamma_min, gamma_max, 1 / gamma, h)
 
     return plan
@@ -341,29 +395,13 @@ def _wow_scales(plan, coefficients, n_scales, nplanes, recomposition_weights, sd
     for s, (_, w, d) in enumerate(zip(range(nplanes), recomposition_weights, sdc)):  # ref:174
         if s and s == early_at and hasattr(plan, "plane_sum_early") and plan.plane_sum_early(s, PLANE_OUT):
             early = s
-        need_moments = preserve_variance or (s == n_scales and whitening and h < 1)
-        if need_moments:
-            tot, tot2, _, _ = plan.reduce(s)
-            mean = tot / npix
-            std = ft(np.sqrt(max(tot2 / npix - mean * mean, 0.0)))
-            rms = ft(np.sqrt(tot2 / npix))
-        if preserve_variance:                                             # ref:178-184
-            power_norm = std if s == n_scales else rms
-        else:
-            power_norm = 1
+        moments = plan.reduce(s) if _wow_needs_moments(s, n_scales, preserve_variance, whitening, h) else None
+        factor = _wow_factor(s, n_scales, w, moments, npix, preserve_variance, whitening, h, ft)
         if s == n_scales:                                                 # ref:185-191
-            if whitening and h < 1:
-                local_power = std
-                if local_power <= 0:
-                    local_power = 1e-15
-            else:
-                local_power = 1
-            factor = ft(w * power_norm / local_power)                     # ref:203
             plan.wow_update(s, PLANE_NONE, 0.0, soft_threshold, PLANE_NONE, factor, gplane)
         else:
             t = coefficients._tau(d, s, soft_threshold)                   # ref:199
             tau, noise_plane = (0.0, PLANE_NONE) if t is None else t
-            factor = ft(w * power_norm)
             if whitening and h < 1 and coefficients._ndim == 3:           # ref:193-196 on a cube
                 # local power = 3-D conv_s(c^2): per-slice 2-D filter + axis-0 filter
                 plan.binary("mul", s, s, _SQ_PLANE)
