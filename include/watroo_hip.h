@@ -598,6 +598,13 @@ int wt_batch_download(wt_batch *batch, int plane, int f0, int nf, float *host, i
 int wt_batch_plane_ptr(wt_batch *batch, int plane, void **ptr, int64_t *frame_stride);
 /* wt_decompose per frame (watroo/wavelets.py:408-444 via AtrousTransform.__call__, ref:307-328); flags bit0 */
 int wt_batch_decompose(wt_batch *batch, int nf, int src, int level, int flags);
+/* wt_decompose_bilateral per frame (watroo/wavelets.py:433-442: the range-weighted branch of atrous, variance of
+ * :434-436 formed in the march): scale s reads the current smooth plane, writes c_{s+1} to a scratch plane (planes
+ * WT_PLANE_SCRATCH(0/1) ping-pong; plane `level` on the last scale) and w_s to plane s.  One launch per scale for all
+ * active frames.  sigma_b: `level` entries.  flags: reserved (the two-kernel form and the side-stream overlap of
+ * wt_decompose_bilateral are not carried over). */
+int wt_batch_decompose_bilateral(wt_batch *batch, int nf, int src, int level, const double *sigma_b,
+                                 int bilateral_scaling, int flags);
 /* wt_decompose_sum per frame: planes + np.sum(planes, axis=0) (watroo/utils.py:98) in the same passes */
 int wt_batch_decompose_sum(wt_batch *batch, int nf, int src, int level, int dst, int flags);
 /* wt_decompose_pass / wt_decompose_pass_sum per frame (utils.denoise, watroo/utils.py:95-98, interleaved) */

@@ -5,7 +5,9 @@ trip per reduction / median for all frames) against the per-frame loop on the sa
   * device-resident wow (transform + per-scale updates + sum): batched vs a loop over pre-acquired per-frame plans
     (HIP events around the whole stack; median / min / max of the samples);
   * host to host: wow_stack vs a plain loop of wow() (wall clock).
-    python tools/bench_wow_stack.py [samples]"""
+--bilateral: the same with bilateral=1 (the flagship flow wow(img, bilateral=1, denoise_coefficients=[5, 2])): the
+batched bilateral march (wt_batch_decompose_bilateral) against per-frame wt_decompose_bilateral.
+    python tools/bench_wow_stack.py [samples] [--bilateral]"""
 import json
 import os
 import sys
@@ -18,7 +20,7 @@ sys.path.insert(0, ROOT)
 import wavelets_amd as W                      # noqa: E402
 from wavelets_amd import _lib as L            # noqa: E402
 from wavelets_amd import batch as B           # noqa: E402
-from wavelets_amd.utils import _wow_device, _wow_n_scales  # noqa: E402
+from wavelets_amd.utils import _wow_device, _wow_n_scales, _wow_sigma_bilateral  # noqa: E402
 from wavelets_amd.wavelets import Coefficients  # noqa: E402
 
 SHAPES = [(64, 512), (64, 1024), (16, 2048)]
@@ -54,7 +56,9 @@ def wall(fn, n, warm=1):
 
 
 def main():
-    samples = int(sys.argv[1]) if len(sys.argv) > 1 else 15
+    argv = [a for a in sys.argv[1:] if a != "--bilateral"]
+    bil = 1 if "--bilateral" in sys.argv[1:] else None
+    samples = int(argv[0]) if argv else 15
     ctx = L.default_context()
     for N, side in SHAPES:
         level = _wow_n_scales((side, side), W.B3spline, None, 0, DC)
@@ -67,16 +71,23 @@ def main():
             p = L.Plan(ctx, side, side, L.B3SPLINE, level)
             p.upload(L.PLANE_INPUT, fr[f])
             plans.append(p)
-        rec = {"shape": [N, side, side], "n_scales": level, "denoise_coefficients": DC}
+        rec = {"shape": [N, side, side], "n_scales": level, "denoise_coefficients": DC, "bilateral": bil}
+        sb = _wow_sigma_bilateral(bil, level)
 
         def batched():
-            bp.decompose(N, L.PLANE_INPUT, level)
-            B._wow_batch_device(bp, N, [None] * N, W.B3spline, level, [], True, DC, True, False, 3.2, None, None, 0)
+            if bil is None:
+                bp.decompose(N, L.PLANE_INPUT, level)
+            else:
+                bp.decompose_bilateral(N, L.PLANE_INPUT, level, sb, False)
+            B._wow_batch_device(bp, N, [None] * N, W.B3spline, level, [], True, DC, True, False, 3.2, None, None, 0, bil)
 
         def loop():
             for p in plans:
-                p.decompose(L.PLANE_INPUT, level, L.FLAG_FUSED | L.FLAG_MEDIAN_HIST)
-                c = Coefficients(p, W.B3spline(2), None)
+                if bil is None:
+                    p.decompose(L.PLANE_INPUT, level, L.FLAG_FUSED | L.FLAG_MEDIAN_HIST)
+                else:
+                    p.decompose_bilateral(L.PLANE_INPUT, level, sb, False, 0)     # (AtrousTransform._run)
+                c = Coefficients(p, W.B3spline(2), sb)
                 _wow_device(c, level, [], True, DC, True, False, 3.2, None, None, 0)
                 c._plan = None                   # (the plan stays ours: not released to the pool)
 
@@ -87,8 +98,8 @@ def main():
         bp.close()
         for p in plans:
             p.close()
-        hb = stats(wall(lambda: W.wow_stack(fr, denoise_coefficients=DC), max(3, samples // 3)))
-        hl = stats(wall(lambda: [W.wow(f, denoise_coefficients=DC) for f in fr], max(3, samples // 3)))
+        hb = stats(wall(lambda: W.wow_stack(fr, denoise_coefficients=DC, bilateral=bil), max(3, samples // 3)))
+        hl = stats(wall(lambda: [W.wow(f, denoise_coefficients=DC, bilateral=bil) for f in fr], max(3, samples // 3)))
         rec["host_to_host"] = {"wow_stack": hb, "wow_loop": hl, "speedup": hl["median_ms"] / hb["median_ms"]}
         L.trim_batches()
         print(json.dumps(rec), flush=True)

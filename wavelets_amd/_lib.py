@@ -203,6 +203,8 @@ SIGNATURES = {
     "wt_batch_download": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _fp, _i64]),
     "wt_batch_plane_ptr": (_c.c_int, [_vp, _c.c_int, _c.POINTER(_vp), _c.POINTER(_i64)]),
     "wt_batch_decompose": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch_decompose_bilateral": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
+                                                _c.c_int, _c.c_int]),
     "wt_batch_decompose_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "wt_batch_decompose_pass": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "wt_batch_decompose_pass_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
@@ -966,6 +968,11 @@ class BatchPlan:
 
     def decompose(self, nf, src, level, flags=FLAG_FUSED):
         check(load().wt_batch_decompose(self._h, nf, src, level, flags))
+
+    def decompose_bilateral(self, nf, src, level, sigma_b, bilateral_scaling=False, flags=0):
+        """Plan.decompose_bilateral for frames 0 .. nf-1: one launch of the batched march per scale"""
+        arr = (_c.c_double * max(level, 1))(*[float(v) for v in sigma_b[:level]])
+        check(load().wt_batch_decompose_bilateral(self._h, nf, src, level, arr, int(bilateral_scaling), flags))
 
     def decompose_sum(self, nf, src, level, dst=PLANE_OUT, flags=FLAG_FUSED):
         check(load().wt_batch_decompose_sum(self._h, nf, src, level, dst, flags))

@@ -7,18 +7,19 @@ back in one host round trip, and the pointwise steps run once over the stack.
     wow_stack(frames, ...)              == np.stack([wow(f, ..., noise=noise_i, ...)[0] for f in frames])
 
 bit for bit.  The sequence of operations per frame is the per-frame path's own (wavelets._interleave_split,
-_scalar_tau, _noise_from_median; utils._wow_lists, _wow_factor, _gamma_range).  Inputs the batched engine does
-not cover run the per-frame loop (batch_eligible / wow_eligible say which)."""
+_scalar_tau, _noise_from_median; utils._wow_lists, _wow_factor, _gamma_range).  With bilateral= the transform
+is the batched bilateral march (one launch per scale for all frames, bilateral_eligible).  Inputs the batched
+engine does not cover run the per-frame loop (batch_eligible / wow_eligible / bilateral_eligible say which)."""
 import numpy as np
 
 from . import _lib
 from ._lib import PLANE_INPUT, PLANE_OUT, PLANE_NONE, PLANE_SCRATCH, FLAG_FUSED
 from .wavelets import (AtrousTransform, B3spline, _family_of, _needs_generic, _interleave_split, _scalar_tau,
-                       _noise_from_median)
+                       _noise_from_median, _sigma_bilateral_list)
 from .utils import (denoise, wow, _GAMMA_PLANE, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments,
-                    _wow_factor, _gamma_range)
+                    _wow_factor, _gamma_range, _wow_sigma_bilateral)
 
-__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'batch_eligible', 'wow_eligible']
+__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'batch_eligible', 'wow_eligible', 'bilateral_eligible']
 
 # levels whose fused schedule has a kernel for every pass (wt_plan_fused_ok), both built-in families: L = 1 is
 # a single-scale pass, and from 9 scales on the schedules hold single-scale passes at D >= 256 (wt_fused_has_pass)
@@ -82,6 +83,35 @@ def wow_eligible(frames, n_scales, scaling_function=B3spline, bilateral=None, no
     return _engine_eligible(frames, scaling_function, bilateral, noise_per_frame)
 
 
+# scales of the batched bilateral transform: one launch of the march per scale, up to the per-scale kernels' limit
+# (wt_decompose_bilateral: scales 0..24)
+BILATERAL_MAX_LEVEL = 25
+
+
+def _real_scalar(v):
+    return isinstance(v, (bool, int, float, np.bool_, np.integer, np.floating))
+
+
+def bilateral_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=()):
+    """True when the batched engine computes this stack WITH bilateral filtering (host logic): the conditions of
+    batch_eligible / wow_eligible for the frames, the scaling function and the noise levels (scalars that are not
+    arrays), `bilateral` a real scalar / bool or a list of them, and 1 <= level <= what wt_decompose_bilateral
+    (25) and the family's sigma_e(bilateral=...) table admit.  False without bilateral filtering: those stacks are
+    batch_eligible's / wow_eligible's.  Everything else runs the per-frame loop."""
+    if bilateral is None:
+        return False
+    if not (_real_scalar(bilateral) or (type(bilateral) is list and all(_real_scalar(v) for v in bilateral))):
+        return False
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level < 1:
+        return False
+    if noise_per_frame is not None and any(type(n) is np.ndarray for n in noise_per_frame):
+        return False
+    if not _engine_eligible(frames, scaling_function, None, noise_per_frame):
+        return False
+    table = scaling_function(2).sigma_e(bilateral=bilateral)
+    return table is not None and level <= min(BILATERAL_MAX_LEVEL, len(table))
+
+
 def _engine_eligible(frames, scaling_function, bilateral, noise_per_frame):
     """the conditions of batch_eligible / wow_eligible other than the level"""
     if not isinstance(frames, np.ndarray) or frames.ndim != 3 or frames.dtype != np.dtype(np.float32) \
@@ -107,12 +137,13 @@ def _chunks(frames, level):
     return _lib.batch_chunks(N, H, W, level)
 
 
-def transform_stack(frames, level, scaling_function=B3spline, out=None):
-    """(N, level+1, H, W) float32: the standard transform of every frame (AtrousTransform(scaling_function)
-    (frame, level).data, ref:307-328), batched."""
+def transform_stack(frames, level, scaling_function=B3spline, out=None, bilateral=None, bilateral_scaling=False):
+    """(N, level+1, H, W) float32: the standard transform of every frame (AtrousTransform(scaling_function,
+    bilateral, bilateral_scaling)(frame, level).data, ref:307-328), batched."""
     fr = _as_frames(frames)
-    if not batch_eligible(fr, level, scaling_function):
-        res = np.stack([AtrousTransform(scaling_function)(f, level).data for f in fr])
+    bil = bilateral_eligible(fr, level, scaling_function, bilateral)
+    if not bil and not batch_eligible(fr, level, scaling_function, bilateral):
+        res = np.stack([AtrousTransform(scaling_function, bilateral, bilateral_scaling)(f, level).data for f in fr])
         if out is not None:
             out[...] = res
             return out
@@ -131,7 +162,11 @@ def transform_stack(frames, level, scaling_function=B3spline, out=None):
     try:
         for f0, nf in chunks:
             bp.upload(PLANE_INPUT, fr[f0:f0 + nf])
-            bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
+            if bil:                                                # ref:433-442, AtrousTransform._run
+                sb = _sigma_bilateral_list(bilateral, level)
+                bp.decompose_bilateral(nf, PLANE_INPUT, level, sb, bilateral_scaling)
+            else:
+                bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
             for s in range(level + 1):
                 bp.download(s, nf, out=out[f0:f0 + nf, s])         # straight into the caller's cube
     finally:
@@ -156,7 +191,8 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
     N = len(fr)
     nl = _noise_list(noise, N)
     level = len(weights)
-    if not batch_eligible(fr, level, scaling_function, bilateral, nl):
+    bil = bilateral_eligible(fr, level, scaling_function, bilateral, nl)
+    if not bil and not batch_eligible(fr, level, scaling_function, bilateral, nl):
         per = nl if nl is not None else [noise] * N
         res = np.stack([denoise(f, weights, scaling_function, n_i, bilateral, soft_threshold, anscombe)
                         for f, n_i in zip(fr, per)])
@@ -173,11 +209,12 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
         return out
     ctx = _lib.default_context()
     sf = scaling_function(2)
-    sigma_e = sf.sigma_e()
+    sigma_e = sf.sigma_e(bilateral=bilateral)
     fam = _family_of(sf)
     sigma = list(weights)
     wgts = (1,) * len(sigma)
-    sched = _lib.schedule(fam, level, True)
+    # (bilateral: no fused schedule - the whole transform, then the thresholds, wavelets._decompose_denoise_sum)
+    sched = [] if bil else _lib.schedule(fam, level, True)
     entries, k, covered = _interleave_split(sched, level, sigma, wgts)
     chunks = _chunks(fr, level)
     bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, fam, level)
@@ -189,7 +226,11 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
                 bp.anscombe(nf, PLANE_INPUT, PLANE_INPUT)                        # ref:93-94
             whole = k == 0 or k == len(sched)
             if whole:                    # transform, then Coefficients._denoise_sum over every plane
-                bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
+                if bil:
+                    sb = _sigma_bilateral_list(bilateral, level)
+                    bp.decompose_bilateral(nf, PLANE_INPUT, level, sb, False)
+                else:
+                    bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
                 used = entries
             else:                        # the passes before the threshold step (wavelets._decompose_denoise_sum)
                 cur = PLANE_INPUT
@@ -244,7 +285,8 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
     # n_scales once for the shared shape, as wow() resolves it for one frame (ref:121-138)
     L = _wow_n_scales(shape, scaling_function, n_scales, h, denoise_coefficients)
     L = _wow_scale_limit(L, scaling_function, 2, bilateral, denoise_coefficients)
-    if not wow_eligible(fr, L, scaling_function, bilateral, nl):
+    bil = bilateral_eligible(fr, L, scaling_function, bilateral, nl)
+    if not bil and not wow_eligible(fr, L, scaling_function, bilateral, nl):
         per = nl if nl is not None else [noise] * N
         res = [wow(f, scaling_function, n_scales, noise=n_i, **kw) for f, n_i in zip(fr, per)]
         images = np.stack([r[0] for r in res])
@@ -267,9 +309,13 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
     try:
         for f0, nf in chunks:
             bp.upload(PLANE_INPUT, fr[f0:f0 + nf])
-            bp.decompose(nf, PLANE_INPUT, L, FLAG_FUSED)                            # ref:148-151
+            if bil:                                                                 # ref:140-151
+                sb = _sigma_bilateral_list(_wow_sigma_bilateral(bilateral, L), L)     # (wow's list, then the transform's)
+                bp.decompose_bilateral(nf, PLANE_INPUT, L, sb, bilateral_scaling)
+            else:
+                bp.decompose(nf, PLANE_INPUT, L, FLAG_FUSED)                        # ref:148-151
             _wow_batch_device(bp, nf, nl[f0:f0 + nf], scaling_function, L, weights, whitening, denoise_coefficients,
-                              soft_threshold, preserve_variance, gamma, gamma_min, gamma_max, h)
+                              soft_threshold, preserve_variance, gamma, gamma_min, gamma_max, h, bilateral)
             bp.download(PLANE_OUT, nf, out=out[f0:f0 + nf])
             if return_coefficients:
                 for s in range(nplanes):
@@ -280,11 +326,12 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
 
 
 def _wow_batch_device(bp, nf, noises, scaling_function, n_scales, weights, whitening, denoise_coefficients,
-                      soft_threshold, preserve_variance, gamma, gamma_min, gamma_max, h):
+                      soft_threshold, preserve_variance, gamma, gamma_min, gamma_max, h, bilateral=None):
     """The device-resident part of wow (ref:157-217, utils._wow_device / _wow_scales) for frames 0 .. nf-1 of a
     batch whose planes 0 .. n_scales hold the transform: whitened planes in place, the images in PLANE_OUT.
-    `noises`: one entry per frame (None: its MAD estimate, taken where the per-frame call's lazy _tau takes it)."""
-    sigma_e = scaling_function(2).sigma_e()
+    `noises`: one entry per frame (None: its MAD estimate, taken where the per-frame call's lazy _tau takes it).
+    `bilateral`: the transform's, for the sigma_e table (Coefficients.sigma_e, ref:122-124)."""
+    sigma_e = scaling_function(2).sigma_e(bilateral=bilateral)
     nplanes = n_scales + 1
     recomposition_weights, sdc = _wow_lists(weights, denoise_coefficients, n_scales)       # ref:160-170
     use_gamma = h > 0

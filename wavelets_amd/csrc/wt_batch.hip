@@ -525,6 +525,47 @@ extern "C" int wt_batch_decompose(wt_batch *b, int nf, int src, int level, int f
     return batch_schedule_run(b, nf, src, level, false, WT_PLANE_NONE, "wt_batch_decompose");
 }
 
+// wt_decompose_bilateral (wt_transform.hip, watroo/wavelets.py:433-442) for the active frames: scale s reads `cur`,
+// writes c_{s+1} to a scratch plane (the two ping-pong; plane `level` on the last scale) and w_s to plane s, the
+// variance formed in the march with f1 = sigma_b[s]^2, f2 = s + 1 under bilateral_scaling.  One launch per scale for
+// all frames (wt_bilateral32_batch.hip); no two-kernel form, no side-stream overlap.
+extern "C" int wt_batch_decompose_bilateral(wt_batch *b, int nf, int src, int level, const double *sigma_b, int bilateral_scaling, int flags)
+{
+    (void)flags;
+    WT_TRY(check_frames(b, nf, "wt_batch_decompose_bilateral"));
+    WtGuard guard_(b->ctx);
+    if (!sigma_b) WT_FAIL("wt_batch_decompose_bilateral: null pointer");
+    if (level < 0 || level > b->max_level) WT_FAIL("wt_batch_decompose_bilateral: level %d exceeds the batch's max_level %d", level, b->max_level);
+    if (src >= 0 && src <= level) WT_FAIL("wt_batch_decompose_bilateral: src plane %d is one of the output planes", src);
+    if (src == WT_PLANE_SCRATCH(0) || src == WT_PLANE_SCRATCH(1)) WT_FAIL("wt_batch_decompose_bilateral: scratch planes 0/1 are used internally");
+    if (level > 25) WT_FAIL("wt_batch_decompose_bilateral: scale %d out of range", level - 1);
+    float *in = nullptr;
+    WT_TRY(bplane(b, src, &in));
+    if (level == 0) {
+        float *d = nullptr;
+        WT_TRY(bplane(b, 0, &d));
+        WT_HIP(hipMemcpyAsync(d, in, (size_t)nf * (size_t)b->fstride * 4, hipMemcpyDeviceToDevice, b->ctx->stream));
+        return 0;
+    }
+    WtFrames fr;
+    fr.n = nf;
+    fr.fstride = b->fstride;
+    for (int s = 0; s < level; ++s) {
+        const int nxt = (s == level - 1) ? level : WT_PLANE_SCRATCH(s & 1);
+        float *oc = nullptr, *ow = nullptr;
+        WT_TRY(bplane(b, nxt, &oc));
+        WT_TRY(bplane(b, s, &ow));
+        ChainArgs a{};
+        a.in = in; a.out_c = oc; a.out_w = ow;
+        // variance = sdev_loc(c_s)^2-form * sigma_b[s]**2 (* (s+1))   watroo/wavelets.py:434-436
+        a.f1 = (float)(sigma_b[s] * sigma_b[s]);
+        a.f2 = bilateral_scaling ? (float)(s + 1) : 1.f;
+        WT_TRY(wt32_bilateral_batch_launch(batch_stencil_ctx(b), a, s, g_opt_bilateral_paired != 0, fr));
+        in = oc;
+    }
+    return 0;
+}
+
 extern "C" int wt_batch_decompose_sum(wt_batch *b, int nf, int src, int level, int dst, int flags)
 {
     WT_TRY(check_frames(b, nf, "wt_batch_decompose_sum"));

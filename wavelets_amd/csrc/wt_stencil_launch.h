@@ -215,6 +215,9 @@ int wt32_stencil_launch(const StencilCtx &sc, int mode, const ChainArgsT<float> 
 // one scale in `mode` (MODE_DECOMP, MODE_WOW_PLAIN, MODE_WOW_GAMMA) on the float planes of the frames `fr` of a batch
 // (wt_stencil32_batch.hip): every frame as wt32_stencil_launch would run it alone, one launch
 int wt32_stencil_batch_launch(const StencilCtx &sc, int mode, const ChainArgsT<float> &a, int s, const char *name, const WtFrames &fr);
+// one scale of the float32 bilateral transform (variance in the kernel, a.f1 / a.f2) on the frames `fr` of a batch
+// (wt_bilateral32_batch.hip): every frame as wt_bilateral2_kernel would run it alone, one launch
+int wt32_bilateral_batch_launch(const StencilCtx &sc, ChainArgsT<float> a, int s, bool paired, const WtFrames &fr);
 // one scale in `mode` (MODE_*) on double planes
 int wt64_stencil_launch(const StencilCtx &sc, int mode, const ChainArgsT<double> &a, int s);
 // the range-weighted dilated filter of one scale (watroo/wavelets.py:74-105) on double planes: the

@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #define WT_UNITS(X)                                                                                           \
-    X(core) X(transform) X(apps) X(stencil32) X(batch) X(stencil32_batch)                                             \
+    X(core) X(transform) X(apps) X(stencil32) X(batch) X(stencil32_batch) X(bilateral32_batch)                        \
     X(fused_f32_k5_acc0) X(fused_f32_k5_acc1) X(fused_f32_k5_acc2) X(fused_f32_k5_acc3)                       \
     X(fused_f32_k3_acc0) X(fused_f32_k3_acc1) X(fused_f32_k3_acc2) X(fused_f32_k3_acc3)                       \
     X(fused_f32_k5_batch_acc0) X(fused_f32_k5_batch_acc1) X(fused_f32_k5_batch_acc2)                            \

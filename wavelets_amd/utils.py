@@ -249,13 +249,7 @@ def wow(data,
 
     n_scales = _wow_scale_limit(n_scales, scaling_function, n_dims, bilateral, denoise_coefficients)
 
-    if bilateral is None:                                                 # ref:140-146
-        sigma_bilateral = None
-    else:
-        sigma_bilateral = copy.copy(bilateral) if type(bilateral) is list \
-            else [bilateral, ] * (n_scales + 1)
-        if len(sigma_bilateral) <= n_scales:
-            sigma_bilateral.extend([1, ] * (n_scales - len(sigma_bilateral) + 1))
+    sigma_bilateral = _wow_sigma_bilateral(bilateral, n_scales)           # ref:140-146
 
     if type(data) is np.ndarray:                                          # ref:148-151
         transform = AtrousTransform(scaling_function, bilateral=sigma_bilateral,
@@ -292,6 +286,18 @@ def _wow_scale_limit(n_scales, scaling_function, n_dims, bilateral, denoise_coef
                       f'function. Using {max_scales}.')
         n_scales = max_scales
     return n_scales
+
+
+def _wow_sigma_bilateral(bilateral, n_scales):
+    """the per-scale sigma_bilateral list wow() hands to its transform, n_scales + 1 long at least (ref:140-146):
+    None without bilateral filtering, a scalar repeated, a short list padded with 1"""
+    if bilateral is None:
+        return None
+    sigma_bilateral = copy.copy(bilateral) if type(bilateral) is list \
+        else [bilateral, ] * (n_scales + 1)
+    if len(sigma_bilateral) <= n_scales:
+        sigma_bilateral.extend([1, ] * (n_scales - len(sigma_bilateral) + 1))
+    return sigma_bilateral
 
 
 def _wow_lists(weights, denoise_coefficients, n_scales):

@@ -579,6 +579,16 @@ def _scalar_tau(sigma, noise, sigma_e_scale, soft=True):
     return tau, PLANE_NONE
 
 
+def _sigma_bilateral_list(bilateral, level):
+    """Per-scale sigma_bilateral list of a transform over `level` scales (ref:421-424): a scalar repeated, a list
+    copied and padded with 1 (AtrousTransform._sigma_bilateral; batch.py runs the same rule for a stack)."""
+    sb = copy.copy(bilateral) if type(bilateral) is list \
+        else [bilateral, ] * (level + 1)
+    if len(sb) <= level:
+        sb.extend([1, ] * (level - len(sb) + 1))
+    return sb
+
+
 def _interleave_split(sched, level, sigma, weights):
     """(entries, k, covered): the (scale, sigma, weight) entries Coefficients.denoise visits (zip truncation,
     ref:148), and where the threshold step goes in the fused schedule `sched` - after its first k passes,
@@ -1282,8 +1292,4 @@ class AtrousTransform:
 
     def _sigma_bilateral(self, level):
         """Per-scale sigma_bilateral list (ref:421-424)."""
-        sb = copy.copy(self.bilateral) if type(self.bilateral) is list \
-            else [self.bilateral, ] * (level + 1)
-        if len(sb) <= level:
-            sb.extend([1, ] * (level - len(sb) + 1))
-        return sb
+        return _sigma_bilateral_list(self.bilateral, level)
