@@ -646,6 +646,53 @@ int wt_batch_gamma_blend(wt_batch *batch, int nf, int recon, int gamma_plane, co
  * watroo/utils.py:205) */
 int wt_batch_plane_sum(wt_batch *batch, int nf, int first, int count, int dst);
 
+/* ---- batches of same-shape frames (float64) ------------------------------------------------
+ * A wt_batch64 is the wt_batch of the float64 engine: the stacks the reference computes in float64 (float64
+ * frames, and the int16 .. int64 / big-endian frames it recasts, watroo/wavelets.py:297, 319-320).  Planes hold the
+ * N frames back to back at the pitch of a wt_plan64 of that width (frame f at f * frame_stride doubles).  Every
+ * frame runs the per-frame float64 schedule, kernel choice and geometry with the frame as grid z, so a frame's
+ * result is bit-identical to the per-frame call on a wt_plan64.  Images (H >= 2) with a built-in family only;
+ * the transforms need an all-fused float64 schedule (wt_batch64_fused_ok).  Planes: 0..max_level,
+ * WT_PLANE_INPUT, WT_PLANE_OUT, WT_PLANE_SCRATCH(0/1) (used internally).  Operations take the number of ACTIVE
+ * frames nf (frames 0 .. nf-1). */
+typedef struct wt_batch64 wt_batch64;
+/* host logic: *ok = 1 when H x W frames of `family` have an all-fused float64 schedule of `level` scales
+ * (wt64_plan_fused_ok of a wt_plan64 of that shape) */
+int wt_batch64_fused_ok(int family, int64_t H, int64_t W, int level, int *ok);
+int wt_batch64_create(wt_ctx *ctx, int n, int H, int W, int family, int max_level, wt_batch64 **batch);
+int wt_batch64_destroy(wt_batch64 *batch);
+/* info[7] = {n, H, W, pitch, frame_stride, max_level, family} */
+int wt_batch64_info(wt_batch64 *batch, int64_t *info);
+/* frames [f0, f0+nf) of a plane <- / -> host frames of H x W contiguous doubles, host_frame_stride doubles apart
+ * (0 = H * W: a C-contiguous (nf, H, W) block) - as wt64_upload / wt64_download */
+int wt_batch64_upload(wt_batch64 *batch, int plane, int f0, int nf, const double *host, int64_t host_frame_stride);
+int wt_batch64_download(wt_batch64 *batch, int plane, int f0, int nf, double *host, int64_t host_frame_stride);
+/* wt64_upload_int for frames [f0, f0+nf): a C-contiguous (nf, H, W) block of element type `dtype` (WT_INT8 ..
+ * WT_FLOAT64, | WT_BYTESWAPPED) crosses PCIe as it is and is widened on the device (the reference's recast to
+ * float64, watroo/wavelets.py:297, 319-320) */
+int wt_batch64_upload_elems(wt_batch64 *batch, int plane, int f0, int nf, const void *host, int dtype);
+/* device pointer of frame 0 of a plane (allocated on first use) and the frame stride in doubles */
+int wt_batch64_plane_ptr(wt_batch64 *batch, int plane, void **ptr, int64_t *frame_stride);
+/* wt64_decompose per frame (watroo/wavelets.py:408-444 via AtrousTransform.__call__, ref:307-328); flags bit0 */
+int wt_batch64_decompose(wt_batch64 *batch, int nf, int src, int level, int flags);
+/* wt64_decompose_sum per frame: planes + np.sum(planes, axis=0) (watroo/utils.py:98) in the same passes */
+int wt_batch64_decompose_sum(wt_batch64 *batch, int nf, int src, int level, int dst, int flags);
+/* wt64_decompose_pass / wt64_decompose_pass_sum per frame (utils.denoise, watroo/utils.py:95-98, interleaved) */
+int wt_batch64_decompose_pass(wt_batch64 *batch, int nf, int cur, int nxt, int s0, int ns, int flags);
+int wt_batch64_decompose_pass_sum(wt_batch64 *batch, int nf, int cur, int nxt, int s0, int ns, int flags,
+                                  int sum_plane, int first, int last);
+/* np.median(np.abs(data[0])) of every active frame (watroo/wavelets.py:127): medians[nf], exact (the values
+ * wt64_abs_median gives), one host round trip */
+int wt_batch64_abs_median(wt_batch64 *batch, int nf, int plane, double *medians);
+/* wt64_denoise_sum per frame (Coefficients.denoise + np.sum, watroo/wavelets.py:145-149, utils.py:97-98): planes
+ * 0..count-1, the first n_den thresholded at tau[frame * n_den + k] (<= 0: significance one), weights wgt[k]
+ * shared by the frames; scalar noise only */
+int wt_batch64_denoise_sum(wt_batch64 *batch, int nf, int count, int dst, int n_den, const double *tau,
+                           const double *wgt, int soft, int write_back);
+/* generalized_anscombe over the active frames (watroo/utils.py:93-94, 99-100; as wt64_anscombe) */
+int wt_batch64_anscombe(wt_batch64 *batch, int nf, int src, int dst, double alpha, double g, double sigma,
+                        int inverse);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,25 @@ SIGNATURES = {
     "wt_batch_reduce": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double)]),
     "wt_batch_gamma_blend": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _fp, _fp, _c.c_float, _c.c_float]),
     "wt_batch_plane_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    # batches of same-shape frames in float64 (wt_batch64)
+    "wt_batch64_fused_ok": (_c.c_int, [_c.c_int, _i64, _i64, _c.c_int, _c.POINTER(_c.c_int)]),
+    "wt_batch64_create": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_vp)]),
+    "wt_batch64_destroy": (_c.c_int, [_vp]),
+    "wt_batch64_info": (_c.c_int, [_vp, _c.POINTER(_i64)]),
+    "wt_batch64_upload": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _i64]),
+    "wt_batch64_download": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _i64]),
+    "wt_batch64_upload_elems": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_int]),
+    "wt_batch64_plane_ptr": (_c.c_int, [_vp, _c.c_int, _c.POINTER(_vp), _c.POINTER(_i64)]),
+    "wt_batch64_decompose": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch64_decompose_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch64_decompose_pass": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch64_decompose_pass_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                                 _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch64_abs_median": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double)]),
+    "wt_batch64_denoise_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
+                                          _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
+    "wt_batch64_anscombe": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_double, _c.c_double,
+                                       _c.c_int]),
 }
 
 _lib = None
@@ -401,7 +420,7 @@ def _shutdown():
     otherwise destroys planes after the runtime's own static destructors ran)."""
     _host_pool.close()
     objs = list(_live)
-    for kind in ((Plan, Plan64, BatchPlan), (Context,)):
+    for kind in ((Plan, Plan64, BatchPlan, BatchPlan64), (Context,)):
         for o in objs:
             if isinstance(o, kind):
                 try:
@@ -900,22 +919,30 @@ BATCH_MAX_FRAMES = 65535                  # grid z of the fused launches (one fr
 BATCH_BYTES = int(os.environ.get("WATROO_HIP_BATCH_BYTES", str(4 << 30)))   # device bytes of one chunk of frames
 
 
-def batch_frame_bytes(H, W, level):
+def _batch_pitch(W, itemsize):
+    """row pitch in elements of a batch's planes: a wt_plan's (4 floats) or a wt_plan64's (2 doubles)"""
+    if itemsize not in (4, 8):
+        raise ValueError(f"itemsize {itemsize}: 4 (float32 batches) or 8 (float64 batches)")
+    return (W + 3) // 4 * 4 if itemsize == 4 else (W + 1) // 2 * 2
+
+
+def batch_frame_bytes(H, W, level, itemsize=4):
     """device bytes one frame of a batch takes: planes 0..level, input, output and two scratch planes at the
-    plan pitch (host logic, wt_batch_create)"""
-    return (level + 5) * H * ((W + 3) // 4 * 4) * 4
+    plan pitch (host logic, wt_batch_create; itemsize=8: wt_batch64_create's double planes)"""
+    return (level + 5) * H * _batch_pitch(W, itemsize) * itemsize
 
 
-def batch_chunks(n, H, W, level, budget=None, max_frames=BATCH_MAX_FRAMES, extra_planes=0):
+def batch_chunks(n, H, W, level, budget=None, max_frames=BATCH_MAX_FRAMES, extra_planes=0, itemsize=4):
     """[(first frame, frames)] of a stack of `n` frames: as many frames per chunk as `budget` bytes of planes
     (default BATCH_BYTES; at least one frame) and the grid allow, the last chunk the remainder.  `extra_planes`:
-    planes per frame beyond batch_frame_bytes' (wow's spare and gamma planes)."""
+    planes per frame beyond batch_frame_bytes' (wow's spare and gamma planes).  `itemsize`: bytes per pixel of
+    the planes (4: wt_batch, 8: wt_batch64)."""
     if n < 0:
         raise ValueError("negative frame count")
     if extra_planes < 0:
         raise ValueError("negative extra plane count")
     budget = BATCH_BYTES if budget is None else budget
-    frame = batch_frame_bytes(H, W, level) + int(extra_planes) * H * ((W + 3) // 4 * 4) * 4
+    frame = batch_frame_bytes(H, W, level, itemsize) + int(extra_planes) * H * _batch_pitch(W, itemsize) * itemsize
     per = max(1, min(int(budget // frame), int(max_frames)))
     return [(f0, min(per, n - f0)) for f0 in range(0, n, per)]
 
@@ -1038,18 +1065,123 @@ class BatchPlan:
         check(load().wt_batch_plane_sum(self._h, nf, first, count, dst))
 
 
-_batch_cache = {}        # id(ctx) -> [BatchPlan], most recently used last (its own small cache: not the plan pool)
+def batch64_fused_ok(family, H, W, level):
+    """True when H x W frames of `family` have an all-fused float64 schedule of `level` scales (host logic,
+    wt_batch64_fused_ok: what wt64_plan_fused_ok answers for a wt_plan64 of that shape)"""
+    ok = _c.c_int(0)
+    check(load().wt_batch64_fused_ok(int(family), int(H), int(W), int(level), _c.byref(ok)))
+    return bool(ok.value)
+
+
+class BatchPlan64:
+    """Double-precision planes of up to `n` frames of one H x W shape (wt_batch64): BatchPlan's operations for the
+    stacks the reference computes in float64.  upload / download move a C-contiguous (nf, H, W) block; integer
+    and big-endian frames cross as they are and are widened on the device (device_widens)."""
+
+    dtype = np.float64
+
+    def __init__(self, ctx, n, H, W, family, max_level):
+        self._h = _vp()
+        self.ctx = ctx
+        check(load().wt_batch64_create(ctx._h, n, H, W, family, max_level, _c.byref(self._h)))
+        info = (_i64 * 7)()
+        check(load().wt_batch64_info(self._h, info))
+        (self.n, self.H, self.W, self.pitch, self.frame_stride, self.max_level, self.family) = [int(v) for v in info]
+        _live.add(self)
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, _vp()
+            check(load().wt_batch64_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def upload(self, plane, frames, f0=0):
+        a = np.asarray(frames)
+        if a.ndim != 3 or a.shape[1:] != (self.H, self.W):
+            raise ValueError(f"frames of shape {a.shape[1:]} != batch frame shape {(self.H, self.W)}")
+        if a.dtype != np.float64 and device_widens(a.dtype):
+            a = np.ascontiguousarray(a)
+            code = _ELEM_CODES[a.dtype.str[1:]] | (16 if not a.dtype.isnative and a.itemsize > 1 else 0)
+            check(load().wt_batch64_upload_elems(self._h, plane, f0, a.shape[0], _vp(a.ctypes.data), code))
+            return
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        check(load().wt_batch64_upload(self._h, plane, f0, a.shape[0], a.ctypes.data_as(_dp), 0))
+
+    def download(self, plane, nf, out=None, f0=0):
+        """(nf, H, W) float64; `out` may be any (nf, H, W) float64 view whose frames are C-contiguous: the frames
+        land in place, page-locked result blocks by default (host_empty)"""
+        if out is None:
+            out = host_empty((nf, self.H, self.W), self.ctx, np.float64)
+        assert out.dtype == np.float64 and out.shape == (nf, self.H, self.W) and out.flags.writeable
+        assert out.strides[1:] == (self.W * 8, 8) and out.strides[0] % 8 == 0 and out.strides[0] >= self.H * self.W * 8
+        check(load().wt_batch64_download(self._h, plane, f0, nf, out.ctypes.data_as(_dp), out.strides[0] // 8))
+        return out
+
+    def plane_ptr(self, plane):
+        """(device pointer of frame 0, frame stride in doubles)"""
+        p, st = _vp(), _i64()
+        check(load().wt_batch64_plane_ptr(self._h, plane, _c.byref(p), _c.byref(st)))
+        return p.value, int(st.value)
+
+    def decompose(self, nf, src, level, flags=FLAG_FUSED):
+        check(load().wt_batch64_decompose(self._h, nf, src, level, flags))
+
+    def decompose_sum(self, nf, src, level, dst=PLANE_OUT, flags=FLAG_FUSED):
+        check(load().wt_batch64_decompose_sum(self._h, nf, src, level, dst, flags))
+
+    def decompose_pass(self, nf, cur, nxt, s0, ns, flags=FLAG_FUSED):
+        check(load().wt_batch64_decompose_pass(self._h, nf, cur, nxt, s0, ns, flags))
+
+    def decompose_pass_sum(self, nf, cur, nxt, s0, ns, flags, sum_plane, first, last):
+        check(load().wt_batch64_decompose_pass_sum(self._h, nf, cur, nxt, s0, ns, flags, sum_plane, int(first), int(last)))
+
+    def abs_median(self, nf, plane):
+        """np.median(np.abs(frame)) of `plane` for frames 0 .. nf-1 (np.float64 each, as Plan64.abs_median)"""
+        m = (_c.c_double * nf)()
+        check(load().wt_batch64_abs_median(self._h, nf, plane, m))
+        return [np.float64(v) for v in m]
+
+    def denoise_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT):
+        """`taus`: one row of thresholds per active frame (all rows of one length n_den)"""
+        n = len(wgts)
+        if len(taus) != nf or any(len(t) != n for t in taus):
+            raise ValueError("denoise_sum: one row of len(wgts) thresholds per frame")
+        ta = (_c.c_double * max(nf * n, 1))(*[float(t) for row in taus for t in row])
+        wa = (_c.c_double * max(n, 1))(*[float(w) for w in wgts])
+        check(load().wt_batch64_denoise_sum(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back)))
+
+    def anscombe(self, nf, src, dst, alpha=1.0, g=0.0, sigma=0.0, inverse=False):
+        check(load().wt_batch64_anscombe(self._h, nf, src, dst, alpha, g, sigma, int(inverse)))
+
+
+_batch_cache = {}        # id(ctx) -> [BatchPlan / BatchPlan64], most recently used last (its own small cache: not the plan pool)
 _BATCH_CACHE_MAX = 2
 
 
 def acquire_batch(ctx, n, H, W, family, max_level):
     """A BatchPlan of at least `n` frames of (H, W, family, max_level) on `ctx`: cached if available, else new."""
+    return _acquire(BatchPlan, ctx, n, H, W, family, max_level)
+
+
+def acquire_batch64(ctx, n, H, W, family, max_level):
+    """A BatchPlan64 of at least `n` frames of (H, W, family, max_level) on `ctx`: cached if available, else new
+    (the cache of acquire_batch; release with release_batch64)."""
+    return _acquire(BatchPlan64, ctx, n, H, W, family, max_level)
+
+
+def _acquire(cls, ctx, n, H, W, family, max_level):
     with _pool_lock:
         lst = _batch_cache.setdefault(id(ctx), [])
         for i, b in enumerate(lst):
-            if b._h and b.ctx is ctx and (b.H, b.W, b.family, b.max_level) == (H, W, family, max_level) and b.n >= n:
+            if type(b) is cls and b._h and b.ctx is ctx and (b.H, b.W, b.family, b.max_level) == (H, W, family, max_level) \
+                    and b.n >= n:
                 return lst.pop(i)
-    return BatchPlan(ctx, n, H, W, family, max_level)
+    return cls(ctx, n, H, W, family, max_level)
 
 
 def trim_batches():
@@ -1069,6 +1201,9 @@ def release_batch(b):
         lst.append(b)
         while len(lst) > _BATCH_CACHE_MAX:
             lst.pop(0).close()
+
+
+release_batch64 = release_batch          # (one cache for both kinds of batch)
 
 
 # ------------------------------------------------------------------------------------------

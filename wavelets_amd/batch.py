@@ -8,18 +8,21 @@ back in one host round trip, and the pointwise steps run once over the stack.
 
 bit for bit.  The sequence of operations per frame is the per-frame path's own (wavelets._interleave_split,
 _scalar_tau, _noise_from_median; utils._wow_lists, _wow_factor, _gamma_range).  With bilateral= the transform
-is the batched bilateral march (one launch per scale for all frames, bilateral_eligible).  Inputs the batched
-engine does not cover run the per-frame loop (batch_eligible / wow_eligible / bilateral_eligible say which)."""
+is the batched bilateral march (one launch per scale for all frames, bilateral_eligible).  Stacks the reference
+computes in float64 (float64 frames; int16 .. int64 and big-endian frames, which it recasts) run transform_stack
+and denoise_stack on the float64 batch (wt_batch64, batch64_eligible).  Inputs the batched engines do not cover
+run the per-frame loop (batch_eligible / batch64_eligible / wow_eligible / bilateral_eligible say which)."""
 import numpy as np
 
 from . import _lib
 from ._lib import PLANE_INPUT, PLANE_OUT, PLANE_NONE, PLANE_SCRATCH, FLAG_FUSED
 from .wavelets import (AtrousTransform, B3spline, _family_of, _needs_generic, _interleave_split, _scalar_tau,
-                       _noise_from_median, _sigma_bilateral_list)
+                       _noise_from_median, _sigma_bilateral_list, _result_dtype)
 from .utils import (denoise, wow, _GAMMA_PLANE, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments,
                     _wow_factor, _gamma_range, _wow_sigma_bilateral)
 
-__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'batch_eligible', 'wow_eligible', 'bilateral_eligible']
+__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'batch_eligible', 'batch64_eligible', 'wow_eligible',
+           'bilateral_eligible']
 
 # levels whose fused schedule has a kernel for every pass (wt_plan_fused_ok), both built-in families: L = 1 is
 # a single-scale pass, and from 9 scales on the schedules hold single-scale passes at D >= 256 (wt_fused_has_pass)
@@ -117,6 +120,14 @@ def _engine_eligible(frames, scaling_function, bilateral, noise_per_frame):
     if not isinstance(frames, np.ndarray) or frames.ndim != 3 or frames.dtype != np.dtype(np.float32) \
             or not frames.dtype.isnative:
         return False
+    if not _family_noise_eligible(scaling_function, bilateral, noise_per_frame):
+        return False
+    H, W = frames.shape[1:]
+    return H >= 1 and W >= 1 and (W + 3) // 4 * 4 * 4 * 64 * 48 < (1 << 31)   # wt_fused_supported
+
+
+def _family_noise_eligible(scaling_function, bilateral, noise_per_frame):
+    """no bilateral filtering, a built-in family with its own taps, scalar noise levels"""
     if bilateral is not None:
         return False
     if _needs_generic(scaling_function):
@@ -126,10 +137,28 @@ def _engine_eligible(frames, scaling_function, bilateral, noise_per_frame):
             return False
     except (ValueError, NotImplementedError):
         return False
-    if noise_per_frame is None or any(n is not None and np.ndim(n) != 0 for n in noise_per_frame):
+    return noise_per_frame is not None and not any(n is not None and np.ndim(n) != 0 for n in noise_per_frame)
+
+
+def batch64_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=()):
+    """True when the float64 batch (wt_batch64) computes this stack (host logic): an (N, H, W) ndarray the
+    reference computes in float64 (wavelets._result_dtype: native float64, or a type of wavelets._RECAST that the
+    device widens - int16 / uint16 / int32 / uint32 / int64, '>f4', '>f8'), no bilateral filtering, a built-in
+    scaling function with its own taps, scalar noise levels, and frames whose float64 schedule of `level` scales
+    is all fused passes (images, H >= 2, rows the fused passes take at 8 bytes per pixel: _lib.batch64_fused_ok,
+    i.e. what wt64_plan_fused_ok answers for one frame).  Everything else keeps its route."""
+    if not isinstance(frames, np.ndarray) or frames.ndim != 3:
         return False
-    H, W = frames.shape[1:]
-    return H >= 1 and W >= 1 and (W + 3) // 4 * 4 * 4 * 64 * 48 < (1 << 31)   # wt_fused_supported
+    if _result_dtype(frames) != np.float64:
+        return False
+    if frames.dtype != np.dtype(np.float64) and not _lib.device_widens(frames.dtype):
+        return False
+    if not _family_noise_eligible(scaling_function, bilateral, noise_per_frame):
+        return False
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+        return False
+    N, H, W = frames.shape
+    return N >= 1 and _lib.batch64_fused_ok(_family_of(scaling_function(2)), H, W, int(level))
 
 
 def _chunks(frames, level):
@@ -137,10 +166,32 @@ def _chunks(frames, level):
     return _lib.batch_chunks(N, H, W, level)
 
 
+def _f64_target(out, shape):
+    """(array the float64 batch downloads into, the caller's `out` to fill afterwards or None): a C-contiguous
+    float64 `out` of the result's shape receives the downloads directly; any other `out` gets the result as the
+    per-frame route hands it over (out[...] = res)"""
+    if out is None:
+        return _lib.host_empty(shape, dtype=np.float64), None       # page-locked: the downloads land at PCIe rate
+    if isinstance(out, np.ndarray) and out.shape == shape and out.dtype == np.float64 and out.flags.c_contiguous \
+            and out.flags.writeable:
+        return out, None
+    oshape = tuple(np.shape(out))
+    try:
+        fits = np.broadcast_shapes(oshape, shape) == oshape
+    except ValueError:
+        fits = False
+    if not fits:                                                    # (checked before any device work)
+        raise ValueError(f"out: an array of shape {shape} expected (got {oshape})")
+    return _lib.host_empty(shape, dtype=np.float64), out
+
+
 def transform_stack(frames, level, scaling_function=B3spline, out=None, bilateral=None, bilateral_scaling=False):
-    """(N, level+1, H, W) float32: the standard transform of every frame (AtrousTransform(scaling_function,
-    bilateral, bilateral_scaling)(frame, level).data, ref:307-328), batched."""
+    """(N, level+1, H, W) float32 (float64 for the stacks the reference computes in float64): the standard
+    transform of every frame (AtrousTransform(scaling_function, bilateral, bilateral_scaling)(frame, level).data,
+    ref:307-328), batched."""
     fr = _as_frames(frames)
+    if batch64_eligible(fr, level, scaling_function, bilateral):
+        return _transform_stack64(fr, level, scaling_function, out)
     bil = bilateral_eligible(fr, level, scaling_function, bilateral)
     if not bil and not batch_eligible(fr, level, scaling_function, bilateral):
         res = np.stack([AtrousTransform(scaling_function, bilateral, bilateral_scaling)(f, level).data for f in fr])
@@ -174,6 +225,28 @@ def transform_stack(frames, level, scaling_function=B3spline, out=None, bilatera
     return out
 
 
+def _transform_stack64(fr, level, scaling_function, out):
+    """transform_stack on the float64 batch (batch64_eligible): per frame, AtrousTransform._call_f64's fused passes"""
+    N, H, W = fr.shape
+    res, fill = _f64_target(out, (N, level + 1, H, W))
+    ctx = _lib.default_context()
+    fam = _family_of(scaling_function(2))
+    chunks = _lib.batch_chunks(N, H, W, level, itemsize=8)
+    bp = _lib.acquire_batch64(ctx, max(nf for _, nf in chunks), H, W, fam, level)
+    try:
+        for f0, nf in chunks:
+            bp.upload(PLANE_INPUT, fr[f0:f0 + nf])               # (integer / big-endian frames: widened on the device)
+            bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
+            for s in range(level + 1):
+                bp.download(s, nf, out=res[f0:f0 + nf, s])
+    finally:
+        _lib.release_batch64(bp)
+    if fill is not None:
+        fill[...] = res
+        return fill
+    return res
+
+
 def _taus_of(entries, noise, sigma_e, soft):
     """one frame's threshold row over `entries` (Coefficients._tau, scalar noise): 0.0 = significance one"""
     row = []
@@ -185,12 +258,27 @@ def _taus_of(entries, noise, sigma_e, soft):
 
 def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_threshold=True, anscombe=False,
                   out=None, bilateral=None):
-    """(N, H, W): utils.denoise of every frame (ref utils.py:83-102), batched.  `noise`: None (each frame's
-    own MAD estimate), a scalar, or one entry per frame."""
+    """(N, H, W): utils.denoise of every frame (ref utils.py:83-102), batched - float32, or float64 for the stacks
+    the reference computes in float64.  `noise`: None (each frame's own MAD estimate), a scalar, or one entry per
+    frame."""
     fr = _as_frames(frames)
     N = len(fr)
     nl = _noise_list(noise, N)
     level = len(weights)
+    if batch64_eligible(fr, level, scaling_function, bilateral, nl):
+        _, H, W = fr.shape
+        res, fill = _f64_target(out, (N, H, W))
+        fam = _family_of(scaling_function(2))
+        chunks = _lib.batch_chunks(N, H, W, level, itemsize=8)
+        bp = _lib.acquire_batch64(_lib.default_context(), max(nf for _, nf in chunks), H, W, fam, level)
+        try:
+            _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe, None, res)
+        finally:
+            _lib.release_batch64(bp)
+        if fill is not None:
+            fill[...] = res
+            return fill
+        return res
     bil = bilateral_eligible(fr, level, scaling_function, bilateral, nl)
     if not bil and not batch_eligible(fr, level, scaling_function, bilateral, nl):
         per = nl if nl is not None else [noise] * N
@@ -208,6 +296,23 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
     if N == 0:
         return out
     ctx = _lib.default_context()
+    fam = _family_of(scaling_function(2))
+    chunks = _chunks(fr, level)
+    bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, fam, level)
+    try:
+        _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe, bilateral if bil else None,
+                        out)
+    finally:
+        _lib.release_batch(bp)
+    return out
+
+
+def _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe, bilateral, out):
+    """denoise_stack's device part on a BatchPlan (float32) or a BatchPlan64 (float64): every chunk of frames
+    through the per-frame sequence of utils.denoise (wavelets._decompose_denoise_sum), results into `out`.
+    `bilateral`: the batched bilateral transform's parameter (float32 batches), else None."""
+    bil = bilateral is not None
+    level = len(weights)
     sf = scaling_function(2)
     sigma_e = sf.sigma_e(bilateral=bilateral)
     fam = _family_of(sf)
@@ -216,47 +321,41 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
     # (bilateral: no fused schedule - the whole transform, then the thresholds, wavelets._decompose_denoise_sum)
     sched = [] if bil else _lib.schedule(fam, level, True)
     entries, k, covered = _interleave_split(sched, level, sigma, wgts)
-    chunks = _chunks(fr, level)
-    bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, fam, level)
-    try:
-        for f0, nf in chunks:
-            noises = list(nl[f0:f0 + nf])
-            bp.upload(PLANE_INPUT, fr[f0:f0 + nf])
-            if anscombe:
-                bp.anscombe(nf, PLANE_INPUT, PLANE_INPUT)                        # ref:93-94
-            whole = k == 0 or k == len(sched)
-            if whole:                    # transform, then Coefficients._denoise_sum over every plane
-                if bil:
-                    sb = _sigma_bilateral_list(bilateral, level)
-                    bp.decompose_bilateral(nf, PLANE_INPUT, level, sb, False)
-                else:
-                    bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
-                used = entries
-            else:                        # the passes before the threshold step (wavelets._decompose_denoise_sum)
-                cur = PLANE_INPUT
-                for i in range(k):
-                    nxt = PLANE_SCRATCH(i & 1)
-                    bp.decompose_pass(nf, cur, nxt, sched[i][0], sched[i][1], FLAG_FUSED)
-                    cur = nxt
-                used = entries[:covered]
-            if any(n is None for n in noises) and any(sig != 0 for _, sig, _ in used):
-                med = bp.abs_median(nf, 0)                                        # ref:131-132 (lazy)
-                noises = [_noise_from_median(m, sigma_e) if n is None else n for n, m in zip(noises, med)]
-            taus = [_taus_of(used, n, sigma_e, soft_threshold) for n in noises]
-            bp.denoise_sum(nf, level + 1 if whole else covered, taus, [w for _, _, w in used], soft_threshold)
-            if not whole:
-                for i in range(k, len(sched)):
-                    last = i == len(sched) - 1
-                    nxt = level if last else PLANE_SCRATCH(i & 1)
-                    bp.decompose_pass_sum(nf, cur, nxt, sched[i][0], sched[i][1], FLAG_FUSED, PLANE_OUT,
-                                          first=False, last=last)
-                    cur = nxt
-            if anscombe:
-                bp.anscombe(nf, PLANE_OUT, PLANE_OUT, inverse=True)              # ref:99-100
-            bp.download(PLANE_OUT, nf, out=out[f0:f0 + nf])
-    finally:
-        _lib.release_batch(bp)
-    return out
+    for f0, nf in chunks:
+        noises = list(nl[f0:f0 + nf])
+        bp.upload(PLANE_INPUT, fr[f0:f0 + nf])
+        if anscombe:
+            bp.anscombe(nf, PLANE_INPUT, PLANE_INPUT)                        # ref:93-94
+        whole = k == 0 or k == len(sched)
+        if whole:                    # transform, then Coefficients._denoise_sum over every plane
+            if bil:
+                sb = _sigma_bilateral_list(bilateral, level)
+                bp.decompose_bilateral(nf, PLANE_INPUT, level, sb, False)
+            else:
+                bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
+            used = entries
+        else:                        # the passes before the threshold step (wavelets._decompose_denoise_sum)
+            cur = PLANE_INPUT
+            for i in range(k):
+                nxt = PLANE_SCRATCH(i & 1)
+                bp.decompose_pass(nf, cur, nxt, sched[i][0], sched[i][1], FLAG_FUSED)
+                cur = nxt
+            used = entries[:covered]
+        if any(n is None for n in noises) and any(sig != 0 for _, sig, _ in used):
+            med = bp.abs_median(nf, 0)                                        # ref:131-132 (lazy)
+            noises = [_noise_from_median(m, sigma_e) if n is None else n for n, m in zip(noises, med)]
+        taus = [_taus_of(used, n, sigma_e, soft_threshold) for n in noises]
+        bp.denoise_sum(nf, level + 1 if whole else covered, taus, [w for _, _, w in used], soft_threshold)
+        if not whole:
+            for i in range(k, len(sched)):
+                last = i == len(sched) - 1
+                nxt = level if last else PLANE_SCRATCH(i & 1)
+                bp.decompose_pass_sum(nf, cur, nxt, sched[i][0], sched[i][1], FLAG_FUSED, PLANE_OUT,
+                                      first=False, last=last)
+                cur = nxt
+        if anscombe:
+            bp.anscombe(nf, PLANE_OUT, PLANE_OUT, inverse=True)              # ref:99-100
+        bp.download(PLANE_OUT, nf, out=out[f0:f0 + nf])
 
 
 def _wow_taus(bp, nf, sigma, scale, noises, sigma_e, soft):

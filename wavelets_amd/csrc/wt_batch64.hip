@@ -1,0 +1,643 @@
+// Batched float64 engine (wt_batch64): the float64 counterpart of wt_batch (wt_batch.hip) for stacks the reference
+// computes in float64 - native float64 frames, and the integer / big-endian frames it recasts to float64
+// (watroo/wavelets.py:297, 319-320).  N frames of the same H x W go through each fused pass in ONE launch, the frame
+// index a grid dimension (wt_fused_batch_kernel<double, ...>, the units fused_f64_k*_batch_acc*).
+//
+// Layout: every plane is one allocation of N frames back to back, frame f at f * H * P doubles (P = the pitch of a
+// wt_plan64 of the same width, even).  A plane is therefore also ONE tall image of N * H rows: transfers, the
+// widening of integer frames, Anscombe and the thresholds + plane sum run once over the whole stack.  Only the fused
+// passes see frames: each frame is its own image there, with the per-frame float64 schedule, kernel choice and
+// geometry (the batch's wt_plan64 `geo` is the one a wt_plan64 of that shape has), so a frame's bits are those of
+// the per-frame call.
+// The MAD median is a per-frame radix select over the 63 magnitude bits of a double (six histogram levels of
+// 11 / 11 / 11 / 11 / 11 / 8 bits, the levels of wt64_abs_median), two ranks per frame for an even pixel count:
+// N exact medians for one host round trip.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "wt_host.h"
+#include "wt_fused_decl.h"
+#include "wt_math64.h"
+#include "wt_unit_probe.h"
+
+WT_UNIT_PROBE_DEFINE
+
+struct WtBatch64Sel {               // select state of one rank of one frame
+    unsigned long long k;           // rank still to find among the keys matching `prefix`
+    unsigned long long prefix;      // key bits fixed so far
+    uint32_t failed, pad;           // failed: the rank lies beyond the frame's keys (never, with every key counted)
+};
+
+struct wt_batch64 {
+    wt_ctx *ctx = nullptr;
+    wt_plan64 geo;                  // ONE frame's geometry, context and taps: what the fused launches read (no planes)
+    int family = WT_B3SPLINE;
+    int n = 0, max_level = 0;
+    int64_t fstride = 0;            // doubles from one frame to the next (H * P)
+    std::vector<double *> coef;     // planes 0 .. max_level
+    double *input = nullptr, *out = nullptr, *scr[2] = {nullptr, nullptr};
+    void *istage = nullptr;         // frames of another element type on their way into a plane
+    size_t istage_cap = 0;
+    uint32_t *d_hist = nullptr;     // [n][2 ranks][WT_HIST_BINS] (allocated by the first median)
+    WtBatch64Sel *d_sel = nullptr;  // [n][2 ranks]
+    WtBatch64Sel *h_sel = nullptr;  // pinned copy
+    double *d_tau = nullptr;        // [n][2 * WT_MAX_SUM_PLANES]: the thresholds of wt_batch64_denoise_sum, then 1 / tau
+    double *h_tau = nullptr;        // pinned staging of the table
+};
+
+// ------------------------------------------------------------------------------------------------ kernels
+// One radix level of the per-frame select: bins of (key >> shift) & bmask over the keys of frame blockIdx.y that
+// match a rank's prefix (key = the magnitude bits of a double: their order is the order of |x|; NaN keys order
+// above infinity and are counted, as wt64_hist_kernel counts them).
+__global__ __launch_bounds__(256) void wt_batch64_hist_kernel(const double *p, int H, int P, int W, int64_t fstride, unsigned long long mask,
+                                                              int shift, uint32_t bmask, const WtBatch64Sel *st, uint32_t *hist)
+{
+    __shared__ uint32_t lh[2][WT_HIST_BINS];
+    const int f = blockIdx.y;
+    for (int i = threadIdx.x; i < 2 * WT_HIST_BINS; i += 256) lh[i / WT_HIST_BINS][i % WT_HIST_BINS] = 0;
+    __syncthreads();
+    const unsigned long long pre0 = st[2 * f].prefix & mask, pre1 = st[2 * f + 1].prefix & mask;
+    const double *fp = p + (int64_t)f * fstride;
+    const int X2 = (W + 1) / 2;                          // double2 groups per row (P even: 16-byte aligned rows)
+    const int64_t items = (int64_t)H * X2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (int64_t)gridDim.x * 256) {
+        const int row = (int)(i / X2), c2 = (int)(i % X2);
+        const double2 v = *reinterpret_cast<const double2 *>(fp + (int64_t)row * P + 2 * c2);
+        const double e[2] = {v.x, v.y};
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (2 * c2 + j >= W) continue;
+            const unsigned long long key = (unsigned long long)__double_as_longlong(e[j]) & 0x7fffffffffffffffull;
+            const uint32_t bin = (uint32_t)(key >> shift) & bmask;
+            if ((key & mask) == pre0) atomicAdd(&lh[0][bin], 1u);
+            if ((key & mask) == pre1) atomicAdd(&lh[1][bin], 1u);
+        }
+    }
+    __syncthreads();
+    uint32_t *gh = hist + (int64_t)f * 2 * WT_HIST_BINS;
+    for (int i = threadIdx.x; i < 2 * WT_HIST_BINS; i += 256) {
+        const uint32_t c = lh[i / WT_HIST_BINS][i % WT_HIST_BINS];
+        if (c) atomicAdd(&gh[i], c);
+    }
+}
+
+// The bin of one rank (block = frame * 2 + rank): fixes bmask's bits of the prefix, leaves the bins cleared.
+__global__ __launch_bounds__(256) void wt_batch64_select_kernel(uint32_t *hist, WtBatch64Sel *st, int nbins, int shift)
+{
+    __shared__ unsigned long long part[256];
+    __shared__ int sel_t;
+    __shared__ unsigned long long sel_before;
+    uint32_t *h = hist + (int64_t)blockIdx.x * WT_HIST_BINS;
+    const int per = nbins / 256;
+    unsigned long long s = 0;
+    for (int i = 0; i < per; ++i) s += h[threadIdx.x * per + i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    WtBatch64Sel &S = st[blockIdx.x];
+    if (threadIdx.x == 0) {
+        unsigned long long cum = 0;
+        int t = -1;
+        for (int i = 0; i < 256; ++i) {
+            if (cum + part[i] > S.k) { t = i; break; }
+            cum += part[i];
+        }
+        if (t < 0) S.failed = 1;
+        sel_t = t;
+        sel_before = cum;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x == sel_t) {
+        unsigned long long cum = sel_before;
+        int b = threadIdx.x * per + per - 1;
+        for (int i = 0; i < per; ++i) {
+            const uint32_t c = h[threadIdx.x * per + i];
+            if (cum + c > S.k) { b = threadIdx.x * per + i; break; }
+            cum += c;
+        }
+        S.prefix |= (unsigned long long)b << shift;
+        S.k -= cum;
+    }
+    __syncthreads();
+    for (int i = 0; i < per; ++i) h[threadIdx.x * per + i] = 0;
+}
+
+// wt64_denoise_sum_kernel (wt_kernels_f64.h) with one threshold row per frame: tab[frame * 2 * n_den + k] = tau,
+// tab[frame * 2 * n_den + n_den + k] = 1 / tau (the host's IEEE division, as wt64_denoise_sum), the frame from the
+// flat index.  Same expressions and accesses (no noise plane): the bits of the per-frame call.
+struct Batch64DenoiseArgs {
+    double *p[WT_MAX_SUM_PLANES];
+    double wgt[WT_MAX_SUM_PLANES];
+    int n, n_den, soft, write_back;
+};
+typedef double wt_b64_ntd2 __attribute__((ext_vector_type(2)));
+__global__ __launch_bounds__(256) void wt_batch64_denoise_sum_kernel(Batch64DenoiseArgs a, const double *tab, double *dst, int64_t n2, int64_t f2)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (int64_t)gridDim.x * 256) {
+        const double *ft = tab + (i / f2) * 2 * a.n_den;
+        double2 acc = make_double2(0.0, 0.0);
+        for (int k = 0; k < a.n; ++k) {
+            const wt_b64_ntd2 raw = __builtin_nontemporal_load(reinterpret_cast<const wt_b64_ntd2 *>(a.p[k]) + i);   // (read exactly once)
+            double2 v = make_double2(raw.x, raw.y);
+            if (k < a.n_den) {
+                const double tau = ft[k], inv_tau = ft[a.n_den + k];
+                double2 sg = make_double2(1.0, 1.0);
+                if (tau > 0.0) sg = make_double2(wt_sig64_inv(v.x, tau, inv_tau, a.soft), wt_sig64_inv(v.y, tau, inv_tau, a.soft));
+                v = make_double2(v.x * (a.wgt[k] * sg.x), v.y * (a.wgt[k] * sg.y));
+                if (a.write_back) reinterpret_cast<double2 *>(a.p[k])[i] = v;
+            }
+            acc = k == 0 ? v : make_double2(acc.x + v.x, acc.y + v.y);
+        }
+        __builtin_nontemporal_store((wt_b64_ntd2){acc.x, acc.y}, reinterpret_cast<wt_b64_ntd2 *>(dst) + i);
+    }
+}
+
+// generalized_anscombe (watroo/wavelets.py:14-21) over the frames as one tall image: wt64_anscombe_kernel's expressions
+__global__ __launch_bounds__(256) void wt_batch64_anscombe_kernel(const double *src, double *dst, int W, int P, int nrows, double alpha, double g,
+                                                                  double sigma, int inverse)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= W) return;
+    for (int y = blockIdx.y; y < nrows; y += gridDim.y) {
+        const int64_t o = (int64_t)y * P + x;
+        const double v = src[o];
+        double r;
+        if (inverse) {
+            const double h = alpha * v / 2.0;
+            r = (h * h + alpha * g - sigma * sigma - 3.0 * alpha / 8.0) / alpha;
+        } else {
+            double dum = alpha * v + 3.0 * alpha * alpha / 8.0 + sigma * sigma - alpha * g;
+            if (dum <= 0.0) dum = 0.0;
+            r = 2.0 * sqrt(dum) / alpha;
+        }
+        dst[o] = r;
+    }
+}
+
+// frames of another element type -> double planes (wt64_upload_int's widening: one element per thread from the
+// tightly packed staging copy, SWAP = the other byte order); the frames are one tall image of nrows = nf * H rows
+template <int N> struct WtB64Uint;
+template <> struct WtB64Uint<1> { typedef uint8_t T; };
+template <> struct WtB64Uint<2> { typedef uint16_t T; };
+template <> struct WtB64Uint<4> { typedef uint32_t T; };
+template <> struct WtB64Uint<8> { typedef uint64_t T; };
+__device__ __forceinline__ uint8_t wt_b64_bswap(uint8_t v) { return v; }
+__device__ __forceinline__ uint16_t wt_b64_bswap(uint16_t v) { return __builtin_bswap16(v); }
+__device__ __forceinline__ uint32_t wt_b64_bswap(uint32_t v) { return __builtin_bswap32(v); }
+__device__ __forceinline__ uint64_t wt_b64_bswap(uint64_t v) { return __builtin_bswap64(v); }
+template <typename I, bool SWAP>
+__global__ __launch_bounds__(256) void wt_batch64_widen_kernel(const I *src, double *dst, int W, int P, int nrows)
+{
+    typedef typename WtB64Uint<sizeof(I)>::T U;
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= W) return;
+    for (int y = blockIdx.y; y < nrows; y += gridDim.y) {
+        U raw = reinterpret_cast<const U *>(src)[(int64_t)y * W + x];
+        if (SWAP) raw = wt_b64_bswap(raw);
+        dst[(int64_t)y * P + x] = (double)__builtin_bit_cast(I, raw);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+static int b64plane(wt_batch64 *b, int id, double **out)
+{
+    double **slot = nullptr;
+    if (id >= 0 && id <= b->max_level) slot = &b->coef[id];
+    else if (id == WT_PLANE_INPUT) slot = &b->input;
+    else if (id == WT_PLANE_OUT) slot = &b->out;
+    else if (id == WT_PLANE_SCRATCH(0)) slot = &b->scr[0];
+    else if (id == WT_PLANE_SCRATCH(1)) slot = &b->scr[1];
+    if (!slot) WT_FAIL("wt_batch64: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1)", id, b->max_level);
+    if (!*slot) WT_HIP(hipMalloc((void **)slot, (size_t)b->n * (size_t)b->fstride * sizeof(double)));
+    *out = *slot;
+    return 0;
+}
+
+static int check_frames64(const wt_batch64 *b, int nf, const char *who)
+{
+    if (!b) WT_FAIL("%s: null batch", who);
+    if (nf < 1 || nf > b->n) WT_FAIL("%s: %d active frames (batch of %d)", who, nf, b->n);
+    return 0;
+}
+
+// fused64_ok (wt_f64.h) for one frame of this shape: an image (H >= 2) whose rows the fused passes take at 8 bytes
+// per pixel and whose float64 schedule of `level` scales is fused passes only
+static bool batch64_all_fused(int family, int64_t H, int64_t W, int level, int32_t *tr, int *np)
+{
+    if ((family != WT_B3SPLINE && family != WT_TRIANGLE) || H < 2 || W < 1 || level < 1) return false;
+    if (!wt_fused_supported_bytes((W + 1) / 2 * 2 * 8)) return false;
+    if (wt_schedule(family, level, 1, tr, 32, np)) return false;
+    for (int i = 0; i < *np; ++i)
+        if (!wt_fused_has_pass(tr[3 * i], tr[3 * i + 1], family)) return false;
+    return true;
+}
+
+extern "C" int wt_batch64_fused_ok(int family, int64_t H, int64_t W, int level, int *ok)
+{
+    if (!ok) WT_FAIL("wt_batch64_fused_ok: null pointer");
+    int32_t tr[3 * 32];
+    int np = 0;
+    *ok = batch64_all_fused(family, H, W, level, tr, &np) ? 1 : 0;
+    return 0;
+}
+
+static int batch64_pass(wt_batch64 *b, int nf, int cur, int nxt, int s0, int ns, int acc, int sum_plane, bool first)
+{
+    if (ns < 1 || ns > WT_FUSED_MAX_SCALES || s0 < 0 || s0 + ns - 1 > b->max_level)
+        WT_FAIL("wt_batch64_decompose_pass: scales [%d,%d) outside the batch (max_level %d)", s0, s0 + ns, b->max_level);
+    if (cur == nxt || (cur >= s0 && cur < s0 + ns) || (nxt >= s0 && nxt < s0 + ns))
+        WT_FAIL("wt_batch64_decompose_pass: input/output planes alias the detail planes of the pass");
+    if (!wt_fused_has_pass(s0, ns, b->family)) WT_FAIL("wt_batch64_decompose_pass: no fused kernel for first scale %d x %d scales", s0, ns);
+    if (acc && first != (s0 == 0))
+        WT_FAIL("wt_batch64_decompose_pass_sum: first must be set for the pass that starts at scale 0 and only for it (got first=%d, s0=%d)", (int)first, s0);
+    // (the arguments of fused64_pass, wt_f64.h)
+    FusedArgsT<double> a{};
+    double *in = nullptr;
+    WT_TRY(b64plane(b, cur, &in));
+    a.in = in;
+    WT_TRY(b64plane(b, nxt, &a.out_c));
+    for (int k = 0; k < ns && k < 3; ++k) WT_TRY(b64plane(b, s0 + k, &a.out_w[k]));
+    if (ns > 3) WT_TRY(b64plane(b, s0 + 3, &a.out_w3));
+    a.g = b->geo.g;
+    if (acc) {
+        if (sum_plane == cur || sum_plane == nxt || (sum_plane >= s0 && sum_plane < s0 + ns))
+            WT_FAIL("wt_batch64_decompose_pass_sum: the sum plane aliases a plane of the pass");
+        WT_TRY(b64plane(b, sum_plane, &a.p_out));
+        a.p_in = first ? nullptr : a.p_out;
+    }
+    FusedRows rows;
+    rows.frames = nf;
+    rows.fstride = b->fstride;
+    const bool b3 = b->family == WT_B3SPLINE;
+    if (acc == 2) return b3 ? wt_fused_tu_f64_k5_batch_acc2(&b->geo, a, s0, ns, rows) : wt_fused_tu_f64_k3_batch_acc2(&b->geo, a, s0, ns, rows);
+    if (acc == 1) return b3 ? wt_fused_tu_f64_k5_batch_acc1(&b->geo, a, s0, ns, rows) : wt_fused_tu_f64_k3_batch_acc1(&b->geo, a, s0, ns, rows);
+    return b3 ? wt_fused_tu_f64_k5_batch_acc0(&b->geo, a, s0, ns, rows) : wt_fused_tu_f64_k3_batch_acc0(&b->geo, a, s0, ns, rows);
+}
+
+static int batch64_schedule_run(wt_batch64 *b, int nf, int src, int level, bool with_sum, int dst, const char *who)
+{
+    if (level < 1 || level > b->max_level) WT_FAIL("%s: level %d outside [1, %d]", who, level, b->max_level);
+    if (src >= 0 && src <= level) WT_FAIL("%s: src plane %d is one of the output planes", who, src);
+    if (src == WT_PLANE_SCRATCH(0) || src == WT_PLANE_SCRATCH(1)) WT_FAIL("%s: scratch planes 0/1 are used internally", who);
+    if (with_sum && ((dst >= 0 && dst <= level) || dst == src || dst == WT_PLANE_SCRATCH(0) || dst == WT_PLANE_SCRATCH(1)))
+        WT_FAIL("%s: dst plane %d is an input / output / internal plane of the transform", who, dst);
+    int32_t tr[3 * 32];
+    int np = 0;
+    if (!batch64_all_fused(b->family, b->geo.g.H, b->geo.g.W, level, tr, &np))
+        WT_FAIL("%s: %d scales have no all-fused float64 schedule for %d x %d frames (wt64_plan_fused_ok): not a batch case", who, level,
+                b->geo.g.H, b->geo.g.W);
+    int cur = src;
+    for (int i = 0; i < np; ++i) {
+        const int s0 = tr[3 * i], ns = tr[3 * i + 1];
+        const bool last = s0 + ns == level;
+        const int nxt = last ? level : WT_PLANE_SCRATCH(i & 1);
+        WT_TRY(batch64_pass(b, nf, cur, nxt, s0, ns, with_sum ? (last ? 2 : 1) : 0, dst, i == 0));
+        cur = nxt;
+    }
+    return 0;
+}
+
+static void batch64_free(wt_batch64 *b, int *bad)
+{
+    auto f = [&](void *q) { if (q && hipFree(q) != hipSuccess) *bad = 1; };
+    for (double *q : b->coef) f(q);
+    f(b->input);
+    f(b->out);
+    f(b->scr[0]);
+    f(b->scr[1]);
+    f(b->istage);
+    f(b->d_hist);
+    f(b->d_sel);
+    f(b->d_tau);
+    if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) *bad = 1;
+    if (b->h_tau && hipHostFree(b->h_tau) != hipSuccess) *bad = 1;
+}
+
+extern "C" int wt_batch64_create(wt_ctx *ctx, int n, int H, int W, int family, int max_level, wt_batch64 **out)
+{
+    WtGuard guard_(ctx);
+    if (!ctx || !out) WT_FAIL("wt_batch64_create: null pointer");
+    *out = nullptr;
+    if (n < 1 || n > 65535) WT_FAIL("wt_batch64_create: %d frames (1..65535 per batch)", n);
+    if (H < 1 || W < 1) WT_FAIL("wt_batch64_create: frame %d x %d", H, W);
+    if (family != WT_B3SPLINE && family != WT_TRIANGLE) WT_FAIL("wt_batch64_create: family %d (built-in families only)", family);
+    if (max_level < 0 || max_level > 30) WT_FAIL("wt_batch64_create: max_level %d", max_level);
+    if (H < 2) WT_FAIL("wt_batch64_create: frames of one row are signals for the float64 engine (no fused passes)");
+    if (!wt_fused_supported_bytes((int64_t)(W + 1) / 2 * 2 * 8)) WT_FAIL("wt_batch64_create: rows of %d pixels are too wide for the fused float64 passes", W);
+    wt_batch64 *b = new wt_batch64;
+    b->ctx = ctx;
+    b->family = family;
+    b->n = n;
+    b->max_level = max_level;
+    // the geometry and taps a wt_plan64 of this shape has (wt64_plan_create)
+    static const double b3[5] = {1. / 16, 1. / 4, 3. / 8, 1. / 4, 1. / 16}, tri[3] = {1. / 4, 1. / 2, 1. / 4};
+    b->geo.ctx = ctx;
+    b->geo.g = Geo{W, (W + 1) / 2 * 2, H, 0, H, 0, 0};
+    b->geo.max_level = max_level;
+    b->geo.ntaps = family == WT_B3SPLINE ? 5 : 3;
+    for (int i = 0; i < b->geo.ntaps; ++i) b->geo.taps[i] = family == WT_B3SPLINE ? b3[i] : tri[i];
+    b->fstride = (int64_t)H * b->geo.g.P;
+    b->coef.assign(max_level + 1, nullptr);
+    hipError_t e = hipMalloc((void **)&b->d_sel, (size_t)n * 2 * sizeof(WtBatch64Sel));
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_tau, (size_t)n * 2 * WT_MAX_SUM_PLANES * sizeof(double));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_sel, (size_t)n * 2 * sizeof(WtBatch64Sel), 0);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_tau, (size_t)n * 2 * WT_MAX_SUM_PLANES * sizeof(double), 0);
+    if (e != hipSuccess) {
+        int bad = 0;
+        batch64_free(b, &bad);
+        delete b;
+        wt_set_error("wt_batch64_create: HIP error %d (%s)", (int)e, hipGetErrorString(e));
+        return 2;
+    }
+    *out = b;
+    return 0;
+}
+
+extern "C" int wt_batch64_destroy(wt_batch64 *b)
+{
+    if (!b) return 0;
+    WtGuard guard_(b->ctx);
+    (void)hipStreamSynchronize(b->ctx->stream);
+    int bad = 0;
+    batch64_free(b, &bad);
+    delete b;
+    if (bad) WT_FAIL("wt_batch64_destroy: a device buffer could not be released");
+    return 0;
+}
+
+extern "C" int wt_batch64_info(wt_batch64 *b, int64_t *info)
+{
+    if (!b || !info) WT_FAIL("wt_batch64_info: null pointer");
+    const Geo &g = b->geo.g;
+    const int64_t v[7] = {b->n, g.H, g.W, g.P, b->fstride, b->max_level, b->family};
+    memcpy(info, v, sizeof v);
+    return 0;
+}
+
+extern "C" int wt_batch64_plane_ptr(wt_batch64 *b, int plane, void **ptr, int64_t *frame_stride)
+{
+    if (!b || !ptr || !frame_stride) WT_FAIL("wt_batch64_plane_ptr: null pointer");
+    WtGuard guard_(b->ctx);
+    double *q = nullptr;
+    WT_TRY(b64plane(b, plane, &q));
+    *ptr = q;
+    *frame_stride = b->fstride;
+    return 0;
+}
+
+static int check_range64(const wt_batch64 *b, int f0, int nf, const char *who)
+{
+    if (f0 < 0 || nf < 1 || f0 + nf > b->n) WT_FAIL("%s: frames [%d, %d) outside the batch of %d", who, f0, f0 + nf, b->n);
+    return 0;
+}
+
+// frames [f0, f0 + nf) of a plane <-> host frames `hstride` doubles apart (rows of W doubles back to back within a frame)
+static int batch64_copy(wt_batch64 *b, int plane, int f0, int nf, double *host, int64_t hstride, bool up, const char *who)
+{
+    if (!b || !host) WT_FAIL("%s: null pointer", who);
+    WT_TRY(check_range64(b, f0, nf, who));
+    const Geo &g = b->geo.g;
+    const int64_t fpx = (int64_t)g.H * g.W;
+    if (hstride == 0) hstride = fpx;
+    if (hstride < fpx) WT_FAIL("%s: host frame stride %lld below the %lld pixels of a frame", who, (long long)hstride, (long long)fpx);
+    WtGuard guard_(b->ctx);
+    WT_TRY(wt_side_join(b->ctx));
+    double *q = nullptr;
+    WT_TRY(b64plane(b, plane, &q));
+    double *dev = q + (int64_t)f0 * b->fstride;
+    const size_t span = ((size_t)(nf - 1) * (size_t)hstride + (size_t)fpx) * 8;
+    const bool pinned = try_pin(host, span);     // (no-op for page-locked blocks: _lib.host_empty)
+    hipError_t e = hipSuccess;
+    // contiguous frames are one tall image of nf * H rows; else one 2-D copy per frame
+    const int pieces = hstride == fpx ? 1 : nf;
+    const size_t rows = (size_t)g.H * (size_t)(hstride == fpx ? nf : 1);
+    for (int i = 0; i < pieces && e == hipSuccess; ++i) {
+        double *d = dev + (int64_t)i * b->fstride, *h = host + (int64_t)i * hstride;
+        e = up ? hipMemcpy2DAsync(d, (size_t)g.P * 8, h, (size_t)g.W * 8, (size_t)g.W * 8, rows, hipMemcpyHostToDevice, b->ctx->stream)
+               : hipMemcpy2DAsync(h, (size_t)g.W * 8, d, (size_t)g.P * 8, (size_t)g.W * 8, rows, hipMemcpyDeviceToHost, b->ctx->stream);
+    }
+    hipError_t e2 = hipStreamSynchronize(b->ctx->stream);
+    if (e == hipSuccess) e = e2;
+    if (pinned) (void)hipHostUnregister(host);
+    WT_HIP(e);
+    return 0;
+}
+
+extern "C" int wt_batch64_upload(wt_batch64 *b, int plane, int f0, int nf, const double *host, int64_t host_frame_stride)
+{
+    return batch64_copy(b, plane, f0, nf, const_cast<double *>(host), host_frame_stride, true, "wt_batch64_upload");
+}
+
+extern "C" int wt_batch64_download(wt_batch64 *b, int plane, int f0, int nf, double *host, int64_t host_frame_stride)
+{
+    return batch64_copy(b, plane, f0, nf, host, host_frame_stride, false, "wt_batch64_download");
+}
+
+template <typename I>
+static void batch64_widen_launch(wt_batch64 *b, double *dst, int nrows, bool swap)
+{
+    const Geo &g = b->geo.g;
+    const dim3 grid((g.W + 255) / 256, (unsigned)std::min(nrows, 32768)), block(256);
+    if (swap) hipLaunchKernelGGL((wt_batch64_widen_kernel<I, true>), grid, block, 0, b->ctx->stream, (const I *)b->istage, dst, g.W, g.P, nrows);
+    else hipLaunchKernelGGL((wt_batch64_widen_kernel<I, false>), grid, block, 0, b->ctx->stream, (const I *)b->istage, dst, g.W, g.P, nrows);
+}
+
+// wt64_upload_int for frames [f0, f0 + nf): a C-contiguous (nf, H, W) block of elements of type `dtype` crosses PCIe
+// as it is and is widened (byte-swapped) into the plane by one kernel over the nf * H rows
+extern "C" int wt_batch64_upload_elems(wt_batch64 *b, int plane, int f0, int nf, const void *host, int dtype)
+{
+    if (!b || !host) WT_FAIL("wt_batch64_upload_elems: null pointer");
+    WT_TRY(check_range64(b, f0, nf, "wt_batch64_upload_elems"));
+    WtGuard guard_(b->ctx);
+    static const int isz[11] = {0, 1, 1, 2, 2, 4, 4, 8, 8, 4, 8};
+    const bool swap = (dtype & WT_BYTESWAPPED) != 0;
+    const int base = dtype & ~WT_BYTESWAPPED;
+    if (base < WT_INT8 || base > WT_FLOAT64) WT_FAIL("wt_batch64_upload_elems: unknown element type %d", dtype);
+    const Geo &g = b->geo.g;
+    const int64_t nrows64 = (int64_t)nf * g.H;
+    if (nrows64 > INT32_MAX) WT_FAIL("wt_batch64_upload_elems: %lld rows in one upload", (long long)nrows64);
+    const int nrows = (int)nrows64;
+    const size_t need = (size_t)nrows * (size_t)g.W * isz[base];
+    WT_TRY(wt_side_join(b->ctx));
+    double *q = nullptr;
+    WT_TRY(b64plane(b, plane, &q));
+    if (b->istage_cap < need) {
+        WT_HIP(hipStreamSynchronize(b->ctx->stream));
+        if (b->istage) (void)hipFree(b->istage);
+        b->istage = nullptr;
+        b->istage_cap = 0;
+        WT_HIP(hipMalloc(&b->istage, need));
+        b->istage_cap = need;
+    }
+    const bool pinned = try_pin(host, need);
+    hipError_t e = hipMemcpyAsync(b->istage, host, need, hipMemcpyHostToDevice, b->ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->ctx->stream);      // (the host frames are free again)
+    if (pinned) (void)hipHostUnregister(const_cast<void *>(host));
+    WT_HIP(e);
+    double *dst = q + (int64_t)f0 * b->fstride;
+    switch (base) {
+        case WT_INT8: batch64_widen_launch<int8_t>(b, dst, nrows, false); break;
+        case WT_UINT8: batch64_widen_launch<uint8_t>(b, dst, nrows, false); break;
+        case WT_INT16: batch64_widen_launch<int16_t>(b, dst, nrows, swap); break;
+        case WT_UINT16: batch64_widen_launch<uint16_t>(b, dst, nrows, swap); break;
+        case WT_INT32: batch64_widen_launch<int32_t>(b, dst, nrows, swap); break;
+        case WT_UINT32: batch64_widen_launch<uint32_t>(b, dst, nrows, swap); break;
+        case WT_INT64: batch64_widen_launch<int64_t>(b, dst, nrows, swap); break;
+        case WT_UINT64: batch64_widen_launch<uint64_t>(b, dst, nrows, swap); break;
+        case WT_FLOAT32: batch64_widen_launch<float>(b, dst, nrows, swap); break;
+        default: batch64_widen_launch<double>(b, dst, nrows, swap); break;
+    }
+    WT_HIP(hipGetLastError());
+    WT_HIP(hipStreamSynchronize(b->ctx->stream));          // (as wt64_upload_int: the staging copy is free again)
+    return 0;
+}
+
+extern "C" int wt_batch64_decompose(wt_batch64 *b, int nf, int src, int level, int flags)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_decompose"));
+    WtGuard guard_(b->ctx);
+    if (!(flags & 1)) WT_FAIL("wt_batch64_decompose: a batch runs the fused passes (flags bit0)");
+    if (level == 0) {
+        double *s = nullptr, *d = nullptr;
+        if (src == 0) WT_FAIL("wt_batch64_decompose: src plane 0 is the output plane");
+        WT_TRY(b64plane(b, src, &s));
+        WT_TRY(b64plane(b, 0, &d));
+        WT_HIP(hipMemcpyAsync(d, s, (size_t)nf * (size_t)b->fstride * 8, hipMemcpyDeviceToDevice, b->ctx->stream));
+        return 0;
+    }
+    return batch64_schedule_run(b, nf, src, level, false, WT_PLANE_NONE, "wt_batch64_decompose");
+}
+
+extern "C" int wt_batch64_decompose_sum(wt_batch64 *b, int nf, int src, int level, int dst, int flags)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_decompose_sum"));
+    WtGuard guard_(b->ctx);
+    if (!(flags & 1)) WT_FAIL("wt_batch64_decompose_sum: a batch runs the fused passes (flags bit0)");
+    return batch64_schedule_run(b, nf, src, level, true, dst, "wt_batch64_decompose_sum");
+}
+
+extern "C" int wt_batch64_decompose_pass(wt_batch64 *b, int nf, int cur, int nxt, int s0, int ns, int flags)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_decompose_pass"));
+    WtGuard guard_(b->ctx);
+    if (!(flags & 1)) WT_FAIL("wt_batch64_decompose_pass: a batch runs the fused passes (flags bit0)");
+    return batch64_pass(b, nf, cur, nxt, s0, ns, 0, WT_PLANE_NONE, false);
+}
+
+extern "C" int wt_batch64_decompose_pass_sum(wt_batch64 *b, int nf, int cur, int nxt, int s0, int ns, int flags, int sum_plane, int first,
+                                             int last)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_decompose_pass_sum"));
+    WtGuard guard_(b->ctx);
+    if (!(flags & 1)) WT_FAIL("wt_batch64_decompose_pass_sum: a batch runs the fused passes (flags bit0)");
+    return batch64_pass(b, nf, cur, nxt, s0, ns, last ? 2 : 1, sum_plane, first != 0);
+}
+
+extern "C" int wt_batch64_abs_median(wt_batch64 *b, int nf, int plane, double *medians)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_abs_median"));
+    if (!medians) WT_FAIL("wt_batch64_abs_median: null pointer");
+    WtGuard guard_(b->ctx);
+    wt_ctx *c = b->ctx;
+    double *q = nullptr;
+    WT_TRY(b64plane(b, plane, &q));
+    if (!b->d_hist) {
+        WT_HIP(hipMalloc((void **)&b->d_hist, (size_t)b->n * 2 * WT_HIST_BINS * sizeof(uint32_t)));
+        WT_HIP(hipMemsetAsync(b->d_hist, 0, (size_t)b->n * 2 * WT_HIST_BINS * sizeof(uint32_t), c->stream));
+    }
+    const Geo &g = b->geo.g;
+    const int64_t N = (int64_t)g.H * g.W;
+    const unsigned long long klo = (unsigned long long)((N - 1) / 2);
+    for (int f = 0; f < nf; ++f)
+        for (int r = 0; r < 2; ++r) b->h_sel[2 * f + r] = WtBatch64Sel{klo + ((N & 1) == 0 && r == 1 ? 1ull : 0ull), 0ull, 0u, 0u};
+    WT_HIP(hipMemcpyAsync(b->d_sel, b->h_sel, (size_t)nf * 2 * sizeof(WtBatch64Sel), hipMemcpyHostToDevice, c->stream));
+    const int64_t items = (int64_t)g.H * ((g.W + 1) / 2);
+    const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((items + 2047) / 2048, std::max(1, 8 * c->num_cus / nf)));
+    // the radix levels of wt64_abs_median: 11 bits five times, then the last 8 (63 magnitude bits)
+    const int shifts[6] = {52, 41, 30, 19, 8, 0};
+    const int bits[6] = {11, 11, 11, 11, 11, 8};
+    unsigned long long mask = 0;
+    for (int lv = 0; lv < 6; ++lv) {
+        const uint32_t bmask = (1u << bits[lv]) - 1u;
+        {
+            ProfScope ps(c, "wt_batch64_hist_kernel");
+            hipLaunchKernelGGL(wt_batch64_hist_kernel, dim3(bx, nf), dim3(256), 0, c->stream, (const double *)q, g.H, g.P, g.W, b->fstride, mask,
+                               shifts[lv], bmask, (const WtBatch64Sel *)b->d_sel, b->d_hist);
+        }
+        {
+            ProfScope ps(c, "wt_batch64_select_kernel");
+            hipLaunchKernelGGL(wt_batch64_select_kernel, dim3(2 * nf), dim3(256), 0, c->stream, b->d_hist, b->d_sel, (int)bmask + 1, shifts[lv]);
+        }
+        WT_HIP(hipGetLastError());
+        mask |= (unsigned long long)bmask << shifts[lv];
+    }
+    WT_HIP(hipMemcpyAsync(b->h_sel, b->d_sel, (size_t)nf * 2 * sizeof(WtBatch64Sel), hipMemcpyDeviceToHost, c->stream));
+    WT_HIP(hipStreamSynchronize(c->stream));               // the one host round trip for all nf medians
+    for (int f = 0; f < nf; ++f)
+        if (b->h_sel[2 * f].failed || b->h_sel[2 * f + 1].failed) WT_FAIL("wt_batch64_abs_median: rank %llu of frame %d not found", klo, f);
+    for (int f = 0; f < nf; ++f) {
+        double lo, hi;
+        memcpy(&lo, &b->h_sel[2 * f].prefix, 8);
+        memcpy(&hi, &b->h_sel[2 * f + 1].prefix, 8);
+        // np.median of float64: the mean of the two middle values of an even count (as wt64_abs_median)
+        medians[f] = (N & 1) ? lo : (lo + hi) / 2.0;
+    }
+    return 0;
+}
+
+extern "C" int wt_batch64_denoise_sum(wt_batch64 *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
+                                      int write_back)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_denoise_sum"));
+    WtGuard guard_(b->ctx);
+    if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > b->max_level)
+        WT_FAIL("wt_batch64_denoise_sum: count %d out of range [1,%d]", count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
+    if (n_den < 0 || n_den > count) WT_FAIL("wt_batch64_denoise_sum: n_den %d outside [0,%d]", n_den, count);
+    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("wt_batch64_denoise_sum: null tau/wgt");
+    if (dst >= 0 && dst < count) WT_FAIL("wt_batch64_denoise_sum: dst plane %d is one of the summed planes", dst);
+    Batch64DenoiseArgs a{};
+    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
+    for (int i = 0; i < count; ++i) {
+        WT_TRY(b64plane(b, i, &a.p[i]));
+        a.wgt[i] = i < n_den ? wgt[i] : 1.0;
+    }
+    double *o = nullptr;
+    WT_TRY(b64plane(b, dst, &o));
+    // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
+    WT_HIP(hipStreamSynchronize(b->ctx->stream));
+    const int row = 2 * std::max(n_den, 1);
+    for (int f = 0; f < nf; ++f)
+        for (int k = 0; k < n_den; ++k) {
+            const double t = tau[f * n_den + k];
+            b->h_tau[f * row + k] = t;
+            b->h_tau[f * row + n_den + k] = t > 0.0 ? 1.0 / t : 0.0;       // (wt64_denoise_sum's inv_tau)
+        }
+    if (n_den == 0)
+        for (int i = 0; i < nf * row; ++i) b->h_tau[i] = 0.0;
+    WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * row * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    const int64_t n2 = (int64_t)nf * b->fstride / 2;
+    ProfScope ps(b->ctx, "wt_batch64_denoise_sum_kernel");
+    hipLaunchKernelGGL(wt_batch64_denoise_sum_kernel, dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8)), dim3(256), 0,
+                       b->ctx->stream, a, (const double *)b->d_tau, o, n2, b->fstride / 2);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch64_anscombe(wt_batch64 *b, int nf, int src, int dst, double alpha, double g, double sigma, int inverse)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_anscombe"));
+    WtGuard guard_(b->ctx);
+    if (alpha == 0.0) WT_FAIL("wt_batch64_anscombe: alpha must be non-zero");
+    double *s = nullptr, *d = nullptr;
+    WT_TRY(b64plane(b, src, &s));
+    WT_TRY(b64plane(b, dst, &d));
+    const Geo &geo = b->geo.g;
+    const int64_t nrows64 = (int64_t)nf * geo.H;
+    if (nrows64 > INT32_MAX) WT_FAIL("wt_batch64_anscombe: %lld rows", (long long)nrows64);
+    const int nrows = (int)nrows64;
+    ProfScope ps(b->ctx, "wt_batch64_anscombe_kernel");
+    hipLaunchKernelGGL(wt_batch64_anscombe_kernel, dim3((geo.W + 255) / 256, (unsigned)std::min(nrows, 32768)), dim3(256), 0, b->ctx->stream,
+                       (const double *)s, d, geo.W, geo.P, nrows, alpha, g, sigma, inverse);
+    WT_HIP(hipGetLastError());
+    return 0;
+}

@@ -401,14 +401,15 @@ static int wt_fused_launch_t(PLAN *p, const FusedArgsT<T> &base, const char *nam
                       g.H >= D * (hw * ((1 << NS) - 1) + 1);
 #if WT_TU_BATCH
     // (a batch unit launches the batched kernels only: the image kernels live in the image units)
-    if constexpr (std::is_same<T, float>::value && ACC != 3) {
+    // (float32 batches: wt_batch, float64 batches: wt_batch64 - plain and accumulate passes of either)
+    if constexpr (ACC != 3) {
         if (fast) hipLaunchKernelGGL((wt_fused_batch_kernel<T, K, NS, D, NW, PD, ACC, true>), grid, block, 0, p->ctx->stream, a);
         else hipLaunchKernelGGL((wt_fused_batch_kernel<T, K, NS, D, NW, PD, ACC, false>), grid, block, 0, p->ctx->stream, a);
     } else {
-        WT_FAIL("fused pass: no batched form of this pass (float32 plain / accumulate passes only)");
+        WT_FAIL("fused pass: no batched form of this pass (plain / accumulate passes only)");
     }
 #else
-    if (frames > 1) WT_FAIL("fused pass: batches run in the batch units (wt_fused_tu_f32_k*_batch_acc*)");
+    if (frames > 1) WT_FAIL("fused pass: batches run in the batch units (wt_fused_tu_f{32,64}_k*_batch_acc*)");
     if (fast) hipLaunchKernelGGL((wt_fused_kernel<T, K, NS, D, NW, PD, ACC, true>), grid, block, 0, p->ctx->stream, a);
     else hipLaunchKernelGGL((wt_fused_kernel<T, K, NS, D, NW, PD, ACC, false>), grid, block, 0, p->ctx->stream, a);
 #endif

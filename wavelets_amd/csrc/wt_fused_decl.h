@@ -93,6 +93,12 @@ WT_FUSED_TU_DECL(3, 0) WT_FUSED_TU_DECL(3, 1) WT_FUSED_TU_DECL(3, 2)
 WT_FUSED_TU_DECL(5, 0) WT_FUSED_TU_DECL(5, 1) WT_FUSED_TU_DECL(5, 2) WT_FUSED_TU_DECL(5, 3)
 WT_FUSED_TU_DECL(3, 0) WT_FUSED_TU_DECL(3, 1) WT_FUSED_TU_DECL(3, 2) WT_FUSED_TU_DECL(3, 3)
 #undef WT_FUSED_TU_DECL
+// the batched float64 passes (wt_batch64: rows.frames = the active frames), units of their own
+#define WT_FUSED_TU_DECL(K, ACC)                                                                                       \
+    int wt_fused_tu_f64_k##K##_batch_acc##ACC(wt_plan64 *p, const FusedArgsT<double> &a, int s0, int ns, const FusedRows &rows);
+WT_FUSED_TU_DECL(5, 0) WT_FUSED_TU_DECL(5, 1) WT_FUSED_TU_DECL(5, 2)
+WT_FUSED_TU_DECL(3, 0) WT_FUSED_TU_DECL(3, 1) WT_FUSED_TU_DECL(3, 2)
+#undef WT_FUSED_TU_DECL
 
 // acc: see wt_fused_dispatch_acc; p_in / p_out only for acc != 0
 static int wt_fused_launch(wt_plan *p, const float *in, float *out_c, float **out_w, int s0, int ns,
