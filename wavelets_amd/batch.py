@@ -7,8 +7,9 @@ back in one host round trip, and the pointwise steps run once over the stack.
     wow_stack(frames, ...)              == np.stack([wow(f, ..., noise=noise_i, ...)[0] for f in frames])
 
 bit for bit.  The sequence of operations per frame is the per-frame path's own (wavelets._interleave_split,
-_scalar_tau, _noise_from_median; utils._wow_lists, _wow_factor, _gamma_range).  With bilateral= the transform
-is the batched bilateral march (one launch per scale for all frames, bilateral_eligible).  Stacks the reference
+_tau_row, _noise_from_median, _sigma_bilateral_list; utils._wow_lists, _wow_factor, _gamma_range,
+_wow_sigma_bilateral).  With bilateral= the transform is the batched bilateral march (one launch per scale for
+all frames, bilateral_eligible).  Stacks the reference
 computes in float64 (float64 frames; int16 .. int64 and big-endian frames, which it recasts) run transform_stack
 and denoise_stack on the float64 batch (wt_batch64, batch64_eligible).  Inputs the batched engines do not cover
 run the per-frame loop (batch_eligible / batch64_eligible / wow_eligible / bilateral_eligible say which)."""
@@ -16,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PLANE_INPUT, PLANE_OUT, PLANE_NONE, PLANE_SCRATCH, FLAG_FUSED
-from .wavelets import (AtrousTransform, B3spline, _family_of, _needs_generic, _interleave_split, _scalar_tau,
+from .wavelets import (AtrousTransform, B3spline, _family_of, _needs_generic, _interleave_split, _tau_row,
                        _noise_from_median, _sigma_bilateral_list, _result_dtype)
 from .utils import (denoise, wow, _GAMMA_PLANE, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments,
                     _wow_factor, _gamma_range, _wow_sigma_bilateral)
@@ -166,6 +167,24 @@ def _chunks(frames, level):
     return _lib.batch_chunks(N, H, W, level)
 
 
+def _f32_target(out, shape):
+    """the array a float32 batch downloads into: the caller's `out` - a C-contiguous float32 array of the result's
+    shape, checked before any device work - or a fresh page-locked block (the downloads land at PCIe rate)"""
+    if out is None:
+        return _lib.host_empty(shape)
+    if out.shape != shape or out.dtype != np.float32 or not out.flags.c_contiguous:
+        raise ValueError(f"out: float32 array of shape {shape} expected")
+    return out
+
+
+def _hand_over(res, out):
+    """the per-frame loop's result: as it is, or filled into the caller's `out`"""
+    if out is None:
+        return res
+    out[...] = res
+    return out
+
+
 def _f64_target(out, shape):
     """(array the float64 batch downloads into, the caller's `out` to fill afterwards or None): a C-contiguous
     float64 `out` of the result's shape receives the downloads directly; any other `out` gets the result as the
@@ -194,16 +213,10 @@ def transform_stack(frames, level, scaling_function=B3spline, out=None, bilatera
         return _transform_stack64(fr, level, scaling_function, out)
     bil = bilateral_eligible(fr, level, scaling_function, bilateral)
     if not bil and not batch_eligible(fr, level, scaling_function, bilateral):
-        res = np.stack([AtrousTransform(scaling_function, bilateral, bilateral_scaling)(f, level).data for f in fr])
-        if out is not None:
-            out[...] = res
-            return out
-        return res
+        return _hand_over(np.stack([AtrousTransform(scaling_function, bilateral, bilateral_scaling)(f, level).data
+                                    for f in fr]), out)
     N, H, W = fr.shape
-    if out is None:
-        out = _lib.host_empty((N, level + 1, H, W))          # page-locked: the downloads land at PCIe rate
-    elif out.shape != (N, level + 1, H, W) or out.dtype != np.float32 or not out.flags.c_contiguous:
-        raise ValueError(f"out: float32 array of shape {(N, level + 1, H, W)} expected")
+    out = _f32_target(out, (N, level + 1, H, W))
     if N == 0:
         return out
     ctx = _lib.default_context()
@@ -247,15 +260,6 @@ def _transform_stack64(fr, level, scaling_function, out):
     return res
 
 
-def _taus_of(entries, noise, sigma_e, soft):
-    """one frame's threshold row over `entries` (Coefficients._tau, scalar noise): 0.0 = significance one"""
-    row = []
-    for scl, sig, _ in entries:
-        t = None if sig == 0 else _scalar_tau(sig, noise, sigma_e[scl], soft)
-        row.append(0.0 if t is None else t[0])
-    return row
-
-
 def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_threshold=True, anscombe=False,
                   out=None, bilateral=None):
     """(N, H, W): utils.denoise of every frame (ref utils.py:83-102), batched - float32, or float64 for the stacks
@@ -282,17 +286,10 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
     bil = bilateral_eligible(fr, level, scaling_function, bilateral, nl)
     if not bil and not batch_eligible(fr, level, scaling_function, bilateral, nl):
         per = nl if nl is not None else [noise] * N
-        res = np.stack([denoise(f, weights, scaling_function, n_i, bilateral, soft_threshold, anscombe)
-                        for f, n_i in zip(fr, per)])
-        if out is not None:
-            out[...] = res
-            return out
-        return res
+        return _hand_over(np.stack([denoise(f, weights, scaling_function, n_i, bilateral, soft_threshold, anscombe)
+                                    for f, n_i in zip(fr, per)]), out)
     _, H, W = fr.shape
-    if out is None:
-        out = _lib.host_empty((N, H, W))                     # page-locked (as denoise(): _download_to)
-    elif out.shape != (N, H, W) or out.dtype != np.float32 or not out.flags.c_contiguous:
-        raise ValueError(f"out: float32 array of shape {(N, H, W)} expected")
+    out = _f32_target(out, (N, H, W))
     if N == 0:
         return out
     ctx = _lib.default_context()
@@ -344,7 +341,7 @@ def _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshol
         if any(n is None for n in noises) and any(sig != 0 for _, sig, _ in used):
             med = bp.abs_median(nf, 0)                                        # ref:131-132 (lazy)
             noises = [_noise_from_median(m, sigma_e) if n is None else n for n, m in zip(noises, med)]
-        taus = [_taus_of(used, n, sigma_e, soft_threshold) for n in noises]
+        taus = [_tau_row(used, n, sigma_e, soft_threshold) for n in noises]
         bp.denoise_sum(nf, level + 1 if whole else covered, taus, [w for _, _, w in used], soft_threshold)
         if not whole:
             for i in range(k, len(sched)):
@@ -364,7 +361,7 @@ def _wow_taus(bp, nf, sigma, scale, noises, sigma_e, soft):
     if sigma != 0 and any(n is None for n in noises):
         med = bp.abs_median(nf, 0)                                               # ref:131-132 (lazy)
         noises = [_noise_from_median(m, sigma_e) if n is None else n for n, m in zip(noises, med)]
-    return [_taus_of([(scale, sigma, None)], n, sigma_e, soft)[0] for n in noises], noises
+    return [_tau_row([(scale, sigma, None)], n, sigma_e, soft)[0] for n in noises], noises
 
 
 def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whitening=True, denoise_coefficients=[],
@@ -388,17 +385,11 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
     if not bil and not wow_eligible(fr, L, scaling_function, bilateral, nl):
         per = nl if nl is not None else [noise] * N
         res = [wow(f, scaling_function, n_scales, noise=n_i, **kw) for f, n_i in zip(fr, per)]
-        images = np.stack([r[0] for r in res])
-        if out is not None:
-            out[...] = images
-            images = out
+        images = _hand_over(np.stack([r[0] for r in res]), out)
         return (images, np.stack([r[1].data for r in res])) if return_coefficients else images
     _, H, W = fr.shape
     nplanes = L + 1
-    if out is None:
-        out = _lib.host_empty((N, H, W))                     # page-locked (as wow(): plan.download)
-    elif out.shape != (N, H, W) or out.dtype != np.float32 or not out.flags.c_contiguous:
-        raise ValueError(f"out: float32 array of shape {(N, H, W)} expected")
+    out = _f32_target(out, (N, H, W))
     planes = _lib.host_empty((N, nplanes, H, W)) if return_coefficients else None
     ctx = _lib.default_context()
     fam = _family_of(scaling_function(2))

@@ -17,9 +17,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import PLANE_INPUT, PLANE_OUT, PLANE_NONE, FLAG_FUSED, Plan, Context
-import copy
 
-from .wavelets import AtrousTransform, B3spline, Coefficients, _family_of
+from .wavelets import AtrousTransform, B3spline, Coefficients, _family_of, _noise_from_median
 
 __all__ = ["partition_rows", "init_comm", "StripTransform"]
 
@@ -172,7 +171,7 @@ class StripTransform:
         return self.scaling_function.sigma_e()
 
     def get_noise(self):
-        return self.plan.abs_median(0) / 0.6745 / self.sigma_e[0]
+        return _noise_from_median(self.plan.abs_median(0), self.sigma_e)
 
     def denoise(self, sigma, weights=None, soft_threshold=True):
         if weights is None:
@@ -223,15 +222,9 @@ class StripTransform:
         of scales is this transform's ``level`` (the reference derives it from the image size,
         ref:122; sharded, every scale's halo hw * 2**s must fit a strip).  Returns this rank's
         rows of the enhanced image; the whitened planes stay on the plan (``plane(s)``)."""
-        from .utils import _wow_device
+        from .utils import _wow_device, _wow_sigma_bilateral
         n_scales = self.level
-        if bilateral is None:                                             # ref:140-146
-            sigma_bilateral = None
-        else:
-            sigma_bilateral = copy.copy(bilateral) if type(bilateral) is list \
-                else [bilateral, ] * (n_scales + 1)
-            if len(sigma_bilateral) <= n_scales:
-                sigma_bilateral.extend([1, ] * (n_scales - len(sigma_bilateral) + 1))
+        sigma_bilateral = _wow_sigma_bilateral(bilateral, n_scales)       # ref:140-146
         transform = AtrousTransform(type(self.scaling_function), bilateral=sigma_bilateral,
                                     bilateral_scaling=bilateral_scaling)
         transform._run(self.plan, n_scales, flags=FLAG_FUSED if self.fused else 0)   # ref:148-151

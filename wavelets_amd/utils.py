@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import PLANE_NONE, PLANE_OUT, PLANE_SCRATCH, acquire_plan, acquire_plan64, default_context, release_plan
 from .wavelets import (AtrousTransform, B3spline, Coefficients, _decompose_denoise_sum, _f32_source, _f64_source, _family_of, _needs_generic,
-                       _result_dtype, _taps_f64, _to_f32_image,
+                       _interleave_split, _result_dtype, _sigma_bilateral_list, _taps_f64, _tau_row, _to_f32_image,
                        generalized_anscombe,
                        PLANE_INPUT)
 
@@ -105,23 +105,12 @@ def _denoise_pipelined(plan, img, level, sf, weights, noise, bilateral, soft_thr
         return None
     if img.size < (1 << 22) or not plan.fused_ok(level):
         return None
-    entries = list(zip(range(level + 1), weights, (1,) * len(weights)))
-    n_den = max([scl + 1 for scl, sig, _ in entries if sig != 0], default=0)
     sched = _lib.schedule(plan.family, level, True)
-    k, covered = 0, 0
-    while k < len(sched) and (covered < n_den or k == 0):
-        covered += sched[k][1]
-        k += 1
-    if k == 0 or k >= len(sched) or n_den == 0:
+    entries, k, covered = _interleave_split(sched, level, weights, (1,) * len(weights))
+    # not the pipeline's: no pass or a single one, every pass before the threshold step, nothing to threshold
+    if k == 0 or k >= len(sched) or not any(sig != 0 for _, sig, _ in entries):
         return None
-    sigma_e = sf.sigma_e()
-    taus = []
-    for scl in range(covered):
-        sig = weights[scl] if scl < len(weights) else 0
-        tau = float(sig * noise * sigma_e[scl]) if sig != 0 and noise != 0 else 0.0     # ref wavelets.py:133-141
-        if tau < 0:                      # erf(|w / tau|) = erf(|w| / |tau|); |w| > tau always true (hard)
-            tau = -tau if soft_threshold else 0.0
-        taus.append(tau)
+    taus = _tau_row(entries[:covered], noise, sf.sigma_e(), soft_threshold)
     try:
         if not (isinstance(out, np.ndarray) and out.ndim == 2 and out.dtype == np.float32 and out.shape == tuple(plan.shape)
                 and out.strides[1] == 4 and out.flags.writeable):
@@ -144,6 +133,25 @@ def _download_to(plan, target):
     return plan.download(PLANE_OUT)
 
 
+def _denoise_serial(plan, img, sf, weights, noise, bilateral, soft_threshold, anscombe, out):
+    """The serial sequence of denoise() for the image `img` on a freshly acquired float32 or float64 `plan` (which
+    the Coefficients object takes over and releases): upload, Anscombe, transform + thresholds + sum, inverse
+    Anscombe, download.  Returns what _download_to returns."""
+    plan.upload(PLANE_INPUT, img)
+    if anscombe:
+        plan.anscombe(PLANE_INPUT, PLANE_INPUT)                           # ref:93-94
+    coefficients = Coefficients(plan, sf, bilateral)
+    coefficients.noise = noise                                            # ref:96
+    # ref:95, 97-98: transform, threshold and sum interleaved (trailing zero sigmas - scales that
+    # are transformed but not thresholded - ride on the accumulate passes); the thresholded planes
+    # themselves are not returned by denoise(), so they are not written back
+    _decompose_denoise_sum(AtrousTransform(type(sf), bilateral=bilateral), plan, len(weights), coefficients, weights,
+                           soft_threshold=soft_threshold, write_back=False)
+    if anscombe:
+        plan.anscombe(PLANE_OUT, PLANE_OUT, inverse=True)                 # ref:99-100
+    return _download_to(plan, out)
+
+
 def denoise(data, weights, scaling_function=B3spline, noise=None, bilateral=None,
             soft_threshold=True, anscombe=False, *, _out=None):
     """Denoise ``data``: transform over ``len(weights)`` scales, threshold each scale at
@@ -156,20 +164,9 @@ def denoise(data, weights, scaling_function=B3spline, noise=None, bilateral=None
         # the first one histogramming |w_0|, thresholds + start of the sum in one kernel
         # (wt64_denoise_sum), the later passes carrying the sum
         img = _f64_source(data)           # (integer images are widened on the device)
-        level = len(weights)
-        transform = AtrousTransform(scaling_function)
         sf = scaling_function(2)
-        plan = acquire_plan64(default_context(), img.shape[0], img.shape[1], _taps_f64(sf, 2), level)
-        plan.upload(PLANE_INPUT, img)
-        if anscombe:
-            plan.anscombe(PLANE_INPUT, PLANE_INPUT)                       # ref:93-94
-        coefficients = Coefficients(plan, sf, None)
-        coefficients.noise = noise                                        # ref:96
-        _decompose_denoise_sum(transform, plan, level, coefficients, weights,
-                               soft_threshold=soft_threshold, write_back=False)
-        if anscombe:
-            plan.anscombe(PLANE_OUT, PLANE_OUT, inverse=True)             # ref:99-100
-        return _download_to(plan, _out)
+        plan = acquire_plan64(default_context(), img.shape[0], img.shape[1], _taps_f64(sf, 2), len(weights))
+        return _denoise_serial(plan, img, sf, weights, noise, None, soft_threshold, anscombe, _out)
     if np.ndim(data) in (1, 3) or (f64 and np.ndim(data) == 2) or _needs_generic(scaling_function):
         # signals, cubes and float64 images: the generic call sequence
         arr = np.asarray(data, np.float64 if f64 else np.float32)
@@ -183,7 +180,6 @@ def denoise(data, weights, scaling_function=B3spline, noise=None, bilateral=None
         return coefficients._from_plane(plan.download(PLANE_OUT)).astype(_result_dtype(data), copy=False)
     img = _f32_source(data, "data")       # (integer / byte-swapped images are widened on the device)
     level = len(weights)
-    transform = AtrousTransform(scaling_function, bilateral=bilateral)
     sf = scaling_function(2)
     plan = acquire_plan(default_context(), img.shape[0], img.shape[1], _family_of(sf), level)
     piped = None
@@ -192,19 +188,8 @@ def denoise(data, weights, scaling_function=B3spline, noise=None, bilateral=None
     if piped is not None:
         release_plan(plan)
         return piped.astype(_result_dtype(data), copy=False)
-    plan.upload(PLANE_INPUT, img)
-    if anscombe:
-        plan.anscombe(PLANE_INPUT, PLANE_INPUT)                           # ref:93-94
-    coefficients = Coefficients(plan, sf, bilateral)
-    coefficients.noise = noise                                            # ref:96
-    # ref:95, 97-98: transform, threshold and sum interleaved (trailing zero sigmas - scales that
-    # are transformed but not thresholded - ride on the accumulate passes); the thresholded planes
-    # themselves are not returned by denoise(), so they are not written back
-    _decompose_denoise_sum(transform, plan, level, coefficients, weights,
-                           soft_threshold=soft_threshold, write_back=False)
-    if anscombe:
-        plan.anscombe(PLANE_OUT, PLANE_OUT, inverse=True)                 # ref:99-100
-    return _download_to(plan, _out).astype(_result_dtype(data), copy=False)
+    return _denoise_serial(plan, img, sf, weights, noise, bilateral, soft_threshold, anscombe, _out).astype(
+        _result_dtype(data), copy=False)
 
 
 def _pad_list(values, n, fill):
@@ -291,13 +276,7 @@ def _wow_scale_limit(n_scales, scaling_function, n_dims, bilateral, denoise_coef
 def _wow_sigma_bilateral(bilateral, n_scales):
     """the per-scale sigma_bilateral list wow() hands to its transform, n_scales + 1 long at least (ref:140-146):
     None without bilateral filtering, a scalar repeated, a short list padded with 1"""
-    if bilateral is None:
-        return None
-    sigma_bilateral = copy.copy(bilateral) if type(bilateral) is list \
-        else [bilateral, ] * (n_scales + 1)
-    if len(sigma_bilateral) <= n_scales:
-        sigma_bilateral.extend([1, ] * (n_scales - len(sigma_bilateral) + 1))
-    return sigma_bilateral
+    return None if bilateral is None else _sigma_bilateral_list(bilateral, n_scales)
 
 
 def _wow_lists(weights, denoise_coefficients, n_scales):

@@ -579,9 +579,19 @@ def _scalar_tau(sigma, noise, sigma_e_scale, soft=True):
     return tau, PLANE_NONE
 
 
+def _tau_row(entries, noise, sigma_e, soft):
+    """One image's (or one frame's) row of thresholds over the (scale, sigma, weight) `entries` for a scalar
+    noise level (Coefficients._tau, ref:129-143): 0.0 = significance one"""
+    row = []
+    for scl, sig, _ in entries:
+        t = None if sig == 0 else _scalar_tau(sig, noise, sigma_e[scl], soft)
+        row.append(0.0 if t is None else t[0])
+    return row
+
+
 def _sigma_bilateral_list(bilateral, level):
-    """Per-scale sigma_bilateral list of a transform over `level` scales (ref:421-424): a scalar repeated, a list
-    copied and padded with 1 (AtrousTransform._sigma_bilateral; batch.py runs the same rule for a stack)."""
+    """Per-scale sigma_bilateral list of a transform over `level` scales (ref:421-424; wow's own, ref utils.py:140-146,
+    is the same rule): a scalar repeated, a list copied and padded with 1."""
     sb = copy.copy(bilateral) if type(bilateral) is list \
         else [bilateral, ] * (level + 1)
     if len(sb) <= level:
@@ -762,7 +772,7 @@ class Coefficients:
         return self.scaling_function.sigma_e(bilateral=self.bilateral)    # ref:122-124
 
     def get_noise(self):
-        """MAD noise estimate: median(|w_0|) / 0.6745 / sigma_e[0] (ref:126-127).  The exact
+        """MAD noise estimate from median(|w_0|) (ref:126-127, _noise_from_median).  The exact
         median is a radix select on the GPU; the scalar divisions follow numpy's promotion."""
         self._device()
         return self._noise_from_device()
@@ -790,6 +800,18 @@ class Coefficients:
         if tau < 0 and not soft:
             return None
         return abs(tau), _NOISE_PLANE
+
+    def _threshold_row(self, entries, soft):
+        """(taus, wgts, noise_plane) of the (scale, sigma, weight) `entries` for wt_denoise_sum: _tau per entry
+        (lazy MAD estimate and noise map included), 0.0 = significance one.  Runs inside a device operation."""
+        taus, wgts, noise_plane = [], [], PLANE_NONE
+        for scl, sig, wgt in entries:
+            t = self._tau(sig, scl, soft)
+            taus.append(0.0 if t is None else t[0])
+            wgts.append(wgt)
+            if t is not None and t[1] != PLANE_NONE:
+                noise_plane = t[1]
+        return taus, wgts, noise_plane
 
     def significance(self, sigma, scale, soft_threshold=True):
         """erf(|w|/tau) (soft) or |w| > tau (hard, bool), tau = sigma*noise*sigma_e[scale]
@@ -846,13 +868,7 @@ class Coefficients:
             return plan
         plan = self._device()
         self._sum_valid = False              # PLANE_OUT becomes the DENOISED sum
-        taus, wgts, noise_plane = [], [], PLANE_NONE
-        for scl, (_, sig, wgt) in enumerate(zip(range(self._nplanes), sigma, weights)):
-            t = self._tau(sig, scl, soft_threshold)
-            taus.append(0.0 if t is None else t[0])
-            wgts.append(wgt)
-            if t is not None and t[1] != PLANE_NONE:
-                noise_plane = t[1]
+        taus, wgts, noise_plane = self._threshold_row(zip(range(self._nplanes), sigma, weights), soft_threshold)
         plan.denoise_sum(self._nplanes, taus, wgts, soft_threshold, noise_plane, write_back)
         if write_back:
             self._refresh_host(range(len(taus)))
@@ -916,13 +932,7 @@ def _decompose_denoise_sum(transform, plan, level, coefficients, sigma, weights=
         if first:
             coefficients.noise = coefficients._noise_from_device()
         cur = nxt
-    taus, wgts, noise_plane = [], [], PLANE_NONE
-    for scl, sig, wgt in entries[:covered]:
-        t = coefficients._tau(sig, scl, soft_threshold)
-        taus.append(0.0 if t is None else t[0])
-        wgts.append(wgt)
-        if t is not None and t[1] != PLANE_NONE:
-            noise_plane = t[1]
+    taus, wgts, noise_plane = coefficients._threshold_row(entries[:covered], soft_threshold)
     plan.denoise_sum(covered, taus, wgts, soft_threshold, noise_plane, write_back)
     for i in range(k, len(sched)):
         last = i == len(sched) - 1
@@ -932,6 +942,35 @@ def _decompose_denoise_sum(transform, plan, level, coefficients, sigma, weights=
         cur = nxt
     coefficients._sum_valid = bool(write_back) and coefficients._host is None
     return plan
+
+
+def _bilateral_scales(plan, level, sb, scaling, nd, depth, var_border, conv_border):
+    """The per-scale sequence of the bilateral transform (ref:433-442; recursive: ref:375-378, 402-403) over `level`
+    scales of the image in the plan's input plane: variance = sdev_loc(c_s)**2 * sb[s]**2 (* (s + 1) with
+    `scaling`), c_{s+1} = the range-weighted convolution of c_s, w_s = c_s - c_{s+1}; the smooth planes ping-pong
+    between two scratch planes.  Signals (nd == 1: the plan holds the taps reversed) and images run the 2-D
+    operators, cubes (nd == 3, `depth` slices) the 3-D ones.  var_border / conv_border: the plan's border code
+    set before the variance step (convolution()'s border, ref:24-32) and before the convolution step (ref:77);
+    None leaves the border as it is."""
+    cur = PLANE_INPUT
+    for s in range(level):
+        nxt = level if s == level - 1 else PLANE_SCRATCH(s & 1)
+        f1 = float(sb[s]) ** 2
+        f2 = float(s + 1) if scaling else 1.0
+        if var_border is not None:
+            plan.set_border(var_border)
+        if nd == 3:
+            plan.local_variance3d(cur, _TMP_PLANE, s, depth, f1, f2)
+        else:
+            plan.local_variance(cur, _TMP_PLANE, s, f1, f2)
+        if conv_border is not None:
+            plan.set_border(conv_border)
+        if nd == 3:
+            plan.bilateral3d_conv(cur, _TMP_PLANE, nxt, s, depth)
+        else:
+            plan.bilateral_conv(cur, _TMP_PLANE, nxt, s, _lib.FLAG_TAPS_REVERSED if nd == 1 else 0)
+        plan.binary("sub", cur, nxt, s)                                    # ref:442
+        cur = nxt
 
 
 def _rebuild_coefficients(data, scaling_function, bilateral, noise):
@@ -1114,23 +1153,9 @@ class AtrousTransform:
             # kernel per scale, wt64_decompose_bilateral)
             plan.decompose_bilateral(PLANE_INPUT, level, self._sigma_bilateral(level), self.bilateral_scaling)
         else:
-            sb = self._sigma_bilateral(level)
-            cur = PLANE_INPUT
-            for s in range(level):
-                nxt = level if s == level - 1 else PLANE_SCRATCH(s & 1)
-                f1 = float(sb[s]) ** 2
-                f2 = float(s + 1) if self.bilateral_scaling else 1.0
-                if nd == 3:
-                    plan.local_variance3d(cur, _TMP_PLANE, s, a.shape[0], f1, f2)
-                    plan.bilateral3d_conv(cur, _TMP_PLANE, nxt, s, a.shape[0])
-                else:
-                    plan.set_border(2 if nd == 1 else 0)           # variance: convolution()'s border
-                    plan.local_variance(cur, _TMP_PLANE, s, f1, f2)
-                    plan.set_border(0)                             # ref:77: symmetric pad
-                    plan.bilateral_conv(cur, _TMP_PLANE, nxt, s,
-                                        _lib.FLAG_TAPS_REVERSED if nd == 1 else 0)
-                plan.binary("sub", cur, nxt, s)                    # ref:442
-                cur = nxt
+            # signals: the variance under convolution()'s 'mirror' border, then the symmetric pad of ref:77
+            borders = (None, None) if nd == 3 else (2 if nd == 1 else 0, 0)
+            _bilateral_scales(plan, level, self._sigma_bilateral(level), self.bilateral_scaling, nd, a.shape[0], *borders)
             if level == 0:
                 plan.decompose(PLANE_INPUT, 0)
         return Coefficients(plan, scaling_function, self.bilateral,
@@ -1173,17 +1198,7 @@ class AtrousTransform:
         # one: the taps of the other axis all reflect onto the same row, carry weight e = 1 and
         # factor out of numerator and denominator.
         # (user-defined taps: the plan of a 1-D signal holds them reversed, see _family_of)
-        sb = self._sigma_bilateral(level)
-        cur = PLANE_INPUT
-        for s in range(level):
-            nxt = level if s == level - 1 else PLANE_SCRATCH(s & 1)
-            plan.set_border(2)
-            plan.local_variance(cur, _TMP_PLANE, s, float(sb[s]) ** 2,
-                                float(s + 1) if self.bilateral_scaling else 1.0)
-            plan.set_border(0)
-            plan.bilateral_conv(cur, _TMP_PLANE, nxt, s, _lib.FLAG_TAPS_REVERSED)
-            plan.binary("sub", cur, nxt, s)                                # ref:442
-            cur = nxt
+        _bilateral_scales(plan, level, self._sigma_bilateral(level), self.bilateral_scaling, 1, 0, 2, 0)
         if level == 0:
             plan.copy(PLANE_INPUT, 0)
         return Coefficients(plan, scaling_function, self.bilateral, _dtype=_result_dtype(arr))
@@ -1204,15 +1219,7 @@ class AtrousTransform:
             plan.decompose3d(PLANE_INPUT, level, Z)
             return Coefficients(plan, scaling_function, None, _shape=(Z, Y, X), _dtype=_result_dtype(arr))
         # bilateral (ref:433-440 on a cube): 3-D variance, then the K^3 range-weighted kernel
-        sb = self._sigma_bilateral(level)
-        cur = PLANE_INPUT
-        for s in range(level):
-            nxt = level if s == level - 1 else PLANE_SCRATCH(s & 1)
-            plan.local_variance3d(cur, _TMP_PLANE, s, Z, float(sb[s]) ** 2,
-                                  float(s + 1) if self.bilateral_scaling else 1.0)
-            plan.bilateral3d_conv(cur, _TMP_PLANE, nxt, s, Z)
-            plan.binary("sub", cur, nxt, s)                                # ref:442
-            cur = nxt
+        _bilateral_scales(plan, level, self._sigma_bilateral(level), self.bilateral_scaling, 3, Z, None, None)
         if level == 0:
             plan.copy(PLANE_INPUT, 0)
         return Coefficients(plan, scaling_function, self.bilateral, _shape=(Z, Y, X), _dtype=_result_dtype(arr))
@@ -1250,24 +1257,11 @@ class AtrousTransform:
                 else:
                     big.decompose(PLANE_INPUT, level, 0)      # one kernel per scale
             else:
-                sb = self._sigma_bilateral(level)
-                cur = PLANE_INPUT
-                for s in range(level):
-                    nxt = level if s == level - 1 else PLANE_SCRATCH(s & 1)
-                    f1 = float(sb[s]) ** 2
-                    f2 = float(s + 1) if self.bilateral_scaling else 1.0
-                    if nd == 3:
-                        big.set_border(sym)
-                        big.local_variance3d(cur, _TMP_PLANE, s, padded.shape[0], f1, f2)
-                        big.bilateral3d_conv(cur, _TMP_PLANE, nxt, s, padded.shape[0])
-                    else:
-                        big.set_border(conv_border)           # ref:375: sdev_loc over convolution()
-                        big.local_variance(cur, _TMP_PLANE, s, f1, f2)
-                        big.set_border(sym)                   # ref:378: mode='symmetric'
-                        big.bilateral_conv(cur, _TMP_PLANE, nxt, s,
-                                           _lib.FLAG_TAPS_REVERSED if nd == 1 else 0)
-                    big.binary("sub", cur, nxt, s)            # ref:402-403
-                    cur = nxt
+                # cubes: the symmetric border for both steps; else ref:375 (sdev_loc over convolution()), then
+                # ref:378 (mode='symmetric')
+                borders = (sym, None) if nd == 3 else (conv_border, sym)
+                _bilateral_scales(big, level, self._sigma_bilateral(level), self.bilateral_scaling, nd, padded.shape[0],
+                                  *borders)
             for s in range(level + 1):                        # ref:405-406
                 if nd == 3:
                     Z, Y, X = arr.shape
