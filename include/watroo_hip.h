@@ -343,6 +343,9 @@ int wt_wow_scale(wt_plan *plan, int plane, int s, double tau, int soft, int nois
                  float factor, int gamma_plane, int flags);
 /* global reductions for wow (watroo/utils.py:180-187,209-211): out = {sum, sumsq, min, max} */
 int wt_reduce(wt_plan *plan, int plane, double out[4]);
+/* plane <- standard normal deviates, Philox4x32-10 keyed by seed, counter (x>>2, y, trial, 0)
+ * (the frame np.random.normal(size=...).astype(np.float32) draws in watroo/wavelets.py:225) */
+int wt_fill_normal(wt_plan *plan, int plane, uint64_t seed, uint32_t trial);
 /* gamma blend (watroo/utils.py:212-217):
  *   g <- clip((g-gmin)/(gmax-gmin),0,1)**(1/gamma); recon <- (1-h)*recon + h*g */
 int wt_gamma_blend(wt_plan *plan, int recon, int gamma_plane, float gmin, float gmax,
@@ -627,6 +630,9 @@ int wt_batch_anscombe(wt_batch *batch, int nf, int src, int dst, float alpha, fl
  * arrays of nf entries; every frame gets the bits of the per-frame call on a wt_plan. */
 /* plane <- value over the active frames (gamma_scaled = zeros, watroo/utils.py:157-158; as wt_fill_plane) */
 int wt_batch_fill(wt_batch *batch, int nf, int plane, float value);
+/* frame f of the plane <- wt_fill_normal(seed, first_trial + f) of a wt_plan of the frame's shape, frames 0 .. nf-1
+ * (the frames of compute_noise_weights' trials, watroo/wavelets.py:223-225) */
+int wt_batch_fill_normal(wt_batch *batch, int nf, int plane, uint64_t seed, uint32_t first_trial);
 /* wt_wow_update per frame without a power plane or noise map (watroo/utils.py:185-191 with local_power = 1, 199-203):
  * wow's last plane, whitening=False and h >= 1; tau[f] <= 0: significance one; gamma_plane may be WT_PLANE_NONE */
 int wt_batch_wow_update(wt_batch *batch, int nf, int plane, const double *tau, int soft, const float *factor,

@@ -85,6 +85,7 @@ SIGNATURES = {
     "wt_download": (_c.c_int, [_vp, _c.c_int, _fp, _i64]),
     "wt_copy_plane": (_c.c_int, [_vp, _c.c_int, _c.c_int]),
     "wt_fill_plane": (_c.c_int, [_vp, _c.c_int, _c.c_float]),
+    "wt_fill_normal": (_c.c_int, [_vp, _c.c_int, _c.c_uint64, _c.c_uint32]),
     "wt_halo_exchange_local": (_c.c_int, [_vp, _vp, _c.c_int, _i64]),
     "wt_halo_exchange": (_c.c_int, [_vp, _c.c_int, _i64]),
     "wt_decompose": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int]),
@@ -215,6 +216,7 @@ SIGNATURES = {
     "wt_batch_anscombe": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float,
                                      _c.c_int]),
     "wt_batch_fill": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_float]),
+    "wt_batch_fill_normal": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_uint64, _c.c_uint32]),
     "wt_batch_wow_update": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _fp, _c.c_int]),
     "wt_batch_wow_scale": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _fp,
                                       _c.c_int]),
@@ -593,6 +595,20 @@ def _elem_source(host, shape):
     return h.ctypes.data, h.strides[0], code
 
 
+def _seed64(seed):
+    """the 64-bit seed of the normal fill as an int, or ValueError"""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"seed: an integer in 0 .. 2**64-1 expected (got {seed!r})")
+    return int(seed)
+
+
+def _trial32(trial):
+    """the trial number of the normal fill: counter word 2 is 32 bits wide"""
+    if isinstance(trial, bool) or not isinstance(trial, (int, np.integer)) or not 0 <= int(trial) < 1 << 32:
+        raise ValueError(f"trial: an integer in 0 .. 2**32-1 expected (got {trial!r})")
+    return int(trial)
+
+
 def _as_f32(a):
     a = np.ascontiguousarray(a, dtype=np.float32)
     if a.ndim != 2:
@@ -717,6 +733,10 @@ class Plan:
 
     def fill(self, plane, value):
         check(load().wt_fill_plane(self._h, plane, value))
+
+    def fill_normal(self, plane, seed, trial=0):
+        """`plane` <- standard normal deviates of (seed, trial): Philox4x32-10, counter (x >> 2, y, trial, 0) (rng.py)"""
+        check(load().wt_fill_normal(self._h, plane, _seed64(seed), _trial32(trial)))
 
     def plane_ptr(self, plane):
         p = _vp()
@@ -1037,6 +1057,10 @@ class BatchPlan:
 
     def fill(self, nf, plane, value):
         check(load().wt_batch_fill(self._h, nf, plane, value))
+
+    def fill_normal(self, nf, plane, seed, first_trial=0):
+        """frame f of `plane` <- Plan.fill_normal(plane, seed, first_trial + f), frames 0 .. nf-1 (rng.py: the layout)"""
+        check(load().wt_batch_fill_normal(self._h, nf, plane, _seed64(seed), _trial32(first_trial)))
 
     def wow_update(self, nf, plane, taus, soft, factors, gamma_plane=PLANE_NONE):
         """Plan.wow_update per frame without power plane or noise map: taus[f] (0.0: significance one), factors[f]"""

@@ -10,6 +10,7 @@
 #include "wt_kernels_apps.h"
 #include "wt_fft.h"
 #include "wt_axis.h"
+#include "wt_rng.h"
 #include "wt_unit_probe.h"
 
 WT_UNIT_PROBE_DEFINE
@@ -662,6 +663,16 @@ extern "C" int wt_mrs_update(wt_plan *p, int plane, int mrs_plane, double tau, i
     hipLaunchKernelGGL(wt_mrs_kernel, dim3(flat_grid(n4)), dim3(256), 0, p->ctx->stream, c, m, nz, n4, tau, soft, persistent, inv_pow);
     WT_HIP(hipGetLastError());
     return 0;
+}
+
+// plane <- standard normal deviates (wt_rng.h: Philox4x32-10 keyed by seed, counter (x >> 2, y, trial, 0))
+extern "C" int wt_fill_normal(wt_plan *p, int plane, uint64_t seed, uint32_t trial)
+{
+    WtGuard guard_(ctx_of(p));
+    if (!p) WT_FAIL("wt_fill_normal: null plan");
+    float *d = nullptr;
+    WT_TRY(plane_base(p, plane, &d));
+    return wt_launch_fill_normal(p->ctx, d, p->g, p->g.nrows, 1, 0, seed, trial);
 }
 
 // =============================================================================================

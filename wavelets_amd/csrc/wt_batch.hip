@@ -20,6 +20,7 @@
 #include "wt_host.h"
 #include "wt_fused_decl.h"
 #include "wt_reduce.h"
+#include "wt_rng.h"
 #include "wt_stencil_launch.h"
 #include "wt_unit_probe.h"
 
@@ -690,6 +691,16 @@ extern "C" int wt_batch_fill(wt_batch *b, int nf, int plane, float value)
     hipLaunchKernelGGL(wt_batch_fill_kernel, dim3(flat_grid(n4)), dim3(256), 0, b->ctx->stream, d, n4, value);
     WT_HIP(hipGetLastError());
     return 0;
+}
+
+// frame f of the plane <- the field wt_fill_normal(seed, first_trial + f) gives a wt_plan of the frame's shape
+extern "C" int wt_batch_fill_normal(wt_batch *b, int nf, int plane, uint64_t seed, uint32_t first_trial)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_fill_normal"));
+    WtGuard guard_(b->ctx);
+    float *d = nullptr;
+    WT_TRY(bplane(b, plane, &d));
+    return wt_launch_fill_normal(b->ctx, d, b->geo.g, b->geo.g.H, nf, b->fstride, seed, first_trial);
 }
 
 static int wow_pairs(wt_batch *b, int nf, const double *tau, const float *factor, const double **dev, const char *who)

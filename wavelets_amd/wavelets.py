@@ -77,8 +77,16 @@ class AbstractScalingFunction:
             raise ValueError("Unsupported number of dimensions")          # ref:208,218
         return getattr(self, f"sigma_e_{self.n_dim}d{suffix}")
 
-    def compute_noise_weights(self, n_scales, n_trials=100, bilateral=None):
-        """Monte-Carlo calibration of sigma_e (ref:221-229) on top of the GPU transform."""
+    def compute_noise_weights(self, n_scales, n_trials=100, bilateral=None, seed=None):
+        """Monte-Carlo calibration of sigma_e (ref:221-229) on top of the GPU transform.
+
+        ``seed`` (not in the reference): None draws every frame with ``np.random.normal`` on the host, as the
+        reference does.  An integer in 0 .. 2**64-1 makes trial t the seeded standard-normal frame (seed, t) of
+        ``rng.normal_frames`` - reproducible, and made on the GPU: images of a built-in family run their trials
+        on the batched engine (filled, transformed and reduced in chunks of frames; no frame and no plane crosses
+        PCIe), other images fill a plan per trial; signals and cubes take the host mirror's frames."""
+        if seed is not None:
+            return self._noise_weights_seeded(n_scales, n_trials, bilateral, _lib._seed64(seed))
         transform = AtrousTransform(self.__class__, bilateral=bilateral)
         std = np.zeros(n_scales)
         for _ in range(n_trials):
@@ -91,8 +99,67 @@ class AbstractScalingFunction:
             npix = float(plan.H) * float(plan.W)
             for s in range(n_scales):
                 tot, tot2, _, _ = plan.reduce(s)
-                std[s] += np.sqrt(max(tot2 / npix - (tot / npix) ** 2, 0.0))
+                std[s] += _std_from_moments(tot, tot2, npix)
         return std / n_trials
+
+    def _noise_weights_seeded(self, n_scales, n_trials, bilateral, seed):
+        """compute_noise_weights with trial t's frame = the seeded normal frame (seed, t) (rng.py)"""
+        from . import batch, rng
+        side = len(self.sigma_e_1d) * 2 ** n_scales
+        transform = AtrousTransform(self.__class__, bilateral=bilateral)
+        std = np.zeros(n_scales)
+        if self.n_dim != 2 or _needs_generic(self):
+            # signals and cubes: the field over the flattened index, counter (i >> 2, 0, trial, 0); images of a
+            # scaling function the generic operator serves: the transform takes a host frame
+            for t in range(n_trials):
+                if self.n_dim == 2:
+                    data = rng.normal_frames(1, (side, side), seed, t)[0]
+                else:
+                    data = rng.normal_frames_host(1, (1, side ** self.n_dim), seed, t).reshape((side,) * self.n_dim)
+                plan = transform(data, n_scales)._device()
+                npix = float(plan.H) * float(plan.W)
+                for s in range(n_scales):
+                    tot, tot2, _, _ = plan.reduce(s)
+                    std[s] += _std_from_moments(tot, tot2, npix)
+            return std / n_trials
+        npix = float(side) * float(side)
+        stack = np.broadcast_to(np.float32(0), (max(n_trials, 1), side, side))     # what the predicates look at
+        bil = batch.bilateral_eligible(stack, n_scales, self.__class__, bilateral)
+        if bil or batch.wow_eligible(stack, n_scales, self.__class__, bilateral):
+            chunks = _lib.batch_chunks(n_trials, side, side, n_scales)
+            if not chunks:
+                return std / n_trials
+            bp = _lib.acquire_batch(default_context(), max(nf for _, nf in chunks), side, side, self._family, n_scales)
+            try:
+                for f0, nf in chunks:
+                    bp.fill_normal(nf, PLANE_INPUT, seed, f0)
+                    if bil:
+                        bp.decompose_bilateral(nf, PLANE_INPUT, n_scales, _sigma_bilateral_list(bilateral, n_scales))
+                    else:
+                        bp.decompose(nf, PLANE_INPUT, n_scales, FLAG_FUSED)
+                    moments = [bp.reduce(nf, s) for s in range(n_scales)]
+                    for f in range(nf):                                   # (trial order, scale by scale: the loop above)
+                        for s in range(n_scales):
+                            std[s] += _std_from_moments(moments[s][f][0], moments[s][f][1], npix)
+            finally:
+                _lib.release_batch(bp)
+            return std / n_trials
+        for t in range(n_trials):                                        # user-defined taps: a plan per trial
+            plan = acquire_plan(default_context(), side, side, _family_of(self), n_scales)
+            try:
+                plan.fill_normal(PLANE_INPUT, seed, t)
+                transform._run(plan, n_scales)
+                for s in range(n_scales):
+                    tot, tot2, _, _ = plan.reduce(s)
+                    std[s] += _std_from_moments(tot, tot2, npix)
+            finally:
+                release_plan(plan)
+        return std / n_trials
+
+
+def _std_from_moments(tot, tot2, npix):
+    """np.std of a plane from its fp64 sum and sum of squares (wt_reduce)"""
+    return np.sqrt(max(tot2 / npix - (tot / npix) ** 2, 0.0))
 
 
 class Triangle(AbstractScalingFunction):
