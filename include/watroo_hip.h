@@ -622,6 +622,11 @@ int wt_batch_abs_median(wt_batch *batch, int nf, int plane, float *medians);
  * weights wgt[k] shared by the frames; scalar noise only */
 int wt_batch_denoise_sum(wt_batch *batch, int nf, int count, int dst, int n_den, const double *tau,
                          const double *wgt, int soft, int write_back);
+/* wt_batch_denoise_sum with one weight row per frame too (utils.enhance per channel, watroo/utils.py:60-78: the
+ * channels of a colour image are frames with their own sigmas AND weights): tau and wgt hold nf * n_den entries, the
+ * row of frame f at f * n_den; 1 <= n_den <= count; scalar noise only */
+int wt_batch_enhance_sum(wt_batch *batch, int nf, int count, int dst, int n_den, const double *tau,
+                         const double *wgt, int soft, int write_back);
 /* generalized_anscombe over the active frames (watroo/utils.py:93-94, 99-100; as wt_anscombe) */
 int wt_batch_anscombe(wt_batch *batch, int nf, int src, int dst, float alpha, float g, float sigma,
                       int inverse);
@@ -694,6 +699,10 @@ int wt_batch64_abs_median(wt_batch64 *batch, int nf, int plane, double *medians)
  * 0..count-1, the first n_den thresholded at tau[frame * n_den + k] (<= 0: significance one), weights wgt[k]
  * shared by the frames; scalar noise only */
 int wt_batch64_denoise_sum(wt_batch64 *batch, int nf, int count, int dst, int n_den, const double *tau,
+                           const double *wgt, int soft, int write_back);
+/* wt_batch64_denoise_sum with one weight row per frame too (utils.enhance per channel, watroo/utils.py:60-78): tau
+ * and wgt hold nf * n_den entries, the row of frame f at f * n_den; 1 <= n_den <= count; scalar noise only */
+int wt_batch64_enhance_sum(wt_batch64 *batch, int nf, int count, int dst, int n_den, const double *tau,
                            const double *wgt, int soft, int write_back);
 /* generalized_anscombe over the active frames (watroo/utils.py:93-94, 99-100; as wt64_anscombe) */
 int wt_batch64_anscombe(wt_batch64 *batch, int nf, int src, int dst, double alpha, double g, double sigma,

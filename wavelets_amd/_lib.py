@@ -213,6 +213,8 @@ SIGNATURES = {
     "wt_batch_abs_median": (_c.c_int, [_vp, _c.c_int, _c.c_int, _fp]),
     "wt_batch_denoise_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
                                         _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
+    "wt_batch_enhance_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
+                                        _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
     "wt_batch_anscombe": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float,
                                      _c.c_int]),
     "wt_batch_fill": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_float]),
@@ -239,6 +241,8 @@ SIGNATURES = {
                                                  _c.c_int, _c.c_int, _c.c_int]),
     "wt_batch64_abs_median": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double)]),
     "wt_batch64_denoise_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
+                                          _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
+    "wt_batch64_enhance_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
                                           _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
     "wt_batch64_anscombe": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_double, _c.c_double,
                                        _c.c_int]),
@@ -935,6 +939,7 @@ class Plan:
 # ------------------------------------------------------------------------------------------
 # batches of same-shape frames (wt_batch): every fused pass runs over all frames in one launch
 # ------------------------------------------------------------------------------------------
+MAX_SUM_PLANES = 16                        # WT_MAX_SUM_PLANES: planes one launch of a plane sum folds
 BATCH_MAX_FRAMES = 65535                  # grid z of the fused launches (one frame per z slice)
 BATCH_BYTES = int(os.environ.get("WATROO_HIP_BATCH_BYTES", str(4 << 30)))   # device bytes of one chunk of frames
 
@@ -965,6 +970,16 @@ def batch_chunks(n, H, W, level, budget=None, max_frames=BATCH_MAX_FRAMES, extra
     frame = batch_frame_bytes(H, W, level, itemsize) + int(extra_planes) * H * _batch_pitch(W, itemsize) * itemsize
     per = max(1, min(int(budget // frame), int(max_frames)))
     return [(f0, min(per, n - f0)) for f0 in range(0, n, per)]
+
+
+def _enhance_rows(nf, taus, wgts):
+    """(n_den, thresholds, weights) of BatchPlan.enhance_sum / BatchPlan64.enhance_sum: nf rows of n_den doubles each"""
+    n = len(taus[0]) if len(taus) else 0
+    if len(taus) != nf or len(wgts) != nf or n < 1 or any(len(t) != n for t in taus) or any(len(w) != n for w in wgts):
+        raise ValueError("enhance_sum: one row of n_den >= 1 thresholds and one of n_den weights per frame")
+    ta = (_c.c_double * (nf * n))(*[float(t) for row in taus for t in row])
+    wa = (_c.c_double * (nf * n))(*[float(w) for row in wgts for w in row])
+    return n, ta, wa
 
 
 class BatchPlan:
@@ -1044,6 +1059,11 @@ class BatchPlan:
         ta = (_c.c_double * max(nf * n, 1))(*[float(t) for row in taus for t in row])
         wa = (_c.c_double * max(n, 1))(*[float(w) for w in wgts])
         check(load().wt_batch_denoise_sum(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back)))
+
+    def enhance_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT):
+        """denoise_sum with one row of weights per active frame as well (utils.enhance: a colour image's channels
+        are frames with their own sigmas and weights); all rows of one length n_den >= 1"""
+        check(load().wt_batch_enhance_sum(self._h, nf, count, dst, *_enhance_rows(nf, taus, wgts), int(soft), int(write_back)))
 
     def anscombe(self, nf, src, dst, alpha=1.0, g=0.0, sigma=0.0, inverse=False):
         check(load().wt_batch_anscombe(self._h, nf, src, dst, alpha, g, sigma, int(inverse)))
@@ -1178,6 +1198,11 @@ class BatchPlan64:
         ta = (_c.c_double * max(nf * n, 1))(*[float(t) for row in taus for t in row])
         wa = (_c.c_double * max(n, 1))(*[float(w) for w in wgts])
         check(load().wt_batch64_denoise_sum(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back)))
+
+    def enhance_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT):
+        """denoise_sum with one row of weights per active frame as well (utils.enhance: a colour image's channels
+        are frames with their own sigmas and weights); all rows of one length n_den >= 1"""
+        check(load().wt_batch64_enhance_sum(self._h, nf, count, dst, *_enhance_rows(nf, taus, wgts), int(soft), int(write_back)))
 
     def anscombe(self, nf, src, dst, alpha=1.0, g=0.0, sigma=0.0, inverse=False):
         check(load().wt_batch64_anscombe(self._h, nf, src, dst, alpha, g, sigma, int(inverse)))

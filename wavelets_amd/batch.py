@@ -5,6 +5,7 @@ back in one host round trip, and the pointwise steps run once over the stack.
     transform_stack(frames, level)      == np.stack([AtrousTransform(sf)(f, level).data for f in frames])
     denoise_stack(frames, weights)      == np.stack([denoise(f, weights, sf, noise_i, ...) for f in frames])
     wow_stack(frames, ...)              == np.stack([wow(f, ..., noise=noise_i, ...)[0] for f in frames])
+    enhance_stack(frames, [noise,] ...) == np.stack([enhance(f, [noise_i,] ...) for f in frames])   (gray or colour frames)
 
 bit for bit.  The sequence of operations per frame is the per-frame path's own (wavelets._interleave_split,
 _tau_row, _noise_from_median, _sigma_bilateral_list; utils._wow_lists, _wow_factor, _gamma_range,
@@ -19,11 +20,11 @@ from . import _lib
 from ._lib import PLANE_INPUT, PLANE_OUT, PLANE_NONE, PLANE_SCRATCH, FLAG_FUSED
 from .wavelets import (AtrousTransform, B3spline, _family_of, _needs_generic, _interleave_split, _tau_row,
                        _noise_from_median, _sigma_bilateral_list, _result_dtype)
-from .utils import (denoise, wow, _GAMMA_PLANE, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments,
+from .utils import (denoise, wow, enhance, _enhance_lists, _GAMMA_PLANE, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments,
                     _wow_factor, _gamma_range, _wow_sigma_bilateral)
 
-__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'batch_eligible', 'batch64_eligible', 'wow_eligible',
-           'bilateral_eligible']
+__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'enhance_stack', 'batch_eligible', 'batch64_eligible',
+           'wow_eligible', 'bilateral_eligible', 'enhance_eligible']
 
 # levels whose fused schedule has a kernel for every pass (wt_plan_fused_ok), both built-in families: L = 1 is
 # a single-scale pass, and from 9 scales on the schedules hold single-scale passes at D >= 256 (wt_fused_has_pass)
@@ -447,3 +448,183 @@ def _wow_batch_device(bp, nf, noises, scaling_function, n_scales, weights, white
         need = gamma_min is None or gamma_max is None
         bounds = [_gamma_range(gamma_min, gamma_max, m) for m in (bp.reduce(nf, _GAMMA_PLANE) if need else [None] * nf)]
         bp.gamma_blend(nf, PLANE_OUT, _GAMMA_PLANE, [b[0] for b in bounds], [b[1] for b in bounds], 1 / gamma, h)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# enhance over stacks of gray or colour frames (utils.enhance, ref utils.py:36-80)
+# ---------------------------------------------------------------------------------------------------------------
+ENHANCE_LEVELS = range(1, _lib.MAX_SUM_PLANES)      # level + 1 planes in one launch of the thresholded weighted sum
+
+
+# float64 groups of at most this many frames of at least this many pixels run the per-frame loop: measured
+# (tools/bench_enhance_stack.py, 1 x 3 x 2048^2 float64, device-resident) the batch is 5 % behind the loop there
+ENHANCE64_FEW_FRAMES, ENHANCE64_LARGE_PIXELS = 3, 1 << 22
+
+
+def enhance_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=(), channels=1):
+    """The route one group of enhance_stack takes (host logic) - the frames and channels of one level, `frames` their
+    (n, H, W) stack, `noise_per_frame` their given noise levels (empty: none given, every frame its MAD estimate):
+    'batch64' (batch64_eligible: the float64 batch), 'bilateral' (bilateral_eligible: the float32 batch behind the
+    batched bilateral march), 'batch' (the float32 batch: _engine_eligible frames, the fused passes or, where the
+    schedule has none, the batched per-scale stencil), or None: the per-frame loop of utils.enhance.  The existing
+    predicates decide; on top of them 1 <= level <= 15 (level + 1 planes in one launch of the sum) and given noise
+    levels that are scalars - no None (utils.enhance would estimate that one lazily), no array (a noise map).
+    `channels`: the channels of every frame that the group holds (its batch has len(frames) * channels frames); a
+    float64 group of at most ENHANCE64_FEW_FRAMES frames of ENHANCE64_LARGE_PIXELS pixels or more goes to the loop."""
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level not in ENHANCE_LEVELS:
+        return None
+    if noise_per_frame is None or any(n is None or type(n) is np.ndarray for n in noise_per_frame):
+        return None
+    if batch64_eligible(frames, level, scaling_function, bilateral, noise_per_frame):
+        few = len(frames) * channels <= ENHANCE64_FEW_FRAMES
+        return None if few and frames.shape[1] * frames.shape[2] >= ENHANCE64_LARGE_PIXELS else 'batch64'
+    if bilateral_eligible(frames, level, scaling_function, bilateral, noise_per_frame):
+        return 'bilateral'
+    if bilateral is None and _engine_eligible(frames, scaling_function, None, noise_per_frame):
+        return 'batch'
+    return None
+
+
+def _as_enhance_frames(frames):
+    """(frames, colour): an (N, H, W) or (N, 3, H, W) array - as given, or stacked from a sequence of 2-D or
+    (3, H, W) frames of one shape and element type (mixed element types: the list, for the per-frame loop)"""
+    if isinstance(frames, np.ndarray):
+        fr = frames
+    else:
+        fr = [np.asarray(f) for f in frames]
+        if len({f.shape for f in fr}) > 1:
+            raise ValueError(f"frames: all frames must have one shape (got {sorted({f.shape for f in fr})})")
+        if len({f.dtype for f in fr}) == 1:
+            fr = np.stack(fr)
+    if len(fr) == 0:
+        raise ValueError("frames: an empty stack")
+    shape = fr[0].shape
+    if len(shape) == 2:
+        return fr, False
+    if len(shape) == 3 and shape[0] == 3:
+        return fr, True
+    raise ValueError(f"frames: (N, H, W) gray or (N, 3, H, W) colour frames (got frames of shape {shape})")
+
+
+def _enhance_noise(noise, n, colour):
+    """enhance_stack's `noise` as one entry per frame - what frame i's utils.enhance call gets as its second
+    argument - or None when no noise is given.  Gray stacks: denoise_stack's forms (a scalar, one entry per frame;
+    a noise map goes to every frame).  Colour stacks: three entries (the reference's args[1][c], shared by the
+    frames) or an (N, 3) array / nested sequence (frame i gets noise[i]); with two more axes, noise maps."""
+    if noise is None:
+        return None
+    if not colour:
+        per = _noise_list(noise, n)
+        return [noise] * n if per is None else per
+    nd = np.ndim(noise)
+    if nd in (1, 3) and len(noise) == 3:
+        return [noise] * n
+    if nd in (2, 4) and len(noise) == n and all(len(row) == 3 for row in noise):
+        return [noise[i] for i in range(n)]
+    raise ValueError(f"noise: three entries (one per channel) or an ({n}, 3) array for a stack of {n} colour frames")
+
+
+def _enhance_groups(plans):
+    """{level: [channel, ...]} of utils._enhance_lists' (channel, sigmas, weights): a channel's level is
+    len(weights) (ref:70); the frames and channels of one level run as one batch"""
+    groups = {}
+    for c, _, wgt in plans:
+        groups.setdefault(len(wgt), []).append(c)
+    return groups
+
+
+def enhance_stack(frames, noise=None, *, weights=None, denoise=None, soft_threshold=True, out=None, **kwargs):
+    """(N, H, W) for gray frames, (N, 3, H, W) for colour frames (channel axis first, as the reference indexes
+    img[c]): utils.enhance of every frame (ref utils.py:36-80), batched - result[i] equals
+    enhance(frames[i], [noise_i,] weights=weights, denoise=denoise, soft_threshold=soft_threshold, **kwargs) bit
+    for bit, float32 or, for the stacks the reference computes in float64, float64.  `noise`: None (every frame and
+    channel its own MAD estimate); gray: a scalar or one per frame; colour: three entries (per channel) or (N, 3).
+    kwargs go to AtrousTransform (scaling_function_class, bilateral, bilateral_scaling).
+
+    Per chunk: upload, transform, the MAD medians of all frames in one round trip (whenever no noise is given, as
+    enhance calls get_noise()), one threshold row and one weight row per frame, the thresholded weighted sum of
+    all planes in one launch (wt_batch_enhance_sum), download.  The channels of one level are frames of one batch;
+    channels of different levels run one batch each (enhance_eligible: the route, or the per-frame loop)."""
+    fr, colour = _as_enhance_frames(frames)
+    N = len(fr)
+    per = _enhance_noise(noise, N, colour)
+    atrous = AtrousTransform(**kwargs)
+    sfc, bilateral = atrous.scaling_function_class, atrous.bilateral
+    # the parameter lists depend on the call's arguments only: once per stack
+    plans = _enhance_lists(3 if colour else 2, weights, denoise)
+    groups = _enhance_groups(plans)
+    routes = {}
+    if isinstance(fr, np.ndarray):
+        for level, chans in groups.items():
+            given = () if per is None else [p if c is Ellipsis else p[c] for p in per for c in chans]
+            routes[level] = enhance_eligible(fr if not colour else fr[:, 0], level, sfc, bilateral, given, len(chans))
+    if not routes or any(r is None for r in routes.values()):
+        kw = dict(weights=weights, denoise=denoise, soft_threshold=soft_threshold, **kwargs)
+        res = np.stack([enhance(f, **kw) if per is None else enhance(f, n_i, **kw) for f, n_i in zip(fr, per or [None] * N)])
+        return _hand_over(res, out)
+    f64 = 'batch64' in routes.values()                     # (one element type: every group takes the same engine)
+    fill = None
+    if f64:
+        res, fill = _f64_target(out, fr.shape)
+    else:
+        res = _f32_target(out, fr.shape)
+    for level, chans in groups.items():
+        _enhance_group(fr, res, per, [p for p in plans if p[0] in chans], level, routes[level], atrous, soft_threshold)
+    if fill is not None:
+        fill[...] = res
+        return fill
+    return res
+
+
+def _enhance_group(fr, res, per, plans, level, route, atrous, soft_threshold):
+    """One group of enhance_stack on a BatchPlan / BatchPlan64: the channels `plans` (utils._enhance_lists' entries
+    of one level) of every frame of `fr`, results into `res`.  A chunk holds m images = m * len(plans) batch
+    frames: image-major (frame i, channel c at i * 3 + c) when the group is all three channels of a C-contiguous
+    stack - one upload and one download per chunk - else channel-major (channel j's frames at j * m ...)."""
+    f64 = route == 'batch64'
+    bil = route == 'bilateral'
+    N = len(fr)
+    H, W = fr.shape[-2:]
+    k = len(plans)
+    sf = atrous.scaling_function_class(2)
+    fam = _family_of(sf)
+    sigma_e = sf.sigma_e(bilateral=atrous.bilateral if bil else None)
+    # ref:76 per channel: Coefficients.denoise's zip over (scale, sigma, weight), padded to the level's rows with
+    # sigma 0 / weight 1 (a plane times 1.0: the plane) when a shared list has grown past a channel's own
+    entries = [list(zip(range(level + 1), dns, wgt)) for _, dns, wgt in plans]
+    entries = [e + [(s, 0, 1) for s in range(len(e), level)] for e in entries]
+    wrows = [[w for _, _, w in e] for e in entries]
+    whole = k == 3 and fr.flags.c_contiguous and res.flags.c_contiguous
+    frames_max = _lib.batch_chunks(N * k, H, W, level, itemsize=8 if f64 else 4)[0][1]
+    m = max(1, frames_max // k)                                      # images per chunk
+    acquire, release = (_lib.acquire_batch64, _lib.release_batch64) if f64 else (_lib.acquire_batch, _lib.release_batch)
+    bp = acquire(_lib.default_context(), min(m, N) * k, H, W, fam, level)
+    try:
+        for i0 in range(0, N, m):
+            n = min(m, N - i0)
+            nf = n * k
+            # (batch frame -> (image, index into plans))
+            order = [(i, j) for i in range(n) for j in range(k)] if whole else [(i, j) for j in range(k) for i in range(n)]
+            if whole:
+                bp.upload(PLANE_INPUT, fr[i0:i0 + n].reshape(nf, H, W))
+            else:
+                for j, (c, _, _) in enumerate(plans):
+                    bp.upload(PLANE_INPUT, fr[i0:i0 + n] if c is Ellipsis else fr[i0:i0 + n, c], f0=j * n)
+            if bil:                                                      # ref:70, AtrousTransform._run
+                sb = _sigma_bilateral_list(atrous.bilateral, level)
+                bp.decompose_bilateral(nf, PLANE_INPUT, level, sb, atrous.bilateral_scaling)
+            else:
+                bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
+            if per is None:                                              # ref:74: get_noise(), eagerly
+                noises = [_noise_from_median(md, sigma_e) for md in bp.abs_median(nf, 0)]
+            else:                                                        # ref:72
+                noises = [per[i0 + i] if plans[j][0] is Ellipsis else per[i0 + i][plans[j][0]] for i, j in order]
+            taus = [_tau_row(entries[j], nz, sigma_e, soft_threshold) for (_, j), nz in zip(order, noises)]
+            bp.enhance_sum(nf, level + 1, taus, [wrows[j] for _, j in order], soft_threshold)   # ref:76-78
+            if whole:
+                bp.download(PLANE_OUT, nf, out=res[i0:i0 + n].reshape(nf, H, W))
+            else:
+                for j, (c, _, _) in enumerate(plans):
+                    bp.download(PLANE_OUT, n, out=res[i0:i0 + n] if c is Ellipsis else res[i0:i0 + n, c], f0=j * n)
+    finally:
+        release(bp)

@@ -42,7 +42,7 @@ struct wt_batch {
     uint32_t *d_hist = nullptr;     // [n][2 ranks][WT_HIST_BINS]
     WtBatchSel *d_sel = nullptr;    // [n][2 ranks]
     WtBatchSel *h_sel = nullptr;    // pinned copy
-    double *d_tau = nullptr;        // [n][WT_MAX_SUM_PLANES] thresholds of wt_batch_denoise_sum
+    double *d_tau = nullptr;        // [n][2 * WT_MAX_SUM_PLANES]: thresholds of wt_batch_denoise_sum; wt_batch_enhance_sum: then the weights
     double *h_tau = nullptr;        // pinned staging of the table
     // wow: WT_PLANE_SCRATCH(3) = the output plane of wt_batch_wow_scale (swapped with the coefficient plane, as
     // wt_wow_scale does), WT_PLANE_SCRATCH(4) = the gamma accumulator (utils.wow's plane ids)
@@ -161,6 +161,41 @@ __global__ __launch_bounds__(256) void wt_batch_denoise_sum_kernel(BatchDenoiseA
                 for (int j = 0; j < 4; ++j) {
                     const float sgn = t > 0.0 ? wt_sig(c[j], tauf * nn[j], t * (double)nn[j], a.soft) : 1.f;
                     c[j] = c[j] * (a.wgt[k] * sgn);
+                }
+                if (a.write_back) reinterpret_cast<float4 *>(a.p[k])[i] = make_float4(c[0], c[1], c[2], c[3]);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = k == 0 ? c[j] : acc[j] + c[j];
+        }
+        reinterpret_cast<float4 *>(out)[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    }
+}
+
+// wt_batch_denoise_sum_kernel with one WEIGHT row per frame as well (utils.enhance per channel, watroo/utils.py:60-78):
+// tab[frame * 2 * n_den + k] = tau, tab[frame * 2 * n_den + n_den + k] = the weight (a double, rounded to float here as
+// wt_denoise_sum rounds it on the host), the frame from the flat index.  Same arithmetic, contraction off: the bits of
+// the per-frame call.
+struct BatchEnhanceArgs {
+    float *p[WT_MAX_SUM_PLANES];
+    int n, n_den, soft, write_back;
+};
+__global__ __launch_bounds__(256) void wt_batch_enhance_sum_kernel(BatchEnhanceArgs a, const double *tab, float *out, int64_t n4, int64_t f4)
+{
+#pragma clang fp contract(off)
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const double *ft = tab + (i / f4) * 2 * a.n_den;
+        const float nn[4] = {1.f, 1.f, 1.f, 1.f};
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < a.n; ++k) {
+            const float4 v = reinterpret_cast<const float4 *>(a.p[k])[i];
+            float c[4] = {v.x, v.y, v.z, v.w};
+            if (k < a.n_den) {
+                const double t = ft[k];
+                const float tauf = (float)t, wgt = (float)ft[a.n_den + k];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float sgn = t > 0.0 ? wt_sig(c[j], tauf * nn[j], t * (double)nn[j], a.soft) : 1.f;
+                    c[j] = c[j] * (wgt * sgn);
                 }
                 if (a.write_back) reinterpret_cast<float4 *>(a.p[k])[i] = make_float4(c[0], c[1], c[2], c[3]);
             }
@@ -409,9 +444,9 @@ extern "C" int wt_batch_create(wt_ctx *ctx, int n, int H, int W, int family, int
     };
     hipError_t e = hipMalloc((void **)&b->d_hist, (size_t)n * 2 * WT_HIST_BINS * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_sel, (size_t)n * 2 * sizeof(WtBatchSel));
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_tau, (size_t)n * WT_MAX_SUM_PLANES * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_tau, (size_t)n * 2 * WT_MAX_SUM_PLANES * sizeof(double));
     if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_sel, (size_t)n * 2 * sizeof(WtBatchSel), 0);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_tau, (size_t)n * WT_MAX_SUM_PLANES * sizeof(double), 0);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_tau, (size_t)n * 2 * WT_MAX_SUM_PLANES * sizeof(double), 0);
     if (e == hipSuccess) e = hipMemsetAsync(b->d_hist, 0, (size_t)n * 2 * WT_HIST_BINS * sizeof(uint32_t), ctx->stream);
     if (e != hipSuccess) return fail(e);
     *out = b;
@@ -663,6 +698,38 @@ extern "C" int wt_batch_denoise_sum(wt_batch *b, int nf, int count, int dst, int
     const int64_t n4 = (int64_t)nf * b->fstride / 4;
     ProfScope ps(b->ctx, "wt_batch_denoise_sum_kernel");
     hipLaunchKernelGGL(wt_batch_denoise_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, b->ctx->stream, a, (const double *)b->d_tau,
+                       o, n4, b->fstride / 4);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch_enhance_sum(wt_batch *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
+                                    int write_back)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_enhance_sum"));
+    WtGuard guard_(b->ctx);
+    if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > b->max_level)
+        WT_FAIL("wt_batch_enhance_sum: count %d out of range [1,%d]", count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
+    if (n_den < 1 || n_den > count) WT_FAIL("wt_batch_enhance_sum: n_den %d outside [1,%d]", n_den, count);
+    if (!tau || !wgt) WT_FAIL("wt_batch_enhance_sum: null tau/wgt");
+    if (dst >= 0 && dst < count) WT_FAIL("wt_batch_enhance_sum: dst plane %d is one of the summed planes", dst);
+    BatchEnhanceArgs a{};
+    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
+    for (int i = 0; i < count; ++i) WT_TRY(bplane(b, i, &a.p[i]));
+    float *o = nullptr;
+    WT_TRY(bplane(b, dst, &o));
+    // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
+    WT_HIP(hipStreamSynchronize(b->ctx->stream));
+    const int row = 2 * n_den;                              // nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables
+    for (int f = 0; f < nf; ++f)
+        for (int k = 0; k < n_den; ++k) {
+            b->h_tau[f * row + k] = tau[f * n_den + k];
+            b->h_tau[f * row + n_den + k] = wgt[f * n_den + k];
+        }
+    WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * row * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    const int64_t n4 = (int64_t)nf * b->fstride / 4;
+    ProfScope ps(b->ctx, "wt_batch_enhance_sum_kernel");
+    hipLaunchKernelGGL(wt_batch_enhance_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, b->ctx->stream, a, (const double *)b->d_tau,
                        o, n4, b->fstride / 4);
     WT_HIP(hipGetLastError());
     return 0;

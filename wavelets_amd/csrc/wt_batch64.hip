@@ -42,7 +42,7 @@ struct wt_batch64 {
     uint32_t *d_hist = nullptr;     // [n][2 ranks][WT_HIST_BINS] (allocated by the first median)
     WtBatch64Sel *d_sel = nullptr;  // [n][2 ranks]
     WtBatch64Sel *h_sel = nullptr;  // pinned copy
-    double *d_tau = nullptr;        // [n][2 * WT_MAX_SUM_PLANES]: the thresholds of wt_batch64_denoise_sum, then 1 / tau
+    double *d_tau = nullptr;        // [n][3 * WT_MAX_SUM_PLANES]: the thresholds of wt_batch64_denoise_sum, then 1 / tau; wt_batch64_enhance_sum: then the weights
     double *h_tau = nullptr;        // pinned staging of the table
 };
 
@@ -144,6 +144,34 @@ __global__ __launch_bounds__(256) void wt_batch64_denoise_sum_kernel(Batch64Deno
                 double2 sg = make_double2(1.0, 1.0);
                 if (tau > 0.0) sg = make_double2(wt_sig64_inv(v.x, tau, inv_tau, a.soft), wt_sig64_inv(v.y, tau, inv_tau, a.soft));
                 v = make_double2(v.x * (a.wgt[k] * sg.x), v.y * (a.wgt[k] * sg.y));
+                if (a.write_back) reinterpret_cast<double2 *>(a.p[k])[i] = v;
+            }
+            acc = k == 0 ? v : make_double2(acc.x + v.x, acc.y + v.y);
+        }
+        __builtin_nontemporal_store((wt_b64_ntd2){acc.x, acc.y}, reinterpret_cast<wt_b64_ntd2 *>(dst) + i);
+    }
+}
+
+// wt_batch64_denoise_sum_kernel with one WEIGHT row per frame as well (utils.enhance per channel, watroo/utils.py:60-78):
+// tab[frame * 3 * n_den + k] = tau, [+ n_den + k] = 1 / tau (the host's IEEE division), [+ 2 * n_den + k] = the weight.
+// Same expressions and accesses: the bits of the per-frame call.
+struct Batch64EnhanceArgs {
+    double *p[WT_MAX_SUM_PLANES];
+    int n, n_den, soft, write_back;
+};
+__global__ __launch_bounds__(256) void wt_batch64_enhance_sum_kernel(Batch64EnhanceArgs a, const double *tab, double *dst, int64_t n2, int64_t f2)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (int64_t)gridDim.x * 256) {
+        const double *ft = tab + (i / f2) * 3 * a.n_den;
+        double2 acc = make_double2(0.0, 0.0);
+        for (int k = 0; k < a.n; ++k) {
+            const wt_b64_ntd2 raw = __builtin_nontemporal_load(reinterpret_cast<const wt_b64_ntd2 *>(a.p[k]) + i);   // (read exactly once)
+            double2 v = make_double2(raw.x, raw.y);
+            if (k < a.n_den) {
+                const double tau = ft[k], inv_tau = ft[a.n_den + k], wgt = ft[2 * a.n_den + k];
+                double2 sg = make_double2(1.0, 1.0);
+                if (tau > 0.0) sg = make_double2(wt_sig64_inv(v.x, tau, inv_tau, a.soft), wt_sig64_inv(v.y, tau, inv_tau, a.soft));
+                v = make_double2(v.x * (wgt * sg.x), v.y * (wgt * sg.y));
                 if (a.write_back) reinterpret_cast<double2 *>(a.p[k])[i] = v;
             }
             acc = k == 0 ? v : make_double2(acc.x + v.x, acc.y + v.y);
@@ -339,9 +367,9 @@ extern "C" int wt_batch64_create(wt_ctx *ctx, int n, int H, int W, int family, i
     b->fstride = (int64_t)H * b->geo.g.P;
     b->coef.assign(max_level + 1, nullptr);
     hipError_t e = hipMalloc((void **)&b->d_sel, (size_t)n * 2 * sizeof(WtBatch64Sel));
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_tau, (size_t)n * 2 * WT_MAX_SUM_PLANES * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_tau, (size_t)n * 3 * WT_MAX_SUM_PLANES * sizeof(double));
     if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_sel, (size_t)n * 2 * sizeof(WtBatch64Sel), 0);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_tau, (size_t)n * 2 * WT_MAX_SUM_PLANES * sizeof(double), 0);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_tau, (size_t)n * 3 * WT_MAX_SUM_PLANES * sizeof(double), 0);
     if (e != hipSuccess) {
         int bad = 0;
         batch64_free(b, &bad);
@@ -618,6 +646,40 @@ extern "C" int wt_batch64_denoise_sum(wt_batch64 *b, int nf, int count, int dst,
     const int64_t n2 = (int64_t)nf * b->fstride / 2;
     ProfScope ps(b->ctx, "wt_batch64_denoise_sum_kernel");
     hipLaunchKernelGGL(wt_batch64_denoise_sum_kernel, dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8)), dim3(256), 0,
+                       b->ctx->stream, a, (const double *)b->d_tau, o, n2, b->fstride / 2);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch64_enhance_sum(wt_batch64 *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
+                                      int write_back)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_enhance_sum"));
+    WtGuard guard_(b->ctx);
+    if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > b->max_level)
+        WT_FAIL("wt_batch64_enhance_sum: count %d out of range [1,%d]", count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
+    if (n_den < 1 || n_den > count) WT_FAIL("wt_batch64_enhance_sum: n_den %d outside [1,%d]", n_den, count);
+    if (!tau || !wgt) WT_FAIL("wt_batch64_enhance_sum: null tau/wgt");
+    if (dst >= 0 && dst < count) WT_FAIL("wt_batch64_enhance_sum: dst plane %d is one of the summed planes", dst);
+    Batch64EnhanceArgs a{};
+    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
+    for (int i = 0; i < count; ++i) WT_TRY(b64plane(b, i, &a.p[i]));
+    double *o = nullptr;
+    WT_TRY(b64plane(b, dst, &o));
+    // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
+    WT_HIP(hipStreamSynchronize(b->ctx->stream));
+    const int row = 3 * n_den;                              // nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables
+    for (int f = 0; f < nf; ++f)
+        for (int k = 0; k < n_den; ++k) {
+            const double t = tau[f * n_den + k];
+            b->h_tau[f * row + k] = t;
+            b->h_tau[f * row + n_den + k] = t > 0.0 ? 1.0 / t : 0.0;       // (wt64_denoise_sum's inv_tau)
+            b->h_tau[f * row + 2 * n_den + k] = wgt[f * n_den + k];
+        }
+    WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * row * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    const int64_t n2 = (int64_t)nf * b->fstride / 2;
+    ProfScope ps(b->ctx, "wt_batch64_enhance_sum_kernel");
+    hipLaunchKernelGGL(wt_batch64_enhance_sum_kernel, dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8)), dim3(256), 0,
                        b->ctx->stream, a, (const double *)b->d_tau, o, n2, b->fstride / 2);
     WT_HIP(hipGetLastError());
     return 0;

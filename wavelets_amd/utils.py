@@ -46,18 +46,15 @@ def prepare_params(param, ndims):
     return out
 
 
-def enhance(*args, weights=None, denoise=None, soft_threshold=True, out=None, **kwargs):
-    """De-noising and / or enhancement by modification of the wavelet coefficients, per channel
-    for (3, H, W) images (ref:36-80): transform over ``len(weights)`` scales, threshold with
-    ``denoise`` sigmas, recombine with ``weights``.  ``args = (img[, noise])``; ``kwargs`` go to
-    ``AtrousTransform``."""
-    img = np.asarray(args[0])
-    channels = [0, 1, 2] if img.ndim == 3 else [Ellipsis]                 # ref:47-50
-    if out is None:
-        out = _lib.host_empty(img.shape, dtype=_result_dtype(img))
-    weights = prepare_params(weights, img.ndim)
-    denoise = prepare_params(denoise, img.ndim)
-    atrous = AtrousTransform(**kwargs)
+def _enhance_lists(ndim, weights, denoise):
+    """[(channel, sigmas, weights)] of enhance() for an image of `ndim` dimensions - one entry with channel
+    Ellipsis for a 2-D image, channels 0, 1, 2 for a colour image: prepare_params (ref:55-56), then the
+    reference's padding of the shorter list (ref:60-68), in its order and on its lists.  A scalar parameter of a
+    colour image is ONE list shared by the three channels ([[param], ] * ndims, ref:23), so a channel's padding
+    is seen by the others; the lists are handed out as they stand once every channel has been padded."""
+    channels = [0, 1, 2] if ndim == 3 else [Ellipsis]                     # ref:47-50
+    weights = prepare_params(weights, ndim)
+    denoise = prepare_params(denoise, ndim)
     plans = []
     for c in channels:                                                    # the reference's list plumbing, in its order
         dns = denoise if c is Ellipsis else denoise[c]
@@ -67,6 +64,19 @@ def enhance(*args, weights=None, denoise=None, soft_threshold=True, out=None, **
         elif len(dns) < len(wgt):
             dns.extend([0] * (len(wgt) - len(dns)))
         plans.append((c, dns, wgt))
+    return plans
+
+
+def enhance(*args, weights=None, denoise=None, soft_threshold=True, out=None, **kwargs):
+    """De-noising and / or enhancement by modification of the wavelet coefficients, per channel
+    for (3, H, W) images (ref:36-80): transform over ``len(weights)`` scales, threshold with
+    ``denoise`` sigmas, recombine with ``weights``.  ``args = (img[, noise])``; ``kwargs`` go to
+    ``AtrousTransform``."""
+    img = np.asarray(args[0])
+    if out is None:
+        out = _lib.host_empty(img.shape, dtype=_result_dtype(img))
+    plans = _enhance_lists(img.ndim, weights, denoise)
+    atrous = AtrousTransform(**kwargs)
 
     def channel(item):
         c, dns, wgt = item
