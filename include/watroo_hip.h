@@ -686,6 +686,17 @@ int wt_batch64_upload_elems(wt_batch64 *batch, int plane, int f0, int nf, const 
 int wt_batch64_plane_ptr(wt_batch64 *batch, int plane, void **ptr, int64_t *frame_stride);
 /* wt64_decompose per frame (watroo/wavelets.py:408-444 via AtrousTransform.__call__, ref:307-328); flags bit0 */
 int wt_batch64_decompose(wt_batch64 *batch, int nf, int src, int level, int flags);
+/* host logic: *ok = 1 when an H x W frame of `family` takes the float64 bilateral march per frame
+ * (wt64_decompose_bilateral, watroo/wavelets.py:433-442, with built-in taps: option "stencil64" on, an image of
+ * H >= 2 rows that wt_batch64_create accepts) and 1 <= level <= 25 - the frames wt_batch64_decompose_bilateral
+ * reproduces bit for bit; with the option off the per-frame call runs three generic kernels per scale */
+int wt_batch64_bilateral_ok(int family, int64_t H, int64_t W, int level, int *ok);
+/* wt64_decompose_bilateral per frame (watroo/wavelets.py:433-442: the range-weighted branch of atrous on float64 /
+ * recast input, :297, 319-320; variance of :434-436 formed in the march): scale s reads the current smooth plane,
+ * writes c_{s+1} to a scratch plane (planes WT_PLANE_SCRATCH(0/1) ping-pong; plane `level` on the last scale) and
+ * w_s to plane s.  One launch per scale for all active frames.  sigma_b: `level` entries.  flags: reserved */
+int wt_batch64_decompose_bilateral(wt_batch64 *batch, int nf, int src, int level, const double *sigma_b,
+                                   int bilateral_scaling, int flags);
 /* wt64_decompose_sum per frame: planes + np.sum(planes, axis=0) (watroo/utils.py:98) in the same passes */
 int wt_batch64_decompose_sum(wt_batch64 *batch, int nf, int src, int level, int dst, int flags);
 /* wt64_decompose_pass / wt64_decompose_pass_sum per frame (utils.denoise, watroo/utils.py:95-98, interleaved) */

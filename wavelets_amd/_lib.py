@@ -235,6 +235,9 @@ SIGNATURES = {
     "wt_batch64_upload_elems": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_int]),
     "wt_batch64_plane_ptr": (_c.c_int, [_vp, _c.c_int, _c.POINTER(_vp), _c.POINTER(_i64)]),
     "wt_batch64_decompose": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch64_bilateral_ok": (_c.c_int, [_c.c_int, _i64, _i64, _c.c_int, _c.POINTER(_c.c_int)]),
+    "wt_batch64_decompose_bilateral": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
+                                                  _c.c_int, _c.c_int]),
     "wt_batch64_decompose_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "wt_batch64_decompose_pass": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "wt_batch64_decompose_pass_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
@@ -1117,6 +1120,15 @@ def batch64_fused_ok(family, H, W, level):
     return bool(ok.value)
 
 
+def batch64_bilateral_ok(family, H, W, level):
+    """True when H x W frames of `family` take the float64 bilateral march per frame and `level` is one of its 1..25
+    scales (host logic, wt_batch64_bilateral_ok: Plan64.decompose_bilateral's built-in route, option "stencil64"
+    included) - the frames BatchPlan64.decompose_bilateral reproduces bit for bit"""
+    ok = _c.c_int(0)
+    check(load().wt_batch64_bilateral_ok(int(family), int(H), int(W), int(level), _c.byref(ok)))
+    return bool(ok.value)
+
+
 class BatchPlan64:
     """Double-precision planes of up to `n` frames of one H x W shape (wt_batch64): BatchPlan's operations for the
     stacks the reference computes in float64.  upload / download move a C-contiguous (nf, H, W) block; integer
@@ -1174,6 +1186,11 @@ class BatchPlan64:
 
     def decompose(self, nf, src, level, flags=FLAG_FUSED):
         check(load().wt_batch64_decompose(self._h, nf, src, level, flags))
+
+    def decompose_bilateral(self, nf, src, level, sigma_b, bilateral_scaling=False, flags=0):
+        """Plan64.decompose_bilateral for frames 0 .. nf-1: one launch of the batched float64 march per scale"""
+        arr = (_c.c_double * max(level, 1))(*[float(v) for v in sigma_b[:level]])
+        check(load().wt_batch64_decompose_bilateral(self._h, nf, src, level, arr, int(bilateral_scaling), flags))
 
     def decompose_sum(self, nf, src, level, dst=PLANE_OUT, flags=FLAG_FUSED):
         check(load().wt_batch64_decompose_sum(self._h, nf, src, level, dst, flags))

@@ -12,8 +12,9 @@ _tau_row, _noise_from_median, _sigma_bilateral_list; utils._wow_lists, _wow_fact
 _wow_sigma_bilateral).  With bilateral= the transform is the batched bilateral march (one launch per scale for
 all frames, bilateral_eligible).  Stacks the reference
 computes in float64 (float64 frames; int16 .. int64 and big-endian frames, which it recasts) run transform_stack
-and denoise_stack on the float64 batch (wt_batch64, batch64_eligible).  Inputs the batched engines do not cover
-run the per-frame loop (batch_eligible / batch64_eligible / wow_eligible / bilateral_eligible say which)."""
+and denoise_stack on the float64 batch (wt_batch64, batch64_eligible), with bilateral= behind the batched float64
+march (bilateral64_eligible).  Inputs the batched engines do not cover run the per-frame loop (batch_eligible /
+batch64_eligible / wow_eligible / bilateral_eligible / bilateral64_eligible say which)."""
 import numpy as np
 
 from . import _lib
@@ -24,7 +25,7 @@ from .utils import (denoise, wow, enhance, _enhance_lists, _GAMMA_PLANE, _wow_n_
                     _wow_factor, _gamma_range, _wow_sigma_bilateral)
 
 __all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'enhance_stack', 'batch_eligible', 'batch64_eligible',
-           'wow_eligible', 'bilateral_eligible', 'enhance_eligible']
+           'wow_eligible', 'bilateral_eligible', 'bilateral64_eligible', 'enhance_eligible']
 
 # levels whose fused schedule has a kernel for every pass (wt_plan_fused_ok), both built-in families: L = 1 is
 # a single-scale pass, and from 9 scales on the schedules hold single-scale passes at D >= 256 (wt_fused_has_pass)
@@ -103,16 +104,27 @@ def bilateral_eligible(frames, level, scaling_function=B3spline, bilateral=None,
     arrays), `bilateral` a real scalar / bool or a list of them, and 1 <= level <= what wt_decompose_bilateral
     (25) and the family's sigma_e(bilateral=...) table admit.  False without bilateral filtering: those stacks are
     batch_eligible's / wow_eligible's.  Everything else runs the per-frame loop."""
+    if not _bilateral_call_eligible(level, bilateral, noise_per_frame):
+        return False
+    if not _engine_eligible(frames, scaling_function, None, noise_per_frame):
+        return False
+    return _bilateral_level_eligible(level, scaling_function, bilateral)
+
+
+def _bilateral_call_eligible(level, bilateral, noise_per_frame):
+    """the conditions of bilateral_eligible / bilateral64_eligible on the call alone: `bilateral` a real scalar /
+    bool or a list of them, an int level >= 1, no noise level that is an array (utils.wow takes a 0-d array as a map)"""
     if bilateral is None:
         return False
     if not (_real_scalar(bilateral) or (type(bilateral) is list and all(_real_scalar(v) for v in bilateral))):
         return False
     if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level < 1:
         return False
-    if noise_per_frame is not None and any(type(n) is np.ndarray for n in noise_per_frame):
-        return False
-    if not _engine_eligible(frames, scaling_function, None, noise_per_frame):
-        return False
+    return noise_per_frame is None or not any(type(n) is np.ndarray for n in noise_per_frame)
+
+
+def _bilateral_level_eligible(level, scaling_function, bilateral):
+    """level <= what the marches (25 scales) and the family's sigma_e(bilateral=...) table admit"""
     table = scaling_function(2).sigma_e(bilateral=bilateral)
     return table is not None and level <= min(BILATERAL_MAX_LEVEL, len(table))
 
@@ -161,6 +173,31 @@ def batch64_eligible(frames, level, scaling_function=B3spline, bilateral=None, n
         return False
     N, H, W = frames.shape
     return N >= 1 and _lib.batch64_fused_ok(_family_of(scaling_function(2)), H, W, int(level))
+
+
+def bilateral64_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=()):
+    """True when the float64 batch computes this stack WITH bilateral filtering (host logic): batch64_eligible's
+    conditions for the frames (an (N, H, W) ndarray the reference computes in float64: native float64, or int16 /
+    uint16 / int32 / uint32 / int64 / '>f4' / '>f8', widened on the device), the scaling function and the noise
+    levels; bilateral_eligible's for `bilateral` (a real scalar / bool or a list of them), the noise levels
+    (scalars that are not arrays) and the level (1 .. min(25, the family's sigma_e(bilateral=...) table)); and frames
+    that take the float64 march per frame (_lib.batch64_bilateral_ok: H >= 2, rows the batch accepts, option
+    "stencil64" on - with it off the per-frame call runs three generic kernels per scale, whose bits differ).  False
+    without bilateral filtering: those stacks are batch64_eligible's.  Everything else runs the per-frame loop."""
+    if not _bilateral_call_eligible(level, bilateral, noise_per_frame):
+        return False
+    if not isinstance(frames, np.ndarray) or frames.ndim != 3:
+        return False
+    if _result_dtype(frames) != np.float64:
+        return False
+    if frames.dtype != np.dtype(np.float64) and not _lib.device_widens(frames.dtype):
+        return False
+    if not _family_noise_eligible(scaling_function, None, noise_per_frame):
+        return False
+    if not _bilateral_level_eligible(level, scaling_function, bilateral):
+        return False
+    N, H, W = frames.shape
+    return N >= 1 and _lib.batch64_bilateral_ok(_family_of(scaling_function(2)), H, W, int(level))
 
 
 def _chunks(frames, level):
@@ -212,6 +249,8 @@ def transform_stack(frames, level, scaling_function=B3spline, out=None, bilatera
     fr = _as_frames(frames)
     if batch64_eligible(fr, level, scaling_function, bilateral):
         return _transform_stack64(fr, level, scaling_function, out)
+    if bilateral64_eligible(fr, level, scaling_function, bilateral):
+        return _transform_stack64(fr, level, scaling_function, out, bilateral, bilateral_scaling)
     bil = bilateral_eligible(fr, level, scaling_function, bilateral)
     if not bil and not batch_eligible(fr, level, scaling_function, bilateral):
         return _hand_over(np.stack([AtrousTransform(scaling_function, bilateral, bilateral_scaling)(f, level).data
@@ -239,8 +278,9 @@ def transform_stack(frames, level, scaling_function=B3spline, out=None, bilatera
     return out
 
 
-def _transform_stack64(fr, level, scaling_function, out):
-    """transform_stack on the float64 batch (batch64_eligible): per frame, AtrousTransform._call_f64's fused passes"""
+def _transform_stack64(fr, level, scaling_function, out, bilateral=None, bilateral_scaling=False):
+    """transform_stack on the float64 batch: per frame, AtrousTransform._call_f64's fused passes (batch64_eligible)
+    or, with `bilateral`, its one march per scale (bilateral64_eligible; ref:433-442)"""
     N, H, W = fr.shape
     res, fill = _f64_target(out, (N, level + 1, H, W))
     ctx = _lib.default_context()
@@ -250,7 +290,11 @@ def _transform_stack64(fr, level, scaling_function, out):
     try:
         for f0, nf in chunks:
             bp.upload(PLANE_INPUT, fr[f0:f0 + nf])               # (integer / big-endian frames: widened on the device)
-            bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
+            if bilateral is not None:
+                sb = _sigma_bilateral_list(bilateral, level)
+                bp.decompose_bilateral(nf, PLANE_INPUT, level, sb, bilateral_scaling)
+            else:
+                bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
             for s in range(level + 1):
                 bp.download(s, nf, out=res[f0:f0 + nf, s])
     finally:
@@ -270,14 +314,17 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
     N = len(fr)
     nl = _noise_list(noise, N)
     level = len(weights)
-    if batch64_eligible(fr, level, scaling_function, bilateral, nl):
+    b64 = batch64_eligible(fr, level, scaling_function, bilateral, nl)
+    bil64 = not b64 and bilateral64_eligible(fr, level, scaling_function, bilateral, nl)
+    if b64 or bil64:
         _, H, W = fr.shape
         res, fill = _f64_target(out, (N, H, W))
         fam = _family_of(scaling_function(2))
         chunks = _lib.batch_chunks(N, H, W, level, itemsize=8)
         bp = _lib.acquire_batch64(_lib.default_context(), max(nf for _, nf in chunks), H, W, fam, level)
         try:
-            _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe, None, res)
+            _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe,
+                            bilateral if bil64 else None, res)
         finally:
             _lib.release_batch64(bp)
         if fill is not None:
@@ -308,7 +355,7 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
 def _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe, bilateral, out):
     """denoise_stack's device part on a BatchPlan (float32) or a BatchPlan64 (float64): every chunk of frames
     through the per-frame sequence of utils.denoise (wavelets._decompose_denoise_sum), results into `out`.
-    `bilateral`: the batched bilateral transform's parameter (float32 batches), else None."""
+    `bilateral`: the batched bilateral transform's parameter (bilateral_eligible / bilateral64_eligible), else None."""
     bil = bilateral is not None
     level = len(weights)
     sf = scaling_function(2)

@@ -536,6 +536,70 @@ extern "C" int wt_batch64_decompose(wt_batch64 *b, int nf, int src, int level, i
     return batch64_schedule_run(b, nf, src, level, false, WT_PLANE_NONE, "wt_batch64_decompose");
 }
 
+// When a frame of this shape takes the float64 bilateral march per frame (wt64_decompose_bilateral's `tiled`:
+// stencil64_ok of a wt_plan64 of that shape - the option, a built-in family, an image), so that the batched march
+// gives the per-frame call's bits; with the option off the per-frame call runs the generic three-kernel form.
+static bool batch64_bilateral_shape_ok(int family, int64_t H, int64_t W, int level)
+{
+    if (family != WT_B3SPLINE && family != WT_TRIANGLE) return false;
+    if (H < 2 || W < 1 || H > INT32_MAX || W > INT32_MAX) return false;
+    if (!wt_fused_supported_bytes((W + 1) / 2 * 2 * 8)) return false;      // (the rows wt_batch64_create accepts)
+    if (level < 1 || level > 25) return false;
+    return wt_get_stencil64() != 0;
+}
+
+extern "C" int wt_batch64_bilateral_ok(int family, int64_t H, int64_t W, int level, int *ok)
+{
+    if (!ok) WT_FAIL("wt_batch64_bilateral_ok: null pointer");
+    *ok = batch64_bilateral_shape_ok(family, H, W, level) ? 1 : 0;
+    return 0;
+}
+
+// wt64_decompose_bilateral (wt_f64.h, watroo/wavelets.py:433-442) for the active frames: scale s reads the current
+// smooth, writes c_{s+1} to a scratch plane (the two ping-pong; plane `level` on the last scale) and w_s to plane s,
+// the variance formed in the march with f1 = sigma_b[s]^2, f2 = s + 1 under bilateral_scaling.  One launch per scale
+// for all frames (wt_bilateral64_batch.hip); no three-kernel form, no side stream, no scale events.
+extern "C" int wt_batch64_decompose_bilateral(wt_batch64 *b, int nf, int src, int level, const double *sigma_b, int bilateral_scaling, int flags)
+{
+    (void)flags;
+    WT_TRY(check_frames64(b, nf, "wt_batch64_decompose_bilateral"));
+    WtGuard guard_(b->ctx);
+    if (!sigma_b) WT_FAIL("wt_batch64_decompose_bilateral: null pointer");
+    if (level < 0 || level > b->max_level) WT_FAIL("wt_batch64_decompose_bilateral: level %d exceeds the batch's max_level %d", level, b->max_level);
+    if (src >= 0 && src <= level) WT_FAIL("wt_batch64_decompose_bilateral: src plane %d is one of the output planes", src);
+    if (src == WT_PLANE_SCRATCH(0) || src == WT_PLANE_SCRATCH(1)) WT_FAIL("wt_batch64_decompose_bilateral: scratch planes 0/1 are used internally");
+    if (level > 25) WT_FAIL("wt_batch64_decompose_bilateral: scale %d out of range", level - 1);
+    double *in = nullptr;
+    WT_TRY(b64plane(b, src, &in));
+    if (level == 0) {
+        double *d = nullptr;
+        WT_TRY(b64plane(b, 0, &d));
+        WT_HIP(hipMemcpyAsync(d, in, (size_t)nf * (size_t)b->fstride * 8, hipMemcpyDeviceToDevice, b->ctx->stream));
+        return 0;
+    }
+    if (!batch64_bilateral_shape_ok(b->family, b->geo.g.H, b->geo.g.W, level))
+        WT_FAIL("wt_batch64_decompose_bilateral: %d x %d frames do not take the float64 march per frame (wt_batch64_bilateral_ok): not a batch case",
+                b->geo.g.H, b->geo.g.W);
+    WtFrames fr;
+    fr.n = nf;
+    fr.fstride = b->fstride;
+    const StencilCtx sc{b->ctx, b->ctx->stream, b->geo.g, b->family};
+    for (int s = 0; s < level; ++s) {
+        const int nxt = (s == level - 1) ? level : WT_PLANE_SCRATCH(s & 1);
+        double *oc = nullptr, *ow = nullptr;
+        WT_TRY(b64plane(b, nxt, &oc));
+        WT_TRY(b64plane(b, s, &ow));
+        ChainArgsT<double> a{};
+        a.in = in; a.out_c = oc; a.out_w = ow;
+        // variance = sdev_loc(c_s)^2-form * sigma_b[s]**2 (* (s+1))   watroo/wavelets.py:434-436
+        a.f1 = sigma_b[s] * sigma_b[s];
+        a.f2 = bilateral_scaling ? (double)(s + 1) : 1.0;
+        WT_TRY(wt64_bilateral_batch_launch(sc, a, s, fr));
+        in = oc;
+    }
+    return 0;
+}
+
 extern "C" int wt_batch64_decompose_sum(wt_batch64 *b, int nf, int src, int level, int dst, int flags)
 {
     WT_TRY(check_frames64(b, nf, "wt_batch64_decompose_sum"));

@@ -205,6 +205,7 @@ extern "C" int wt64_download(wt_plan64 *p, int plane, double *host, int64_t host
 static int fused64_family(const wt_plan64 *p);
 static int g_opt_stencil64 = getenv("WT_NO_STENCIL64") ? 0 : 1;
 void wt_set_stencil64(int on) { g_opt_stencil64 = on; }
+int wt_get_stencil64() { return g_opt_stencil64; }
 static inline bool stencil64_ok(const wt_plan64 *p) { return g_opt_stencil64 && fused64_family(p) >= 0 && p->g.H >= 2; }
 static inline StencilCtx stencil64_ctx(const wt_plan64 *p, hipStream_t st = nullptr)
 {

@@ -87,6 +87,7 @@ void wt_set_fused64(int on);                                                 // 
 void wt_set_select64_list(int on);
 void wt_set_f64_pairs(int on);
 void wt_set_stencil64(int on);
+int wt_get_stencil64();                                                      // (wt_batch64_bilateral_ok: stencil64_ok's option)
 
 // ------------------------------------------------------------------ plans (wt_core.hip)
 static inline int family_taps(int family) { return family == WT_B3SPLINE ? 5 : 3; }

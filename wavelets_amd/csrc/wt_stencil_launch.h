@@ -224,3 +224,6 @@ int wt64_stencil_launch(const StencilCtx &sc, int mode, const ChainArgsT<double>
 // marching kernel of wt_bilateral64.h; var == nullptr: variance of wavelets.py:434-436 formed in the kernel
 int wt64_bilateral_launch(const StencilCtx &sc, const double *in, const double *var, double *out, double *out_w, int s,
                           double f1, double f2);
+// one scale of the float64 bilateral transform (variance in the kernel, a.f1 / a.f2) on the frames `fr` of a batch
+// (wt_bilateral64_batch.hip): every frame as wt64_bilateral_march_kernel would run it alone, one launch
+int wt64_bilateral_batch_launch(const StencilCtx &sc, ChainArgsT<double> a, int s, const WtFrames &fr);
