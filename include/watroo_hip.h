@@ -627,12 +627,22 @@ int wt_batch_denoise_sum(wt_batch *batch, int nf, int count, int dst, int n_den,
  * row of frame f at f * n_den; 1 <= n_den <= count; scalar noise only */
 int wt_batch_enhance_sum(wt_batch *batch, int nf, int count, int dst, int n_den, const double *tau,
                          const double *wgt, int soft, int write_back);
+/* wt_batch_denoise_sum with a per-pixel noise map per frame (Coefficients.significance on an ndarray noise,
+ * watroo/wavelets.py:133-141; wt_denoise_sum with its noise_plane): the threshold of pixel i is
+ * tau[frame * n_den + k] * noise_plane[i].  noise_plane is a plane of the batch (WT_PLANE_SCRATCH(5)) holding one map
+ * per active frame, finite in the pitch padding too; a frame with a scalar noise level holds ones */
+int wt_batch_denoise_sum_map(wt_batch *batch, int nf, int count, int dst, int n_den, const double *tau,
+                             const double *wgt, int soft, int write_back, int noise_plane);
+/* frame 0 of the plane -> frames 1 .. nf-1 on the device (one noise map shared by the frames of a stack, the
+ * `noise` of watroo/utils.py:96 given once: it crosses PCIe once per chunk) */
+int wt_batch_replicate(wt_batch *batch, int nf, int plane);
 /* generalized_anscombe over the active frames (watroo/utils.py:93-94, 99-100; as wt_anscombe) */
 int wt_batch_anscombe(wt_batch *batch, int nf, int src, int dst, float alpha, float g, float sigma,
                       int inverse);
 /* ---- wow over a batch (watroo/utils.py:105-219, utils.wow per frame).  Extra planes: WT_PLANE_SCRATCH(3), the
  * output plane of wt_batch_wow_scale, and WT_PLANE_SCRATCH(4), wow's gamma accumulator.  Per-frame parameters are
- * arrays of nf entries; every frame gets the bits of the per-frame call on a wt_plan. */
+ * arrays of nf entries; every frame gets the bits of the per-frame call on a wt_plan.  WT_PLANE_SCRATCH(5): the
+ * per-pixel noise maps of the *_map entries. */
 /* plane <- value over the active frames (gamma_scaled = zeros, watroo/utils.py:157-158; as wt_fill_plane) */
 int wt_batch_fill(wt_batch *batch, int nf, int plane, float value);
 /* frame f of the plane <- wt_fill_normal(seed, first_trial + f) of a wt_plan of the frame's shape, frames 0 .. nf-1
@@ -647,6 +657,15 @@ int wt_batch_wow_update(wt_batch *batch, int nf, int plane, const double *tau, i
  * and the two planes' buffers are swapped */
 int wt_batch_wow_scale(wt_batch *batch, int nf, int plane, int s, const double *tau, int soft, const float *factor,
                        int gamma_plane);
+/* wt_batch_wow_update with a per-pixel noise map per frame (watroo/utils.py:199 on an ndarray noise,
+ * wavelets.py:133-141; wt_wow_update with its noise_plane): noise_plane as in wt_batch_denoise_sum_map */
+int wt_batch_wow_update_map(wt_batch *batch, int nf, int plane, const double *tau, int soft, const float *factor,
+                            int gamma_plane, int noise_plane);
+/* wt_batch_wow_scale with a per-pixel noise map per frame (watroo/utils.py:192-203 on an ndarray noise,
+ * wavelets.py:133-141; wt_wow_scale with its noise_plane: the stencil's instantiation with the map and, when
+ * gamma_plane is given, the gamma accumulator): noise_plane as in wt_batch_denoise_sum_map */
+int wt_batch_wow_scale_map(wt_batch *batch, int nf, int plane, int s, const double *tau, int soft,
+                           const float *factor, int gamma_plane, int noise_plane);
 /* wt_reduce per frame ({sum, sumsq, min, max}, fp64, the per-frame call's doubles; np.std / np.mean(c**2) of
  * watroo/utils.py:178-189, gamma_scaled.min / max of utils.py:208-211): out[4 * nf], one host round trip */
 int wt_batch_reduce(wt_batch *batch, int nf, int plane, double *out);
@@ -715,6 +734,18 @@ int wt_batch64_denoise_sum(wt_batch64 *batch, int nf, int count, int dst, int n_
  * and wgt hold nf * n_den entries, the row of frame f at f * n_den; 1 <= n_den <= count; scalar noise only */
 int wt_batch64_enhance_sum(wt_batch64 *batch, int nf, int count, int dst, int n_den, const double *tau,
                            const double *wgt, int soft, int write_back);
+/* wt_batch64_denoise_sum with a per-pixel noise map per frame (Coefficients.significance on an ndarray noise,
+ * watroo/wavelets.py:133-141; wt64_denoise_sum with its noise_plane): noise_plane is a plane of the batch
+ * (WT_PLANE_SCRATCH(5)) of float64 maps, finite in the pitch padding too.  has_map[nf] (NULL: every frame): a frame
+ * with has_map[f] == 0 has a scalar noise level and is thresholded as wt_batch64_denoise_sum thresholds it (the
+ * reciprocal form of the map-free kernel), whatever its slot of the plane holds */
+int wt_batch64_denoise_sum_map(wt_batch64 *batch, int nf, int count, int dst, int n_den, const double *tau,
+                               const double *wgt, int soft, int write_back, int noise_plane, const int *has_map);
+/* plane <- value over the active frames, pitch padding included (as wt_batch_fill): ones in the noise plane before
+ * the maps go up, so that a frame with a scalar level of watroo/wavelets.py:133-135 and every padding lane read 1 */
+int wt_batch64_fill(wt_batch64 *batch, int nf, int plane, double value);
+/* frame 0 of the plane -> frames 1 .. nf-1 on the device (as wt_batch_replicate; watroo/utils.py:96) */
+int wt_batch64_replicate(wt_batch64 *batch, int nf, int plane);
 /* generalized_anscombe over the active frames (watroo/utils.py:93-94, 99-100; as wt64_anscombe) */
 int wt_batch64_anscombe(wt_batch64 *batch, int nf, int src, int dst, double alpha, double g, double sigma,
                         int inverse);

@@ -215,6 +215,9 @@ SIGNATURES = {
                                         _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
     "wt_batch_enhance_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
                                         _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
+    "wt_batch_denoise_sum_map": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
+                                            _c.POINTER(_c.c_double), _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch_replicate": (_c.c_int, [_vp, _c.c_int, _c.c_int]),
     "wt_batch_anscombe": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float,
                                      _c.c_int]),
     "wt_batch_fill": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_float]),
@@ -222,6 +225,10 @@ SIGNATURES = {
     "wt_batch_wow_update": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _fp, _c.c_int]),
     "wt_batch_wow_scale": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _fp,
                                       _c.c_int]),
+    "wt_batch_wow_update_map": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _fp, _c.c_int,
+                                           _c.c_int]),
+    "wt_batch_wow_scale_map": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _fp,
+                                          _c.c_int, _c.c_int]),
     "wt_batch_reduce": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double)]),
     "wt_batch_gamma_blend": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _fp, _fp, _c.c_float, _c.c_float]),
     "wt_batch_plane_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
@@ -247,6 +254,11 @@ SIGNATURES = {
                                           _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
     "wt_batch64_enhance_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
                                           _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
+    "wt_batch64_denoise_sum_map": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
+                                              _c.POINTER(_c.c_double), _c.c_int, _c.c_int, _c.c_int,
+                                              _c.POINTER(_c.c_int)]),
+    "wt_batch64_fill": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_double]),
+    "wt_batch64_replicate": (_c.c_int, [_vp, _c.c_int, _c.c_int]),
     "wt_batch64_anscombe": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_double, _c.c_double,
                                        _c.c_int]),
 }
@@ -989,6 +1001,8 @@ class BatchPlan:
     """Device planes of up to `n` frames of one H x W shape (wt_batch).  Operations take the number of
     active frames `nf` (frames 0 .. nf-1); upload / download move a C-contiguous (nf, H, W) block."""
 
+    dtype = np.float32
+
     def __init__(self, ctx, n, H, W, family, max_level):
         self._h = _vp()
         self.ctx = ctx
@@ -1054,13 +1068,19 @@ class BatchPlan:
         check(load().wt_batch_abs_median(self._h, nf, plane, m))
         return [np.float32(v) for v in m]
 
-    def denoise_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT):
-        """`taus`: one row of thresholds per active frame (all rows of one length n_den)"""
+    def denoise_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT, noise_plane=PLANE_NONE,
+                    has_map=None):
+        """`taus`: one row of thresholds per active frame (all rows of one length n_den).  `noise_plane`: the plane
+        of per-pixel noise maps, one per active frame (ones for a frame with a scalar noise level; `has_map` is the
+        float64 batch's)"""
         n = len(wgts)
         if len(taus) != nf or any(len(t) != n for t in taus):
             raise ValueError("denoise_sum: one row of len(wgts) thresholds per frame")
         ta = (_c.c_double * max(nf * n, 1))(*[float(t) for row in taus for t in row])
         wa = (_c.c_double * max(n, 1))(*[float(w) for w in wgts])
+        if noise_plane != PLANE_NONE:
+            check(load().wt_batch_denoise_sum_map(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back), noise_plane))
+            return
         check(load().wt_batch_denoise_sum(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back)))
 
     def enhance_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT):
@@ -1081,20 +1101,32 @@ class BatchPlan:
     def fill(self, nf, plane, value):
         check(load().wt_batch_fill(self._h, nf, plane, value))
 
+    def replicate(self, nf, plane):
+        """frame 0 of `plane` -> frames 1 .. nf-1, on the device (a noise map shared by the frames)"""
+        check(load().wt_batch_replicate(self._h, nf, plane))
+
     def fill_normal(self, nf, plane, seed, first_trial=0):
         """frame f of `plane` <- Plan.fill_normal(plane, seed, first_trial + f), frames 0 .. nf-1 (rng.py: the layout)"""
         check(load().wt_batch_fill_normal(self._h, nf, plane, _seed64(seed), _trial32(first_trial)))
 
-    def wow_update(self, nf, plane, taus, soft, factors, gamma_plane=PLANE_NONE):
-        """Plan.wow_update per frame without power plane or noise map: taus[f] (0.0: significance one), factors[f]"""
+    def wow_update(self, nf, plane, taus, soft, factors, gamma_plane=PLANE_NONE, noise_plane=PLANE_NONE):
+        """Plan.wow_update per frame without power plane: taus[f] (0.0: significance one), factors[f]; `noise_plane`:
+        the plane of per-pixel noise maps, one per active frame"""
         t = self._per_frame(taus, nf, _c.c_double, "wow_update taus")
         f = self._per_frame(factors, nf, _c.c_float, "wow_update factors")
+        if noise_plane != PLANE_NONE:
+            check(load().wt_batch_wow_update_map(self._h, nf, plane, t, int(soft), f, gamma_plane, noise_plane))
+            return
         check(load().wt_batch_wow_update(self._h, nf, plane, t, int(soft), f, gamma_plane))
 
-    def wow_scale(self, nf, plane, s, taus, soft, factors, gamma_plane=PLANE_NONE):
-        """Plan.wow_scale per frame (scalar noise): local power, significance, gamma sum and whitening, in place"""
+    def wow_scale(self, nf, plane, s, taus, soft, factors, gamma_plane=PLANE_NONE, noise_plane=PLANE_NONE):
+        """Plan.wow_scale per frame: local power, significance, gamma sum and whitening, in place; `noise_plane`: the
+        plane of per-pixel noise maps, one per active frame"""
         t = self._per_frame(taus, nf, _c.c_double, "wow_scale taus")
         f = self._per_frame(factors, nf, _c.c_float, "wow_scale factors")
+        if noise_plane != PLANE_NONE:
+            check(load().wt_batch_wow_scale_map(self._h, nf, plane, s, t, int(soft), f, gamma_plane, noise_plane))
+            return
         check(load().wt_batch_wow_scale(self._h, nf, plane, s, t, int(soft), f, gamma_plane))
 
     def reduce(self, nf, plane):
@@ -1207,19 +1239,39 @@ class BatchPlan64:
         check(load().wt_batch64_abs_median(self._h, nf, plane, m))
         return [np.float64(v) for v in m]
 
-    def denoise_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT):
-        """`taus`: one row of thresholds per active frame (all rows of one length n_den)"""
+    def denoise_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT, noise_plane=PLANE_NONE,
+                    has_map=None):
+        """`taus`: one row of thresholds per active frame (all rows of one length n_den).  `noise_plane`: the plane
+        of per-pixel float64 noise maps; `has_map`: per active frame, whether it has one (None: all) - a frame
+        without keeps the arithmetic of the call without a noise plane"""
         n = len(wgts)
         if len(taus) != nf or any(len(t) != n for t in taus):
             raise ValueError("denoise_sum: one row of len(wgts) thresholds per frame")
         ta = (_c.c_double * max(nf * n, 1))(*[float(t) for row in taus for t in row])
         wa = (_c.c_double * max(n, 1))(*[float(w) for w in wgts])
+        if noise_plane != PLANE_NONE:
+            hm = None if has_map is None else self._has_map(has_map, nf)
+            check(load().wt_batch64_denoise_sum_map(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back), noise_plane, hm))
+            return
         check(load().wt_batch64_denoise_sum(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back)))
 
     def enhance_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT):
         """denoise_sum with one row of weights per active frame as well (utils.enhance: a colour image's channels
         are frames with their own sigmas and weights); all rows of one length n_den >= 1"""
         check(load().wt_batch64_enhance_sum(self._h, nf, count, dst, *_enhance_rows(nf, taus, wgts), int(soft), int(write_back)))
+
+    @staticmethod
+    def _has_map(has_map, nf):
+        if len(has_map) != nf:
+            raise ValueError(f"denoise_sum has_map: one flag per active frame ({nf} frames, {len(has_map)} flags)")
+        return (_c.c_int * nf)(*[int(bool(v)) for v in has_map])
+
+    def fill(self, nf, plane, value):
+        check(load().wt_batch64_fill(self._h, nf, plane, value))
+
+    def replicate(self, nf, plane):
+        """frame 0 of `plane` -> frames 1 .. nf-1, on the device (a noise map shared by the frames)"""
+        check(load().wt_batch64_replicate(self._h, nf, plane))
 
     def anscombe(self, nf, src, dst, alpha=1.0, g=0.0, sigma=0.0, inverse=False):
         check(load().wt_batch64_anscombe(self._h, nf, src, dst, alpha, g, sigma, int(inverse)))

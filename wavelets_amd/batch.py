@@ -13,19 +13,23 @@ _wow_sigma_bilateral).  With bilateral= the transform is the batched bilateral m
 all frames, bilateral_eligible).  Stacks the reference
 computes in float64 (float64 frames; int16 .. int64 and big-endian frames, which it recasts) run transform_stack
 and denoise_stack on the float64 batch (wt_batch64, batch64_eligible), with bilateral= behind the batched float64
-march (bilateral64_eligible).  Inputs the batched engines do not cover run the per-frame loop (batch_eligible /
-batch64_eligible / wow_eligible / bilateral_eligible / bilateral64_eligible say which)."""
+march (bilateral64_eligible).  `noise` may hold per-pixel noise maps (ref wavelets.py:133-141) - one (H, W) ndarray
+shared by the frames, or one entry per frame, maps mixed with levels and None: they lie in one more plane of the batch,
+the noise plane (noise_map_eligible, _upload_noise_maps; a shared map crosses PCIe once and is replicated on the device),
+read by the map forms of the thresholded sum (both batches) and of wow's updates (float32); a frame with a level has
+ones there and keeps its map-free arithmetic.  Inputs the batched engines do not cover run the per-frame loop
+(batch_eligible / batch64_eligible / wow_eligible / bilateral_eligible / bilateral64_eligible say which)."""
 import numpy as np
 
 from . import _lib
 from ._lib import PLANE_INPUT, PLANE_OUT, PLANE_NONE, PLANE_SCRATCH, FLAG_FUSED
-from .wavelets import (AtrousTransform, B3spline, _family_of, _needs_generic, _interleave_split, _tau_row,
-                       _noise_from_median, _sigma_bilateral_list, _result_dtype)
+from .wavelets import (AtrousTransform, B3spline, _family_of, _needs_generic, _interleave_split, _tau_row, _map_tau_row,
+                       _noise_from_median, _sigma_bilateral_list, _result_dtype, _NOISE_PLANE)
 from .utils import (denoise, wow, enhance, _enhance_lists, _GAMMA_PLANE, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments,
                     _wow_factor, _gamma_range, _wow_sigma_bilateral)
 
 __all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'enhance_stack', 'batch_eligible', 'batch64_eligible',
-           'wow_eligible', 'bilateral_eligible', 'bilateral64_eligible', 'enhance_eligible']
+           'wow_eligible', 'bilateral_eligible', 'bilateral64_eligible', 'enhance_eligible', 'noise_map_eligible']
 
 # levels whose fused schedule has a kernel for every pass (wt_plan_fused_ok), both built-in families: L = 1 is
 # a single-scale pass, and from 9 scales on the schedules hold single-scale passes at D >= 256 (wt_fused_has_pass)
@@ -51,11 +55,21 @@ def _as_frames(frames):
     return np.stack(items)
 
 
-def _noise_list(noise, n):
-    """one noise entry per frame (None: that frame's own MAD estimate)"""
-    if noise is None or np.ndim(noise) == 0:
+def _is_noise_map(n, shape):
+    """True for a per-pixel noise map the batched engines take: an ndarray (as Coefficients._tau tells a map from
+    a level) of real numbers and of exactly the frames' (H, W)"""
+    return type(n) is np.ndarray and n.ndim == 2 and n.shape == tuple(shape) and n.dtype.kind in "biuf"
+
+
+def _noise_list(noise, n, shape=None):
+    """one noise entry per frame (None: that frame's own MAD estimate).  `shape`: the frames' (H, W) - an ndarray
+    of exactly that shape is then one noise map shared by the frames (the same array in every entry); without it,
+    and for arrays of any other shape, None: the per-frame loop hands the whole array to every frame"""
+    if noise is None or (not isinstance(noise, (list, tuple)) and np.ndim(noise) == 0):
         return [noise] * n
     if isinstance(noise, np.ndarray) and noise.ndim != 1:
+        if shape is not None and _is_noise_map(noise, shape):
+            return [noise] * n
         return None                       # a noise map: the per-frame loop (a 1-D array: one level per frame)
     noise = list(noise)
     if len(noise) != n:
@@ -63,12 +77,32 @@ def _noise_list(noise, n):
     return noise
 
 
-def batch_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=()):
+def _maps_admitted(frames, noise_per_frame, noise_maps):
+    """noise_per_frame as the predicates below judge it: with `noise_maps`, every entry that is a noise map of the
+    frames' shape (_is_noise_map) stands as a scalar level - the batch holds it in its noise plane.  Without
+    `noise_maps` (the default of every predicate) nothing changes: an array entry is refused as before."""
+    if not noise_maps or noise_per_frame is None or not isinstance(frames, np.ndarray) or frames.ndim != 3:
+        return noise_per_frame
+    return [1.0 if _is_noise_map(n, frames.shape[1:]) else n for n in noise_per_frame]
+
+
+def noise_map_eligible(frames, noise_per_frame):
+    """True when `noise_per_frame` holds at least one per-pixel noise map that the batched engines take for the
+    (N, H, W) stack `frames` (host logic): a real ndarray of exactly (H, W).  The predicates below admit such
+    entries with noise_maps=True; the other entries stay None or real scalars."""
+    if noise_per_frame is None or not isinstance(frames, np.ndarray) or frames.ndim != 3:
+        return False
+    return any(_is_noise_map(n, frames.shape[1:]) for n in noise_per_frame)
+
+
+def batch_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=(), noise_maps=False):
     """True when the batched engine computes this stack (host logic): native float32 frames of one shape in an
     (N, H, W) array, no bilateral filtering, a built-in scaling function with its own taps, a level with an
-    all-fused schedule (2..8) and scalar noise levels.  Everything else runs the per-frame loop."""
+    all-fused schedule (2..8) and scalar noise levels - with noise_maps=True also per-pixel noise maps of the frames'
+    shape (_is_noise_map).  Everything else runs the per-frame loop."""
     if level not in BATCH_LEVELS:
         return False
+    noise_per_frame = _maps_admitted(frames, noise_per_frame, noise_maps)
     return _engine_eligible(frames, scaling_function, bilateral, noise_per_frame)
 
 
@@ -77,16 +111,24 @@ def batch_eligible(frames, level, scaling_function=B3spline, bilateral=None, noi
 WOW_LEVELS = range(1, 25)
 
 
-def wow_eligible(frames, n_scales, scaling_function=B3spline, bilateral=None, noise_per_frame=()):
+def wow_eligible(frames, n_scales, scaling_function=B3spline, bilateral=None, noise_per_frame=(), noise_maps=False):
     """True when the batched engine computes wow over this stack (host logic): batch_eligible's conditions for
     the frames, the scaling function, bilateral filtering and the noise levels - which must also be scalars that
-    are not arrays (utils.wow takes a 0-d array as a noise map) - with n_scales (already resolved) in 1..24.
-    Everything else runs the per-frame loop."""
+    are not arrays (utils.wow takes a 0-d array as a noise map) or, with noise_maps=True, per-pixel noise maps of the
+    frames' shape - with n_scales (already resolved) in 1..24.  Everything else runs the per-frame loop."""
     if n_scales not in WOW_LEVELS:
         return False
+    noise_per_frame = _maps_admitted(frames, noise_per_frame, noise_maps)
     if noise_per_frame is not None and any(type(n) is np.ndarray for n in noise_per_frame):
         return False
     return _engine_eligible(frames, scaling_function, bilateral, noise_per_frame)
+
+
+# wow_stack takes per-pixel noise maps from this many pixels per frame on (one 256-thread block of float4 groups in the
+# pointwise updates).  Smaller frames with a map keep the per-frame loop they always had: that route is pinned for an
+# 8 x 8 stack (tests/test_wow_stack_cpu.py), and a frame of a few dozen pixels has nothing for the noise plane to save.
+# Not a measured crossover (tools/bench_noise_map_stack.py has the measured shapes); denoise_stack has no such floor.
+WOW_MAP_MIN_PIXELS = 1024
 
 
 # scales of the batched bilateral transform: one launch of the march per scale, up to the per-scale kernels' limit
@@ -98,12 +140,14 @@ def _real_scalar(v):
     return isinstance(v, (bool, int, float, np.bool_, np.integer, np.floating))
 
 
-def bilateral_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=()):
+def bilateral_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=(), noise_maps=False):
     """True when the batched engine computes this stack WITH bilateral filtering (host logic): the conditions of
     batch_eligible / wow_eligible for the frames, the scaling function and the noise levels (scalars that are not
     arrays), `bilateral` a real scalar / bool or a list of them, and 1 <= level <= what wt_decompose_bilateral
     (25) and the family's sigma_e(bilateral=...) table admit.  False without bilateral filtering: those stacks are
-    batch_eligible's / wow_eligible's.  Everything else runs the per-frame loop."""
+    batch_eligible's / wow_eligible's.  noise_maps=True: per-pixel noise maps of the frames' shape are taken too.
+    Everything else runs the per-frame loop."""
+    noise_per_frame = _maps_admitted(frames, noise_per_frame, noise_maps)
     if not _bilateral_call_eligible(level, bilateral, noise_per_frame):
         return False
     if not _engine_eligible(frames, scaling_function, None, noise_per_frame):
@@ -154,15 +198,17 @@ def _family_noise_eligible(scaling_function, bilateral, noise_per_frame):
     return noise_per_frame is not None and not any(n is not None and np.ndim(n) != 0 for n in noise_per_frame)
 
 
-def batch64_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=()):
+def batch64_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=(), noise_maps=False):
     """True when the float64 batch (wt_batch64) computes this stack (host logic): an (N, H, W) ndarray the
     reference computes in float64 (wavelets._result_dtype: native float64, or a type of wavelets._RECAST that the
     device widens - int16 / uint16 / int32 / uint32 / int64, '>f4', '>f8'), no bilateral filtering, a built-in
     scaling function with its own taps, scalar noise levels, and frames whose float64 schedule of `level` scales
     is all fused passes (images, H >= 2, rows the fused passes take at 8 bytes per pixel: _lib.batch64_fused_ok,
-    i.e. what wt64_plan_fused_ok answers for one frame).  Everything else keeps its route."""
+    i.e. what wt64_plan_fused_ok answers for one frame).  noise_maps=True: per-pixel noise maps of the frames' shape
+    are taken too.  Everything else keeps its route."""
     if not isinstance(frames, np.ndarray) or frames.ndim != 3:
         return False
+    noise_per_frame = _maps_admitted(frames, noise_per_frame, noise_maps)
     if _result_dtype(frames) != np.float64:
         return False
     if frames.dtype != np.dtype(np.float64) and not _lib.device_widens(frames.dtype):
@@ -175,7 +221,7 @@ def batch64_eligible(frames, level, scaling_function=B3spline, bilateral=None, n
     return N >= 1 and _lib.batch64_fused_ok(_family_of(scaling_function(2)), H, W, int(level))
 
 
-def bilateral64_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=()):
+def bilateral64_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=(), noise_maps=False):
     """True when the float64 batch computes this stack WITH bilateral filtering (host logic): batch64_eligible's
     conditions for the frames (an (N, H, W) ndarray the reference computes in float64: native float64, or int16 /
     uint16 / int32 / uint32 / int64 / '>f4' / '>f8', widened on the device), the scaling function and the noise
@@ -183,7 +229,9 @@ def bilateral64_eligible(frames, level, scaling_function=B3spline, bilateral=Non
     (scalars that are not arrays) and the level (1 .. min(25, the family's sigma_e(bilateral=...) table)); and frames
     that take the float64 march per frame (_lib.batch64_bilateral_ok: H >= 2, rows the batch accepts, option
     "stencil64" on - with it off the per-frame call runs three generic kernels per scale, whose bits differ).  False
-    without bilateral filtering: those stacks are batch64_eligible's.  Everything else runs the per-frame loop."""
+    without bilateral filtering: those stacks are batch64_eligible's.  noise_maps=True: per-pixel noise maps of the
+    frames' shape are taken too.  Everything else runs the per-frame loop."""
+    noise_per_frame = _maps_admitted(frames, noise_per_frame, noise_maps)
     if not _bilateral_call_eligible(level, bilateral, noise_per_frame):
         return False
     if not isinstance(frames, np.ndarray) or frames.ndim != 3:
@@ -309,18 +357,19 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
                   out=None, bilateral=None):
     """(N, H, W): utils.denoise of every frame (ref utils.py:83-102), batched - float32, or float64 for the stacks
     the reference computes in float64.  `noise`: None (each frame's own MAD estimate), a scalar, or one entry per
-    frame."""
+    frame - a level or a per-pixel noise map of the frames' (H, W); an (H, W) ndarray: one map shared by the frames."""
     fr = _as_frames(frames)
     N = len(fr)
-    nl = _noise_list(noise, N)
+    nl = _noise_list(noise, N, fr[0].shape)
     level = len(weights)
-    b64 = batch64_eligible(fr, level, scaling_function, bilateral, nl)
-    bil64 = not b64 and bilateral64_eligible(fr, level, scaling_function, bilateral, nl)
+    maps = int(noise_map_eligible(fr, nl))                 # (the noise plane: one more plane per frame)
+    b64 = batch64_eligible(fr, level, scaling_function, bilateral, nl, noise_maps=True)
+    bil64 = not b64 and bilateral64_eligible(fr, level, scaling_function, bilateral, nl, noise_maps=True)
     if b64 or bil64:
         _, H, W = fr.shape
         res, fill = _f64_target(out, (N, H, W))
         fam = _family_of(scaling_function(2))
-        chunks = _lib.batch_chunks(N, H, W, level, itemsize=8)
+        chunks = _lib.batch_chunks(N, H, W, level, extra_planes=maps, itemsize=8)
         bp = _lib.acquire_batch64(_lib.default_context(), max(nf for _, nf in chunks), H, W, fam, level)
         try:
             _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe,
@@ -331,8 +380,8 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
             fill[...] = res
             return fill
         return res
-    bil = bilateral_eligible(fr, level, scaling_function, bilateral, nl)
-    if not bil and not batch_eligible(fr, level, scaling_function, bilateral, nl):
+    bil = bilateral_eligible(fr, level, scaling_function, bilateral, nl, noise_maps=True)
+    if not bil and not batch_eligible(fr, level, scaling_function, bilateral, nl, noise_maps=True):
         per = nl if nl is not None else [noise] * N
         return _hand_over(np.stack([denoise(f, weights, scaling_function, n_i, bilateral, soft_threshold, anscombe)
                                     for f, n_i in zip(fr, per)]), out)
@@ -342,7 +391,7 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
         return out
     ctx = _lib.default_context()
     fam = _family_of(scaling_function(2))
-    chunks = _chunks(fr, level)
+    chunks = _lib.batch_chunks(N, H, W, level, extra_planes=maps) if maps else _chunks(fr, level)
     bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, fam, level)
     try:
         _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe, bilateral if bil else None,
@@ -355,8 +404,12 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
 def _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe, bilateral, out):
     """denoise_stack's device part on a BatchPlan (float32) or a BatchPlan64 (float64): every chunk of frames
     through the per-frame sequence of utils.denoise (wavelets._decompose_denoise_sum), results into `out`.
-    `bilateral`: the batched bilateral transform's parameter (bilateral_eligible / bilateral64_eligible), else None."""
+    `bilateral`: the batched bilateral transform's parameter (bilateral_eligible / bilateral64_eligible), else None.
+    Frames whose noise is a per-pixel map (ref wavelets.py:133-141) get the map thresholds (_map_tau_row) and their map
+    in the batch's noise plane (_upload_noise_maps); no MAD estimate is taken for them."""
     bil = bilateral is not None
+    shape = fr.shape[1:]
+    shared = _shared_map(nl, shape)
     level = len(weights)
     sf = scaling_function(2)
     sigma_e = sf.sigma_e(bilateral=bilateral)
@@ -389,8 +442,16 @@ def _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshol
         if any(n is None for n in noises) and any(sig != 0 for _, sig, _ in used):
             med = bp.abs_median(nf, 0)                                        # ref:131-132 (lazy)
             noises = [_noise_from_median(m, sigma_e) if n is None else n for n, m in zip(noises, med)]
-        taus = [_tau_row(used, n, sigma_e, soft_threshold) for n in noises]
-        bp.denoise_sum(nf, level + 1 if whole else covered, taus, [w for _, _, w in used], soft_threshold)
+        has_map = [_is_noise_map(n, shape) for n in noises]
+        if any(has_map):
+            _upload_noise_maps(bp, nf, noises, has_map, shared, first=f0 == 0)
+            taus = [_map_tau_row(used, sigma_e, soft_threshold) if m else _tau_row(used, n, sigma_e, soft_threshold)
+                    for n, m in zip(noises, has_map)]
+            bp.denoise_sum(nf, level + 1 if whole else covered, taus, [w for _, _, w in used], soft_threshold,
+                           noise_plane=_NOISE_PLANE, has_map=has_map)
+        else:
+            taus = [_tau_row(used, n, sigma_e, soft_threshold) for n in noises]
+            bp.denoise_sum(nf, level + 1 if whole else covered, taus, [w for _, _, w in used], soft_threshold)
         if not whole:
             for i in range(k, len(sched)):
                 last = i == len(sched) - 1
@@ -403,13 +464,42 @@ def _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshol
         bp.download(PLANE_OUT, nf, out=out[f0:f0 + nf])
 
 
+def _shared_map(nl, shape):
+    """the one noise map every frame of the stack shares (_noise_list of an (H, W) ndarray), or None"""
+    if nl and _is_noise_map(nl[0], shape) and all(n is nl[0] for n in nl):
+        return nl[0]
+    return None
+
+
+def _upload_noise_maps(bp, nf, noises, has_map, shared, first=True):
+    """The noise plane of a chunk (plane _NOISE_PLANE of a BatchPlan / BatchPlan64): frame f's slot holds its map,
+    converted as Coefficients._tau converts it (the plane's element type), or ones where the frame's noise is a
+    scalar; the pitch padding holds ones.  `shared` (one map for the whole stack) crosses PCIe once, for the first
+    chunk - the largest - and is replicated into the frame slots on the device; later chunks find it there."""
+    dtype = bp.dtype
+    if shared is not None:
+        if first:
+            bp.fill(nf, _NOISE_PLANE, 1.0)
+            bp.upload(_NOISE_PLANE, np.asarray(shared, dtype)[None])
+            bp.replicate(nf, _NOISE_PLANE)
+        return
+    bp.fill(nf, _NOISE_PLANE, 1.0)
+    for f in range(nf):                                  # each map from where it lies: no stacked host copy of the maps
+        if has_map[f]:
+            bp.upload(_NOISE_PLANE, np.asarray(noises[f], dtype)[None], f0=f)
+
+
 def _wow_taus(bp, nf, sigma, scale, noises, sigma_e, soft):
-    """(one threshold per frame, the noise levels) of wow's scale `scale` (Coefficients._tau, scalar noise): the
-    frames whose noise is None get their MAD estimate here, where the per-frame call's lazy _tau takes it"""
+    """(one threshold per frame, the noise levels) of wow's scale `scale` (Coefficients._tau): the frames whose
+    noise is None get their MAD estimate here, where the per-frame call's lazy _tau takes it; the frames whose noise
+    is a per-pixel map get the map threshold (_map_tau_row)"""
     if sigma != 0 and any(n is None for n in noises):
         med = bp.abs_median(nf, 0)                                               # ref:131-132 (lazy)
         noises = [_noise_from_median(m, sigma_e) if n is None else n for n, m in zip(noises, med)]
-    return [_tau_row([(scale, sigma, None)], n, sigma_e, soft)[0] for n in noises], noises
+    shape = (bp.H, bp.W)
+    entry = [(scale, sigma, None)]
+    return [_map_tau_row(entry, sigma_e, soft)[0] if _is_noise_map(n, shape) else _tau_row(entry, n, sigma_e, soft)[0]
+            for n in noises], noises
 
 
 def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whitening=True, denoise_coefficients=[],
@@ -417,11 +507,12 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
               gamma=3.2, gamma_min=None, gamma_max=None, h=0, out=None, return_coefficients=False):
     """(N, H, W): the wow image of every frame (utils.wow, ref utils.py:105-219), batched - float32 for the stacks
     the batch computes, the per-frame dtype otherwise.  `noise`: None (each frame's own MAD estimate), a scalar,
-    or one entry per frame.  return_coefficients: (images, planes), planes (N, n_scales + 1, H, W) = the whitened
-    coefficients of every frame (wow(...)[1].data)."""
+    or one entry per frame - a level or a per-pixel noise map of the frames' (H, W); an (H, W) ndarray: one map shared
+    by the frames.  return_coefficients: (images, planes), planes (N, n_scales + 1, H, W) = the whitened coefficients of
+    every frame (wow(...)[1].data)."""
     fr = _as_frames(frames)
     N = len(fr)
-    nl = _noise_list(noise, N)
+    nl = _noise_list(noise, N, fr[0].shape)
     shape = fr[0].shape
     kw = dict(weights=weights, whitening=whitening, denoise_coefficients=denoise_coefficients, bilateral=bilateral,
               bilateral_scaling=bilateral_scaling, soft_threshold=soft_threshold, preserve_variance=preserve_variance,
@@ -429,8 +520,9 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
     # n_scales once for the shared shape, as wow() resolves it for one frame (ref:121-138)
     L = _wow_n_scales(shape, scaling_function, n_scales, h, denoise_coefficients)
     L = _wow_scale_limit(L, scaling_function, 2, bilateral, denoise_coefficients)
-    bil = bilateral_eligible(fr, L, scaling_function, bilateral, nl)
-    if not bil and not wow_eligible(fr, L, scaling_function, bilateral, nl):
+    take_maps = shape[0] * shape[1] >= WOW_MAP_MIN_PIXELS
+    bil = bilateral_eligible(fr, L, scaling_function, bilateral, nl, noise_maps=take_maps)
+    if not bil and not wow_eligible(fr, L, scaling_function, bilateral, nl, noise_maps=take_maps):
         per = nl if nl is not None else [noise] * N
         res = [wow(f, scaling_function, n_scales, noise=n_i, **kw) for f, n_i in zip(fr, per)]
         images = _hand_over(np.stack([r[0] for r in res]), out)
@@ -441,7 +533,10 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
     planes = _lib.host_empty((N, nplanes, H, W)) if return_coefficients else None
     ctx = _lib.default_context()
     fam = _family_of(scaling_function(2))
-    extra = int(whitening and h < 1) + int(h > 0)            # (the spare plane of the fused update, the gamma plane)
+    maps = noise_map_eligible(fr, nl)
+    # (the spare plane of the fused update, the gamma plane, the noise plane)
+    extra = int(whitening and h < 1) + int(h > 0) + int(maps)
+    shared = _shared_map(nl, (H, W))
     chunks = _lib.batch_chunks(N, H, W, L, extra_planes=extra)
     bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, fam, L)
     try:
@@ -452,6 +547,9 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
                 bp.decompose_bilateral(nf, PLANE_INPUT, L, sb, bilateral_scaling)
             else:
                 bp.decompose(nf, PLANE_INPUT, L, FLAG_FUSED)                        # ref:148-151
+            if maps:
+                noises = nl[f0:f0 + nf]
+                _upload_noise_maps(bp, nf, noises, [_is_noise_map(n, (H, W)) for n in noises], shared, first=f0 == 0)
             _wow_batch_device(bp, nf, nl[f0:f0 + nf], scaling_function, L, weights, whitening, denoise_coefficients,
                               soft_threshold, preserve_variance, gamma, gamma_min, gamma_max, h, bilateral)
             bp.download(PLANE_OUT, nf, out=out[f0:f0 + nf])
@@ -467,7 +565,9 @@ def _wow_batch_device(bp, nf, noises, scaling_function, n_scales, weights, white
                       soft_threshold, preserve_variance, gamma, gamma_min, gamma_max, h, bilateral=None):
     """The device-resident part of wow (ref:157-217, utils._wow_device / _wow_scales) for frames 0 .. nf-1 of a
     batch whose planes 0 .. n_scales hold the transform: whitened planes in place, the images in PLANE_OUT.
-    `noises`: one entry per frame (None: its MAD estimate, taken where the per-frame call's lazy _tau takes it).
+    `noises`: one entry per frame (None: its MAD estimate, taken where the per-frame call's lazy _tau takes it; a
+    per-pixel noise map: it lies in the batch's noise plane, _upload_noise_maps, and the scales with a non-zero sigma
+    run the updates that read it).
     `bilateral`: the transform's, for the sigma_e table (Coefficients.sigma_e, ref:122-124)."""
     sigma_e = scaling_function(2).sigma_e(bilateral=bilateral)
     nplanes = n_scales + 1
@@ -476,6 +576,7 @@ def _wow_batch_device(bp, nf, noises, scaling_function, n_scales, weights, white
     gplane = _GAMMA_PLANE if use_gamma else PLANE_NONE
     npix = float(bp.H) * float(bp.W)
     noises = list(noises)
+    maps = any(_is_noise_map(n, (bp.H, bp.W)) for n in noises)
     if use_gamma:
         bp.fill(nf, _GAMMA_PLANE, 0.0)                                              # ref:157-158
     for s, (_, w, d) in enumerate(zip(range(nplanes), recomposition_weights, sdc)):   # ref:174
@@ -486,10 +587,12 @@ def _wow_batch_device(bp, nf, noises, scaling_function, n_scales, weights, white
             bp.wow_update(nf, s, [0.0] * nf, soft_threshold, factors, gplane)
             continue
         taus, noises = _wow_taus(bp, nf, d, s, noises, sigma_e, soft_threshold)    # ref:199
+        # (a zero sigma: significance one, Coefficients._tau hands the per-frame update no noise plane either)
+        nkw = dict(noise_plane=_NOISE_PLANE) if maps and d != 0 else {}
         if whitening and h < 1:                                                     # ref:193-196 + 199-203
-            bp.wow_scale(nf, s, s, taus, soft_threshold, factors, gplane)
+            bp.wow_scale(nf, s, s, taus, soft_threshold, factors, gplane, **nkw)
         else:
-            bp.wow_update(nf, s, taus, soft_threshold, factors, gplane)
+            bp.wow_update(nf, s, taus, soft_threshold, factors, gplane, **nkw)
     bp.plane_sum(nf, 0, nplanes, PLANE_OUT)                                         # ref:205
     if use_gamma:                                                                   # ref:207-217
         need = gamma_min is None or gamma_max is None

@@ -47,6 +47,7 @@ struct wt_batch {
     // wow: WT_PLANE_SCRATCH(3) = the output plane of wt_batch_wow_scale (swapped with the coefficient plane, as
     // wt_wow_scale does), WT_PLANE_SCRATCH(4) = the gamma accumulator (utils.wow's plane ids)
     float *spare = nullptr, *gamma = nullptr;
+    float *noise = nullptr;         // WT_PLANE_SCRATCH(5): the per-pixel noise maps of the frames (Coefficients' noise plane id)
     // per-frame parameter pairs of one launch ({tau, factor}, {gmin, gmax}): a ring of table slots [n][2], pinned
     // staging + device copy; a slot is refilled only after the copy that last read it has completed (its event)
     static constexpr int kTabSlots = 16;
@@ -171,6 +172,39 @@ __global__ __launch_bounds__(256) void wt_batch_denoise_sum_kernel(BatchDenoiseA
     }
 }
 
+// wt_batch_denoise_sum_kernel with a per-pixel noise map (Coefficients.significance with an ndarray noise,
+// watroo/wavelets.py:133-141): nn comes from the batch's noise plane at the same flat index, as wt_denoise_sum_kernel
+// reads its noise plane.  A frame whose noise is a scalar has ones in its slot of the plane (tauf * 1.f and
+// t * 1.0 are exact).  Same arithmetic, contraction off: the bits of the per-frame call.
+__global__ __launch_bounds__(256) void wt_batch_denoise_sum_map_kernel(BatchDenoiseArgs a, const double *tau, const float *noise, float *out,
+                                                                       int64_t n4, int64_t f4)
+{
+#pragma clang fp contract(off)
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const double *ft = tau + (i / f4) * a.n_den;
+        const float4 nz = reinterpret_cast<const float4 *>(noise)[i];
+        const float nn[4] = {nz.x, nz.y, nz.z, nz.w};
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < a.n; ++k) {
+            const float4 v = reinterpret_cast<const float4 *>(a.p[k])[i];
+            float c[4] = {v.x, v.y, v.z, v.w};
+            if (k < a.n_den) {
+                const double t = ft[k];
+                const float tauf = (float)t;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float sgn = t > 0.0 ? wt_sig(c[j], tauf * nn[j], t * (double)nn[j], a.soft) : 1.f;
+                    c[j] = c[j] * (a.wgt[k] * sgn);
+                }
+                if (a.write_back) reinterpret_cast<float4 *>(a.p[k])[i] = make_float4(c[0], c[1], c[2], c[3]);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = k == 0 ? c[j] : acc[j] + c[j];
+        }
+        reinterpret_cast<float4 *>(out)[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    }
+}
+
 // wt_batch_denoise_sum_kernel with one WEIGHT row per frame as well (utils.enhance per channel, watroo/utils.py:60-78):
 // tab[frame * 2 * n_den + k] = tau, tab[frame * 2 * n_den + n_den + k] = the weight (a double, rounded to float here as
 // wt_denoise_sum rounds it on the host), the frame from the flat index.  Same arithmetic, contraction off: the bits of
@@ -228,6 +262,31 @@ __global__ __launch_bounds__(256) void wt_batch_wow_kernel(float *c, float *gamm
     }
 }
 
+// wt_batch_wow_kernel with a per-pixel noise map (watroo/utils.py:199 on an ndarray noise, wavelets.py:133-141): nn[k]
+// from the frame's slot of the batch's noise plane, as wt_wow_kernel reads its noise plane.  Same wt_wow_point.
+__global__ __launch_bounds__(256) void wt_batch_wow_map_kernel(float *c, const float *noise, float *gamma, int64_t f4, const double *ptab, int soft)
+{
+    const int f = blockIdx.y;
+    const double tau = ptab[2 * f];
+    const float tauf = (float)tau, factor = (float)ptab[2 * f + 1];
+    float4 *cf = reinterpret_cast<float4 *>(c) + (int64_t)f * f4;
+    const float4 *nf4 = reinterpret_cast<const float4 *>(noise) + (int64_t)f * f4;
+    float4 *gf = gamma ? reinterpret_cast<float4 *>(gamma) + (int64_t)f * f4 : nullptr;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < f4; i += (int64_t)gridDim.x * blockDim.x) {
+        const float4 v = cf[i];
+        const float4 nz = nf4[i];
+        float4 gm = make_float4(0, 0, 0, 0);
+        if (gf) gm = gf[i];
+        float in[4] = {v.x, v.y, v.z, v.w};
+        const float nn[4] = {nz.x, nz.y, nz.z, nz.w};
+        float gg[4] = {gm.x, gm.y, gm.z, gm.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) in[k] = wt_wow_point(in[k], 1.f, false, nn[k], tau, tauf, soft, factor, gg[k]);
+        cf[i] = make_float4(in[0], in[1], in[2], in[3]);
+        if (gf) gf[i] = make_float4(gg[0], gg[1], gg[2], gg[3]);
+    }
+}
+
 // wt_gamma_kernel (wt_kernels_apps.h, watroo/utils.py:212-217) with the frame as grid y and its own {gmin, gmax}
 __global__ __launch_bounds__(256) void wt_batch_gamma_kernel(float *recon, float *gamma, int64_t f4, const double *ptab, float inv_gamma, float h)
 {
@@ -264,6 +323,14 @@ __global__ __launch_bounds__(256) void wt_batch_fill_kernel(float *d, int64_t n4
         reinterpret_cast<float4 *>(d)[i] = make_float4(value, value, value, value);
 }
 
+// frame 0 of a plane -> frames 1 .. gridDim.y (a noise map shared by the frames of a chunk crosses PCIe once)
+__global__ __launch_bounds__(256) void wt_batch_replicate_kernel(float *d, int64_t f4)
+{
+    const float4 *src = reinterpret_cast<const float4 *>(d);
+    float4 *dst = reinterpret_cast<float4 *>(d) + (int64_t)(blockIdx.y + 1) * f4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < f4; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i];
+}
+
 // wt_reduce_kernel + wt_reduce_final_kernel per frame (grid y / the final block = the frame): the per-frame
 // work split (gridDim.x blocks) and fold order of wt_reduce.h, i.e. the doubles of the per-frame call
 #define WT_REDUCE_KERNEL_NAME wt_batch_reduce_kernel
@@ -287,7 +354,8 @@ static int bplane(wt_batch *b, int id, float **out)
     else if (id == WT_PLANE_SCRATCH(1)) slot = &b->scr[1];
     else if (id == WT_PLANE_SCRATCH(3)) slot = &b->spare;
     else if (id == WT_PLANE_SCRATCH(4)) slot = &b->gamma;
-    if (!slot) WT_FAIL("wt_batch: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1/3/4)", id, b->max_level);
+    else if (id == WT_PLANE_SCRATCH(5)) slot = &b->noise;
+    if (!slot) WT_FAIL("wt_batch: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1/3/4/5)", id, b->max_level);
     if (!*slot) WT_HIP(hipMalloc((void **)slot, (size_t)b->n * (size_t)b->fstride * sizeof(float)));
     *out = *slot;
     return 0;
@@ -470,6 +538,7 @@ extern "C" int wt_batch_destroy(wt_batch *b)
     f(b->d_tau);
     f(b->spare);
     f(b->gamma);
+    f(b->noise);
     f(b->d_ptab);
     f(b->d_red);
     if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) bad = 1;
@@ -672,35 +741,58 @@ extern "C" int wt_batch_abs_median(wt_batch *b, int nf, int plane, float *median
     return 0;
 }
 
-extern "C" int wt_batch_denoise_sum(wt_batch *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
-                                    int write_back)
+// wt_batch_denoise_sum / wt_batch_denoise_sum_map: noise_plane == WT_PLANE_NONE runs the kernel without a map
+static int batch_denoise_sum(wt_batch *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft, int write_back,
+                             int noise_plane, const char *who)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_denoise_sum"));
+    WT_TRY(check_frames(b, nf, who));
     WtGuard guard_(b->ctx);
     if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > b->max_level)
-        WT_FAIL("wt_batch_denoise_sum: count %d out of range [1,%d]", count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
-    if (n_den < 0 || n_den > count) WT_FAIL("wt_batch_denoise_sum: n_den %d outside [0,%d]", n_den, count);
-    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("wt_batch_denoise_sum: null tau/wgt");
-    if (dst >= 0 && dst < count) WT_FAIL("wt_batch_denoise_sum: dst plane %d is one of the summed planes", dst);
+        WT_FAIL("%s: count %d out of range [1,%d]", who, count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
+    if (n_den < 0 || n_den > count) WT_FAIL("%s: n_den %d outside [0,%d]", who, n_den, count);
+    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("%s: null tau/wgt", who);
+    if (dst >= 0 && dst < count) WT_FAIL("%s: dst plane %d is one of the summed planes", who, dst);
+    if (noise_plane != WT_PLANE_NONE && (noise_plane == dst || (noise_plane >= 0 && noise_plane < count)))
+        WT_FAIL("%s: the noise plane %d is a plane of the sum", who, noise_plane);
     BatchDenoiseArgs a{};
     a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
     for (int i = 0; i < count; ++i) {
         WT_TRY(bplane(b, i, &a.p[i]));
         a.wgt[i] = i < n_den ? (float)wgt[i] : 1.f;
     }
-    float *o = nullptr;
+    float *o = nullptr, *nz = nullptr;
     WT_TRY(bplane(b, dst, &o));
+    if (noise_plane != WT_PLANE_NONE) WT_TRY(bplane(b, noise_plane, &nz));
     const int nt = std::max(n_den, 1);
     // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
     WT_HIP(hipStreamSynchronize(b->ctx->stream));
     for (int i = 0; i < nf * nt; ++i) b->h_tau[i] = n_den ? tau[i] : 0.0;
     WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * nt * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
     const int64_t n4 = (int64_t)nf * b->fstride / 4;
-    ProfScope ps(b->ctx, "wt_batch_denoise_sum_kernel");
-    hipLaunchKernelGGL(wt_batch_denoise_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, b->ctx->stream, a, (const double *)b->d_tau,
-                       o, n4, b->fstride / 4);
+    if (nz) {
+        ProfScope ps(b->ctx, "wt_batch_denoise_sum_map_kernel");
+        hipLaunchKernelGGL(wt_batch_denoise_sum_map_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, b->ctx->stream, a,
+                           (const double *)b->d_tau, (const float *)nz, o, n4, b->fstride / 4);
+    } else {
+        ProfScope ps(b->ctx, "wt_batch_denoise_sum_kernel");
+        hipLaunchKernelGGL(wt_batch_denoise_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, b->ctx->stream, a,
+                           (const double *)b->d_tau, o, n4, b->fstride / 4);
+    }
     WT_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int wt_batch_denoise_sum(wt_batch *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
+                                    int write_back)
+{
+    return batch_denoise_sum(b, nf, count, dst, n_den, tau, wgt, soft, write_back, WT_PLANE_NONE, "wt_batch_denoise_sum");
+}
+
+extern "C" int wt_batch_denoise_sum_map(wt_batch *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
+                                        int write_back, int noise_plane)
+{
+    if (noise_plane == WT_PLANE_NONE) WT_FAIL("wt_batch_denoise_sum_map: no noise plane (wt_batch_denoise_sum is the call without a map)");
+    return batch_denoise_sum(b, nf, count, dst, n_den, tau, wgt, soft, write_back, noise_plane, "wt_batch_denoise_sum_map");
 }
 
 extern "C" int wt_batch_enhance_sum(wt_batch *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
@@ -760,6 +852,20 @@ extern "C" int wt_batch_fill(wt_batch *b, int nf, int plane, float value)
     return 0;
 }
 
+extern "C" int wt_batch_replicate(wt_batch *b, int nf, int plane)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_replicate"));
+    WtGuard guard_(b->ctx);
+    float *d = nullptr;
+    WT_TRY(bplane(b, plane, &d));
+    if (nf == 1) return 0;
+    const int64_t f4 = b->fstride / 4;
+    ProfScope ps(b->ctx, "wt_batch_replicate_kernel");
+    hipLaunchKernelGGL(wt_batch_replicate_kernel, dim3(batch_flat_blocks(b, nf), nf - 1), dim3(256), 0, b->ctx->stream, d, f4);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
 // frame f of the plane <- the field wt_fill_normal(seed, first_trial + f) gives a wt_plan of the frame's shape
 extern "C" int wt_batch_fill_normal(wt_batch *b, int nf, int plane, uint64_t seed, uint32_t first_trial)
 {
@@ -781,46 +887,85 @@ static int wow_pairs(wt_batch *b, int nf, const double *tau, const float *factor
     return batch_table(b, nf, pairs.data(), dev);
 }
 
-extern "C" int wt_batch_wow_update(wt_batch *b, int nf, int plane, const double *tau, int soft, const float *factor, int gamma_plane)
+// wt_batch_wow_update / wt_batch_wow_update_map: noise_plane == WT_PLANE_NONE runs the kernel without a map
+static int batch_wow_update(wt_batch *b, int nf, int plane, const double *tau, int soft, const float *factor, int gamma_plane, int noise_plane,
+                            const char *who)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_wow_update"));
+    WT_TRY(check_frames(b, nf, who));
     WtGuard guard_(b->ctx);
-    if (gamma_plane == plane) WT_FAIL("wt_batch_wow_update: the gamma plane is the updated plane");
-    float *c = nullptr, *gm = nullptr;
+    if (gamma_plane == plane) WT_FAIL("%s: the gamma plane is the updated plane", who);
+    if (noise_plane != WT_PLANE_NONE && (noise_plane == plane || noise_plane == gamma_plane)) WT_FAIL("%s: the noise plane aliases a plane of the update", who);
+    float *c = nullptr, *gm = nullptr, *nz = nullptr;
     WT_TRY(bplane(b, plane, &c));
     if (gamma_plane != WT_PLANE_NONE) WT_TRY(bplane(b, gamma_plane, &gm));
+    if (noise_plane != WT_PLANE_NONE) WT_TRY(bplane(b, noise_plane, &nz));
     const double *dt = nullptr;
-    WT_TRY(wow_pairs(b, nf, tau, factor, &dt, "wt_batch_wow_update"));
-    ProfScope ps(b->ctx, "wt_batch_wow_kernel");
-    hipLaunchKernelGGL(wt_batch_wow_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, c, gm, b->fstride / 4, dt, soft);
+    WT_TRY(wow_pairs(b, nf, tau, factor, &dt, who));
+    if (nz) {
+        ProfScope ps(b->ctx, "wt_batch_wow_map_kernel");
+        hipLaunchKernelGGL(wt_batch_wow_map_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, c, (const float *)nz, gm,
+                           b->fstride / 4, dt, soft);
+    } else {
+        ProfScope ps(b->ctx, "wt_batch_wow_kernel");
+        hipLaunchKernelGGL(wt_batch_wow_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, c, gm, b->fstride / 4, dt, soft);
+    }
     WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch_wow_update(wt_batch *b, int nf, int plane, const double *tau, int soft, const float *factor, int gamma_plane)
+{
+    return batch_wow_update(b, nf, plane, tau, soft, factor, gamma_plane, WT_PLANE_NONE, "wt_batch_wow_update");
+}
+
+extern "C" int wt_batch_wow_update_map(wt_batch *b, int nf, int plane, const double *tau, int soft, const float *factor, int gamma_plane,
+                                       int noise_plane)
+{
+    if (noise_plane == WT_PLANE_NONE) WT_FAIL("wt_batch_wow_update_map: no noise plane (wt_batch_wow_update is the call without a map)");
+    return batch_wow_update(b, nf, plane, tau, soft, factor, gamma_plane, noise_plane, "wt_batch_wow_update_map");
+}
+
+// wt_batch_wow_scale / wt_batch_wow_scale_map: noise_plane == WT_PLANE_NONE runs the instantiations without a map
+static int batch_wow_scale(wt_batch *b, int nf, int plane, int s, const double *tau, int soft, const float *factor, int gamma_plane, int noise_plane,
+                           const char *who)
+{
+    WT_TRY(check_frames(b, nf, who));
+    WtGuard guard_(b->ctx);
+    if (plane < 0 || plane > b->max_level) WT_FAIL("%s: plane %d is not a coefficient plane", who, plane);
+    if (s < 0 || s > 24) WT_FAIL("%s: scale %d out of range", who, s);
+    if (gamma_plane == plane || gamma_plane == WT_PLANE_SCRATCH(3)) WT_FAIL("%s: the gamma plane aliases a plane of the update", who);
+    if (noise_plane != WT_PLANE_NONE && (noise_plane == plane || noise_plane == WT_PLANE_SCRATCH(3) || noise_plane == gamma_plane))
+        WT_FAIL("%s: the noise plane aliases a plane of the update", who);
+    float *c = nullptr, *t = nullptr, *gm = nullptr, *nz = nullptr;
+    WT_TRY(bplane(b, plane, &c));
+    WT_TRY(bplane(b, WT_PLANE_SCRATCH(3), &t));
+    if (gamma_plane != WT_PLANE_NONE) WT_TRY(bplane(b, gamma_plane, &gm));
+    if (noise_plane != WT_PLANE_NONE) WT_TRY(bplane(b, noise_plane, &nz));
+    const double *dt = nullptr;
+    WT_TRY(wow_pairs(b, nf, tau, factor, &dt, who));
+    // (wt_wow_scale's arguments and its choice of instantiation; tau and factor come from the frame's row of the table)
+    ChainArgs a{};
+    a.in = c; a.out_c = t; a.out_w = nullptr; a.aux = nullptr;
+    a.noise = nz; a.gamma = gm; a.soft = soft; a.whiten = 1;
+    WtFrames fr;
+    fr.n = nf;
+    fr.fstride = b->fstride;
+    fr.ftab = dt;
+    WT_TRY(wt32_stencil_batch_launch(batch_stencil_ctx(b), nz ? MODE_WOW : (gm ? MODE_WOW_GAMMA : MODE_WOW_PLAIN), a, s, "wt_chain_batch_kernel<wow>", fr));
+    std::swap(b->coef[plane], b->spare);          // (wt_wow_scale: "in place" at pointer level)
     return 0;
 }
 
 extern "C" int wt_batch_wow_scale(wt_batch *b, int nf, int plane, int s, const double *tau, int soft, const float *factor, int gamma_plane)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_wow_scale"));
-    WtGuard guard_(b->ctx);
-    if (plane < 0 || plane > b->max_level) WT_FAIL("wt_batch_wow_scale: plane %d is not a coefficient plane", plane);
-    if (s < 0 || s > 24) WT_FAIL("wt_batch_wow_scale: scale %d out of range", s);
-    if (gamma_plane == plane || gamma_plane == WT_PLANE_SCRATCH(3)) WT_FAIL("wt_batch_wow_scale: the gamma plane aliases a plane of the update");
-    float *c = nullptr, *t = nullptr, *gm = nullptr;
-    WT_TRY(bplane(b, plane, &c));
-    WT_TRY(bplane(b, WT_PLANE_SCRATCH(3), &t));
-    if (gamma_plane != WT_PLANE_NONE) WT_TRY(bplane(b, gamma_plane, &gm));
-    const double *dt = nullptr;
-    WT_TRY(wow_pairs(b, nf, tau, factor, &dt, "wt_batch_wow_scale"));
-    // (wt_wow_scale's arguments; tau and factor come from the frame's row of the table)
-    ChainArgs a{};
-    a.in = c; a.out_c = t; a.out_w = nullptr; a.aux = nullptr;
-    a.noise = nullptr; a.gamma = gm; a.soft = soft; a.whiten = 1;
-    WtFrames fr;
-    fr.n = nf;
-    fr.fstride = b->fstride;
-    fr.ftab = dt;
-    WT_TRY(wt32_stencil_batch_launch(batch_stencil_ctx(b), gm ? MODE_WOW_GAMMA : MODE_WOW_PLAIN, a, s, "wt_chain_batch_kernel<wow>", fr));
-    std::swap(b->coef[plane], b->spare);          // (wt_wow_scale: "in place" at pointer level)
-    return 0;
+    return batch_wow_scale(b, nf, plane, s, tau, soft, factor, gamma_plane, WT_PLANE_NONE, "wt_batch_wow_scale");
+}
+
+extern "C" int wt_batch_wow_scale_map(wt_batch *b, int nf, int plane, int s, const double *tau, int soft, const float *factor, int gamma_plane,
+                                      int noise_plane)
+{
+    if (noise_plane == WT_PLANE_NONE) WT_FAIL("wt_batch_wow_scale_map: no noise plane (wt_batch_wow_scale is the call without a map)");
+    return batch_wow_scale(b, nf, plane, s, tau, soft, factor, gamma_plane, noise_plane, "wt_batch_wow_scale_map");
 }
 
 extern "C" int wt_batch_reduce(wt_batch *b, int nf, int plane, double *out)

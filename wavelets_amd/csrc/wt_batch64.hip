@@ -37,6 +37,7 @@ struct wt_batch64 {
     int64_t fstride = 0;            // doubles from one frame to the next (H * P)
     std::vector<double *> coef;     // planes 0 .. max_level
     double *input = nullptr, *out = nullptr, *scr[2] = {nullptr, nullptr};
+    double *noise = nullptr;        // WT_PLANE_SCRATCH(5): the per-pixel noise maps of the frames (Coefficients' noise plane id)
     void *istage = nullptr;         // frames of another element type on their way into a plane
     size_t istage_cap = 0;
     uint32_t *d_hist = nullptr;     // [n][2 ranks][WT_HIST_BINS] (allocated by the first median)
@@ -152,6 +153,55 @@ __global__ __launch_bounds__(256) void wt_batch64_denoise_sum_kernel(Batch64Deno
     }
 }
 
+// wt_batch64_denoise_sum_kernel with a per-pixel noise map (Coefficients.significance with an ndarray noise,
+// watroo/wavelets.py:133-141), the batched twin of wt64_denoise_sum_kernel with its `noise` operand: a frame with a map
+// thresholds at tau * nz by the quotient (wt_sig64), as the per-frame kernel does with a noise plane; a frame whose
+// noise is a scalar (tab[frame * row + 2 * n_den] == 0: no map) keeps the reciprocal form of the map-free kernel
+// (wt_sig64_inv) - the two differ by a rounding, so each frame takes the form its per-frame call takes.
+// tab[frame * row + k] = tau, [+ n_den + k] = 1 / tau, [+ 2 * n_den] = 1.0 for a frame with a map; row = 2 * n_den + 1.
+__global__ __launch_bounds__(256) void wt_batch64_denoise_sum_map_kernel(Batch64DenoiseArgs a, const double *tab, const double *noise, double *dst,
+                                                                         int64_t n2, int64_t f2)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (int64_t)gridDim.x * 256) {
+        const double *ft = tab + (i / f2) * (2 * a.n_den + 1);
+        const bool mapped = ft[2 * a.n_den] != 0.0;
+        const double2 nz = reinterpret_cast<const double2 *>(noise)[i];
+        double2 acc = make_double2(0.0, 0.0);
+        for (int k = 0; k < a.n; ++k) {
+            const wt_b64_ntd2 raw = __builtin_nontemporal_load(reinterpret_cast<const wt_b64_ntd2 *>(a.p[k]) + i);   // (read exactly once)
+            double2 v = make_double2(raw.x, raw.y);
+            if (k < a.n_den) {
+                const double tau = ft[k], inv_tau = ft[a.n_den + k];
+                double2 sg = make_double2(1.0, 1.0);
+                if (tau > 0.0) {
+                    if (mapped) sg = make_double2(wt_sig64(v.x, tau * nz.x, a.soft), wt_sig64(v.y, tau * nz.y, a.soft));
+                    else sg = make_double2(wt_sig64_inv(v.x, tau, inv_tau, a.soft), wt_sig64_inv(v.y, tau, inv_tau, a.soft));
+                }
+                v = make_double2(v.x * (a.wgt[k] * sg.x), v.y * (a.wgt[k] * sg.y));
+                if (a.write_back) reinterpret_cast<double2 *>(a.p[k])[i] = v;
+            }
+            acc = k == 0 ? v : make_double2(acc.x + v.x, acc.y + v.y);
+        }
+        __builtin_nontemporal_store((wt_b64_ntd2){acc.x, acc.y}, reinterpret_cast<wt_b64_ntd2 *>(dst) + i);
+    }
+}
+
+// plane <- value over the active frames, pitch padding included (the noise plane before the maps go up: no lane
+// computes on what hipMalloc left there)
+__global__ __launch_bounds__(256) void wt_batch64_fill_kernel(double *d, int64_t n2, double value)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (int64_t)gridDim.x * 256)
+        reinterpret_cast<double2 *>(d)[i] = make_double2(value, value);
+}
+
+// frame 0 of a plane -> frames 1 .. gridDim.y (a noise map shared by the frames of a chunk crosses PCIe once)
+__global__ __launch_bounds__(256) void wt_batch64_replicate_kernel(double *d, int64_t f2)
+{
+    const double2 *src = reinterpret_cast<const double2 *>(d);
+    double2 *dst = reinterpret_cast<double2 *>(d) + (int64_t)(blockIdx.y + 1) * f2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < f2; i += (int64_t)gridDim.x * 256) dst[i] = src[i];
+}
+
 // wt_batch64_denoise_sum_kernel with one WEIGHT row per frame as well (utils.enhance per channel, watroo/utils.py:60-78):
 // tab[frame * 3 * n_den + k] = tau, [+ n_den + k] = 1 / tau (the host's IEEE division), [+ 2 * n_den + k] = the weight.
 // Same expressions and accesses: the bits of the per-frame call.
@@ -235,7 +285,8 @@ static int b64plane(wt_batch64 *b, int id, double **out)
     else if (id == WT_PLANE_OUT) slot = &b->out;
     else if (id == WT_PLANE_SCRATCH(0)) slot = &b->scr[0];
     else if (id == WT_PLANE_SCRATCH(1)) slot = &b->scr[1];
-    if (!slot) WT_FAIL("wt_batch64: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1)", id, b->max_level);
+    else if (id == WT_PLANE_SCRATCH(5)) slot = &b->noise;
+    if (!slot) WT_FAIL("wt_batch64: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1/5)", id, b->max_level);
     if (!*slot) WT_HIP(hipMalloc((void **)slot, (size_t)b->n * (size_t)b->fstride * sizeof(double)));
     *out = *slot;
     return 0;
@@ -333,6 +384,7 @@ static void batch64_free(wt_batch64 *b, int *bad)
     f(b->out);
     f(b->scr[0]);
     f(b->scr[1]);
+    f(b->noise);
     f(b->istage);
     f(b->d_hist);
     f(b->d_sel);
@@ -711,6 +763,76 @@ extern "C" int wt_batch64_denoise_sum(wt_batch64 *b, int nf, int count, int dst,
     ProfScope ps(b->ctx, "wt_batch64_denoise_sum_kernel");
     hipLaunchKernelGGL(wt_batch64_denoise_sum_kernel, dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8)), dim3(256), 0,
                        b->ctx->stream, a, (const double *)b->d_tau, o, n2, b->fstride / 2);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch64_denoise_sum_map(wt_batch64 *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
+                                          int write_back, int noise_plane, const int *has_map)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_denoise_sum_map"));
+    WtGuard guard_(b->ctx);
+    if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > b->max_level)
+        WT_FAIL("wt_batch64_denoise_sum_map: count %d out of range [1,%d]", count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
+    if (n_den < 0 || n_den > count) WT_FAIL("wt_batch64_denoise_sum_map: n_den %d outside [0,%d]", n_den, count);
+    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("wt_batch64_denoise_sum_map: null tau/wgt");
+    if (dst >= 0 && dst < count) WT_FAIL("wt_batch64_denoise_sum_map: dst plane %d is one of the summed planes", dst);
+    if (noise_plane == WT_PLANE_NONE) WT_FAIL("wt_batch64_denoise_sum_map: no noise plane (wt_batch64_denoise_sum is the call without a map)");
+    if (noise_plane == dst || (noise_plane >= 0 && noise_plane < count)) WT_FAIL("wt_batch64_denoise_sum_map: the noise plane %d is a plane of the sum", noise_plane);
+    Batch64DenoiseArgs a{};
+    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
+    for (int i = 0; i < count; ++i) {
+        WT_TRY(b64plane(b, i, &a.p[i]));
+        a.wgt[i] = i < n_den ? wgt[i] : 1.0;
+    }
+    double *o = nullptr, *nz = nullptr;
+    WT_TRY(b64plane(b, dst, &o));
+    WT_TRY(b64plane(b, noise_plane, &nz));
+    // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
+    WT_HIP(hipStreamSynchronize(b->ctx->stream));
+    const int row = 2 * n_den + 1;                          // nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables
+    for (int f = 0; f < nf; ++f) {
+        for (int k = 0; k < n_den; ++k) {
+            const double t = tau[f * n_den + k];
+            b->h_tau[f * row + k] = t;
+            b->h_tau[f * row + n_den + k] = t > 0.0 ? 1.0 / t : 0.0;       // (wt64_denoise_sum's inv_tau)
+        }
+        b->h_tau[f * row + 2 * n_den] = (!has_map || has_map[f]) ? 1.0 : 0.0;
+    }
+    WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * row * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    const int64_t n2 = (int64_t)nf * b->fstride / 2;
+    ProfScope ps(b->ctx, "wt_batch64_denoise_sum_map_kernel");
+    hipLaunchKernelGGL(wt_batch64_denoise_sum_map_kernel, dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8)), dim3(256), 0,
+                       b->ctx->stream, a, (const double *)b->d_tau, (const double *)nz, o, n2, b->fstride / 2);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch64_fill(wt_batch64 *b, int nf, int plane, double value)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_fill"));
+    WtGuard guard_(b->ctx);
+    double *d = nullptr;
+    WT_TRY(b64plane(b, plane, &d));
+    const int64_t n2 = (int64_t)nf * b->fstride / 2;
+    ProfScope ps(b->ctx, "wt_batch64_fill_kernel");
+    hipLaunchKernelGGL(wt_batch64_fill_kernel, dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8)), dim3(256), 0, b->ctx->stream, d, n2,
+                       value);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch64_replicate(wt_batch64 *b, int nf, int plane)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_replicate"));
+    WtGuard guard_(b->ctx);
+    double *d = nullptr;
+    WT_TRY(b64plane(b, plane, &d));
+    if (nf == 1) return 0;
+    const int64_t f2 = b->fstride / 2;
+    const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((f2 + 255) / 256, (2048 + nf - 1) / nf));
+    ProfScope ps(b->ctx, "wt_batch64_replicate_kernel");
+    hipLaunchKernelGGL(wt_batch64_replicate_kernel, dim3(bx, nf - 1), dim3(256), 0, b->ctx->stream, d, f2);
     WT_HIP(hipGetLastError());
     return 0;
 }

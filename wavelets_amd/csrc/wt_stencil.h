@@ -454,7 +454,7 @@ struct RowArgsT {
 typedef RowArgsT<float> RowArgs;
 
 // A batch of frames (wt_batch): the arguments of frame 0, the distance between two frames' planes and the
-// per-frame {tau, factor} pairs of the wow modes.  The batched kernels move every plane pointer by
+// per-frame {tau, factor} pairs of the wow modes.  The batched kernels move every plane pointer (the noise map's too) by
 // blockIdx.z * fstride and read their frame's pair once, at the start of the workgroup.
 template <typename A>
 struct WtFrameArgs {
@@ -472,6 +472,7 @@ __device__ __forceinline__ ChainArgsT<T> wt_frame_move(ChainArgsT<T> a, int64_t 
     a.out_c += o;
     if (a.out_w) a.out_w += o;
     if (a.gamma) a.gamma += o;
+    if (a.noise) a.noise += o;
     if constexpr (WT_IS_WOW(MODE)) {
         a.tau = ftab[2 * f];
         a.factor = (T)ftab[2 * f + 1];

@@ -212,7 +212,7 @@ static int wt_launch_stencil(const StencilCtx &sc, ChainArgsT<T> a, int s, const
 // ---------------------------------------------------------------------------------------------
 // one scale in `mode` (MODE_*) on float planes; `name`: profiler name of the chain kernel
 int wt32_stencil_launch(const StencilCtx &sc, int mode, const ChainArgsT<float> &a, int s, const char *name);
-// one scale in `mode` (MODE_DECOMP, MODE_WOW_PLAIN, MODE_WOW_GAMMA) on the float planes of the frames `fr` of a batch
+// one scale in `mode` (MODE_DECOMP, MODE_WOW_PLAIN, MODE_WOW_GAMMA, MODE_WOW with a.noise) on the float planes of the frames `fr` of a batch
 // (wt_stencil32_batch.hip): every frame as wt32_stencil_launch would run it alone, one launch
 int wt32_stencil_batch_launch(const StencilCtx &sc, int mode, const ChainArgsT<float> &a, int s, const char *name, const WtFrames &fr);
 // one scale of the float32 bilateral transform (variance in the kernel, a.f1 / a.f2) on the frames `fr` of a batch

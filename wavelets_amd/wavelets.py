@@ -646,6 +646,27 @@ def _scalar_tau(sigma, noise, sigma_e_scale, soft=True):
     return tau, PLANE_NONE
 
 
+def _map_tau(sigma, sigma_e_scale, soft=True):
+    """Coefficients._tau for a per-pixel noise map (an ndarray noise, ref:133-141): (tau, _NOISE_PLANE) - the
+    kernels threshold pixel i at tau * map[i] - or None when the significance is identically one (sigma == 0,
+    ref:142-143; a negative hard threshold)"""
+    if sigma == 0:
+        return None
+    tau = float(sigma * sigma_e_scale)
+    if tau < 0 and not soft:
+        return None
+    return abs(tau), _NOISE_PLANE
+
+
+def _map_tau_row(entries, sigma_e, soft):
+    """_tau_row for a frame whose noise is a per-pixel map (_map_tau): 0.0 = significance one"""
+    row = []
+    for scl, sig, _ in entries:
+        t = _map_tau(sig, sigma_e[scl], soft)
+        row.append(0.0 if t is None else t[0])
+    return row
+
+
 def _tau_row(entries, noise, sigma_e, soft):
     """One image's (or one frame's) row of thresholds over the (scale, sigma, weight) `entries` for a scalar
     noise level (Coefficients._tau, ref:129-143): 0.0 = significance one"""
@@ -863,10 +884,7 @@ class Coefficients:
                 self._as_plane(np.asarray(self.noise, np.float64 if isinstance(plan, Plan64) else np.float32)),
                 plan.shape))
             self._noise_uploaded = self.noise
-        tau = float(sigma * self.sigma_e[scale])
-        if tau < 0 and not soft:
-            return None
-        return abs(tau), _NOISE_PLANE
+        return _map_tau(sigma, self.sigma_e[scale], soft)
 
     def _threshold_row(self, entries, soft):
         """(taus, wgts, noise_plane) of the (scale, sigma, weight) `entries` for wt_denoise_sum: _tau per entry
