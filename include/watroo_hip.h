@@ -682,8 +682,9 @@ int wt_batch_plane_sum(wt_batch *batch, int nf, int first, int count, int dst);
  * N frames back to back at the pitch of a wt_plan64 of that width (frame f at f * frame_stride doubles).  Every
  * frame runs the per-frame float64 schedule, kernel choice and geometry with the frame as grid z, so a frame's
  * result is bit-identical to the per-frame call on a wt_plan64.  Images (H >= 2) with a built-in family only;
- * the transforms need an all-fused float64 schedule (wt_batch64_fused_ok).  Planes: 0..max_level,
- * WT_PLANE_INPUT, WT_PLANE_OUT, WT_PLANE_SCRATCH(0/1) (used internally).  Operations take the number of ACTIVE
+ * the transforms with a plane sum need an all-fused float64 schedule (wt_batch64_fused_ok), the plain transform
+ * also takes the schedules of wt_batch64_wow_ok.  Planes: 0..max_level, WT_PLANE_INPUT, WT_PLANE_OUT,
+ * WT_PLANE_SCRATCH(0/1) (used internally), WT_PLANE_SCRATCH(3/4/5) (wow, noise maps).  Operations take the number of ACTIVE
  * frames nf (frames 0 .. nf-1). */
 typedef struct wt_batch64 wt_batch64;
 /* host logic: *ok = 1 when H x W frames of `family` have an all-fused float64 schedule of `level` scales
@@ -749,6 +750,45 @@ int wt_batch64_replicate(wt_batch64 *batch, int nf, int plane);
 /* generalized_anscombe over the active frames (watroo/utils.py:93-94, 99-100; as wt64_anscombe) */
 int wt_batch64_anscombe(wt_batch64 *batch, int nf, int src, int dst, double alpha, double g, double sigma,
                         int inverse);
+/* ---- wow over a float64 batch (watroo/utils.py:105-219, utils.wow per frame on a wt_plan64): the float64 twins of
+ * the wt_batch_wow_* entries, `double` where those have `float`.  Extra planes: WT_PLANE_SCRATCH(3), the output plane
+ * of wt_batch64_wow_scale, WT_PLANE_SCRATCH(4), wow's gamma accumulator, WT_PLANE_SCRATCH(5), the per-pixel noise
+ * maps of the *_map entries.  Per-frame parameters are arrays of nf entries; every frame gets the bits of the
+ * per-frame call.  wt_batch64_decompose serves wow's transform: levels 1..24 where wt_batch64_wow_ok, the single-scale
+ * passes without a fused kernel on the batched per-scale stencil (watroo/wavelets.py:408-444). */
+/* host logic: *ok = 1 when wow over H x W frames of `family` with `level` scales (1..24) runs on the batch: an image
+ * (H >= 2) with rows wt_batch64_create accepts, a float64 schedule (watroo/wavelets.py:408-444) of fused passes and
+ * single-scale passes, and option "stencil64" on - with it off wt64_decompose and wt64_wow_scale take the generic
+ * kernels per frame, whose bits differ.  wt_batch64_fused_ok keeps its narrower meaning */
+int wt_batch64_wow_ok(int family, int64_t H, int64_t W, int level, int *ok);
+/* wt64_wow_update per frame without a power plane or noise map (watroo/utils.py:185-191 with local_power = 1,
+ * 199-203): wow's last plane, whitening=False and h >= 1; tau[f] <= 0: significance one; gamma_plane may be
+ * WT_PLANE_NONE */
+int wt_batch64_wow_update(wt_batch64 *batch, int nf, int plane, const double *tau, int soft, const double *factor,
+                          int gamma_plane);
+/* wt64_wow_scale per frame, scalar noise (watroo/utils.py:192-203): local power conv_s(c^2), significance, gamma sum
+ * and whitening of plane `plane` at scale s in one batched stencil launch; the result goes to WT_PLANE_SCRATCH(3)
+ * and the two planes' buffers are swapped */
+int wt_batch64_wow_scale(wt_batch64 *batch, int nf, int plane, int s, const double *tau, int soft,
+                         const double *factor, int gamma_plane);
+/* wt_batch64_wow_update with a per-pixel noise map per frame (watroo/utils.py:199 on an ndarray noise,
+ * wavelets.py:133-141; wt64_wow_update with its noise_plane): noise_plane as in wt_batch64_denoise_sum_map, ones in
+ * the slot of a frame with a scalar level */
+int wt_batch64_wow_update_map(wt_batch64 *batch, int nf, int plane, const double *tau, int soft,
+                              const double *factor, int gamma_plane, int noise_plane);
+/* wt_batch64_wow_scale with a per-pixel noise map per frame (watroo/utils.py:192-203 on an ndarray noise,
+ * wavelets.py:133-141; wt64_wow_scale with its noise_plane) */
+int wt_batch64_wow_scale_map(wt_batch64 *batch, int nf, int plane, int s, const double *tau, int soft,
+                             const double *factor, int gamma_plane, int noise_plane);
+/* wt64_reduce per frame ({sum, sumsq, min, max}, the per-frame call's doubles; np.std / np.mean(c**2) of
+ * watroo/utils.py:178-189, gamma_scaled.min / max of utils.py:208-211): out[4 * nf], one host round trip */
+int wt_batch64_reduce(wt_batch64 *batch, int nf, int plane, double *out);
+/* wt64_gamma_blend per frame (watroo/utils.py:212-217) with the frame's gmin[f] / gmax[f] */
+int wt_batch64_gamma_blend(wt_batch64 *batch, int nf, int recon, int gamma_plane, const double *gmin,
+                           const double *gmax, double inv_gamma, double h);
+/* wt64_plane_sum per frame: dst = planes [first, first + count) summed in plane order (np.sum(coefficients, axis=0),
+ * watroo/utils.py:205); count <= 32 */
+int wt_batch64_plane_sum(wt_batch64 *batch, int nf, int first, int count, int dst);
 
 #ifdef __cplusplus
 }

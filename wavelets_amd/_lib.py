@@ -261,6 +261,19 @@ SIGNATURES = {
     "wt_batch64_replicate": (_c.c_int, [_vp, _c.c_int, _c.c_int]),
     "wt_batch64_anscombe": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_double, _c.c_double,
                                        _c.c_int]),
+    "wt_batch64_wow_ok": (_c.c_int, [_c.c_int, _i64, _i64, _c.c_int, _c.POINTER(_c.c_int)]),
+    "wt_batch64_wow_update": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int,
+                                         _c.POINTER(_c.c_double), _c.c_int]),
+    "wt_batch64_wow_scale": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int,
+                                        _c.POINTER(_c.c_double), _c.c_int]),
+    "wt_batch64_wow_update_map": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int,
+                                             _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
+    "wt_batch64_wow_scale_map": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int,
+                                            _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
+    "wt_batch64_reduce": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double)]),
+    "wt_batch64_gamma_blend": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
+                                          _c.POINTER(_c.c_double), _c.c_double, _c.c_double]),
+    "wt_batch64_plane_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
 }
 
 _lib = None
@@ -1161,6 +1174,15 @@ def batch64_bilateral_ok(family, H, W, level):
     return bool(ok.value)
 
 
+def batch64_wow_ok(family, H, W, level):
+    """True when wow over H x W frames of `family` with `level` scales runs on the float64 batch (host logic,
+    wt_batch64_wow_ok: 1..24 scales, fused passes or single-scale stencil passes, option "stencil64" on) - the frames
+    BatchPlan64.decompose and BatchPlan64.wow_scale reproduce bit for bit"""
+    ok = _c.c_int(0)
+    check(load().wt_batch64_wow_ok(int(family), int(H), int(W), int(level), _c.byref(ok)))
+    return bool(ok.value)
+
+
 class BatchPlan64:
     """Double-precision planes of up to `n` frames of one H x W shape (wt_batch64): BatchPlan's operations for the
     stacks the reference computes in float64.  upload / download move a C-contiguous (nf, H, W) block; integer
@@ -1275,6 +1297,43 @@ class BatchPlan64:
 
     def anscombe(self, nf, src, dst, alpha=1.0, g=0.0, sigma=0.0, inverse=False):
         check(load().wt_batch64_anscombe(self._h, nf, src, dst, alpha, g, sigma, int(inverse)))
+
+    # -- wow (wt_batch64_wow_*): BatchPlan's methods, the per-frame parameters as doubles
+    _per_frame = staticmethod(BatchPlan._per_frame)
+
+    def wow_update(self, nf, plane, taus, soft, factors, gamma_plane=PLANE_NONE, noise_plane=PLANE_NONE):
+        """Plan64.wow_update per frame without power plane: taus[f] (0.0: significance one), factors[f]; `noise_plane`:
+        the plane of per-pixel noise maps, one per active frame"""
+        t = self._per_frame(taus, nf, _c.c_double, "wow_update taus")
+        f = self._per_frame(factors, nf, _c.c_double, "wow_update factors")
+        if noise_plane != PLANE_NONE:
+            check(load().wt_batch64_wow_update_map(self._h, nf, plane, t, int(soft), f, gamma_plane, noise_plane))
+            return
+        check(load().wt_batch64_wow_update(self._h, nf, plane, t, int(soft), f, gamma_plane))
+
+    def wow_scale(self, nf, plane, s, taus, soft, factors, gamma_plane=PLANE_NONE, noise_plane=PLANE_NONE):
+        """Plan64.wow_scale per frame: local power, significance, gamma sum and whitening, in place; `noise_plane`: the
+        plane of per-pixel noise maps, one per active frame"""
+        t = self._per_frame(taus, nf, _c.c_double, "wow_scale taus")
+        f = self._per_frame(factors, nf, _c.c_double, "wow_scale factors")
+        if noise_plane != PLANE_NONE:
+            check(load().wt_batch64_wow_scale_map(self._h, nf, plane, s, t, int(soft), f, gamma_plane, noise_plane))
+            return
+        check(load().wt_batch64_wow_scale(self._h, nf, plane, s, t, int(soft), f, gamma_plane))
+
+    def reduce(self, nf, plane):
+        """[(sum, sumsq, min, max)] of every active frame (Plan64.reduce's doubles)"""
+        out = (_c.c_double * (4 * nf))()
+        check(load().wt_batch64_reduce(self._h, nf, plane, out))
+        return [tuple(out[4 * f:4 * f + 4]) for f in range(nf)]
+
+    def gamma_blend(self, nf, recon, gamma_plane, gmins, gmaxs, inv_gamma, h):
+        lo = self._per_frame(gmins, nf, _c.c_double, "gamma_blend gmins")
+        hi = self._per_frame(gmaxs, nf, _c.c_double, "gamma_blend gmaxs")
+        check(load().wt_batch64_gamma_blend(self._h, nf, recon, gamma_plane, lo, hi, inv_gamma, h))
+
+    def plane_sum(self, nf, first, count, dst=PLANE_OUT):
+        check(load().wt_batch64_plane_sum(self._h, nf, first, count, dst))
 
 
 _batch_cache = {}        # id(ctx) -> [BatchPlan / BatchPlan64], most recently used last (its own small cache: not the plan pool)

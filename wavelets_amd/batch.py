@@ -13,12 +13,15 @@ _wow_sigma_bilateral).  With bilateral= the transform is the batched bilateral m
 all frames, bilateral_eligible).  Stacks the reference
 computes in float64 (float64 frames; int16 .. int64 and big-endian frames, which it recasts) run transform_stack
 and denoise_stack on the float64 batch (wt_batch64, batch64_eligible), with bilateral= behind the batched float64
-march (bilateral64_eligible).  `noise` may hold per-pixel noise maps (ref wavelets.py:133-141) - one (H, W) ndarray
+march (bilateral64_eligible), and wow_stack on the same batch (wow64_eligible: the transform's scales beyond the fused
+passes and the fused update of every scale on the batched float64 per-scale stencil, one launch per scale for all
+frames; moments, medians and the gamma range of all frames in one host round trip each).  `noise` may hold per-pixel noise maps (ref wavelets.py:133-141) - one (H, W) ndarray
 shared by the frames, or one entry per frame, maps mixed with levels and None: they lie in one more plane of the batch,
 the noise plane (noise_map_eligible, _upload_noise_maps; a shared map crosses PCIe once and is replicated on the device),
-read by the map forms of the thresholded sum (both batches) and of wow's updates (float32); a frame with a level has
+read by the map forms of the thresholded sum and of wow's updates (both batches); a frame with a level has
 ones there and keeps its map-free arithmetic.  Inputs the batched engines do not cover run the per-frame loop
-(batch_eligible / batch64_eligible / wow_eligible / bilateral_eligible / bilateral64_eligible say which)."""
+(batch_eligible / batch64_eligible / wow_eligible / wow64_eligible / bilateral_eligible / bilateral64_eligible say
+which)."""
 import numpy as np
 
 from . import _lib
@@ -29,7 +32,8 @@ from .utils import (denoise, wow, enhance, _enhance_lists, _GAMMA_PLANE, _wow_n_
                     _wow_factor, _gamma_range, _wow_sigma_bilateral)
 
 __all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'enhance_stack', 'batch_eligible', 'batch64_eligible',
-           'wow_eligible', 'bilateral_eligible', 'bilateral64_eligible', 'enhance_eligible', 'noise_map_eligible']
+           'wow_eligible', 'wow64_eligible', 'bilateral_eligible', 'bilateral64_eligible', 'enhance_eligible',
+           'noise_map_eligible']
 
 # levels whose fused schedule has a kernel for every pass (wt_plan_fused_ok), both built-in families: L = 1 is
 # a single-scale pass, and from 9 scales on the schedules hold single-scale passes at D >= 256 (wt_fused_has_pass)
@@ -246,6 +250,55 @@ def bilateral64_eligible(frames, level, scaling_function=B3spline, bilateral=Non
         return False
     N, H, W = frames.shape
     return N >= 1 and _lib.batch64_bilateral_ok(_family_of(scaling_function(2)), H, W, int(level))
+
+
+# wow_stack takes float64 stacks from this many pixels per frame on: WOW_MAP_MIN_PIXELS' number and its reasoning - the
+# per-frame loop is pinned for an 8 x 8 float64 stack (tests/test_wow_stack_cpu.py), and a frame of a few dozen pixels
+# has nothing for a batch to save.  A condition, not a measured crossover (tools/bench_wow64_stack.py has the
+# measured shapes).
+WOW64_MIN_PIXELS = WOW_MAP_MIN_PIXELS
+
+# float64 stacks of at most this many frames of at least this many pixels run the per-frame loop: measured
+# (tools/bench_wow64_stack.py, 2 x 4096^2 float64, denoise_coefficients=[5, 2]) the batch is 2 % behind the loop there
+# host to host (13.3 against 13.0 ms, ranges apart) and 4 % device-resident; the default and bilateral cases are level
+WOW64_FEW_FRAMES, WOW64_LARGE_PIXELS = 2, 1 << 24
+
+
+def wow64_eligible(frames, n_scales, scaling_function=B3spline, bilateral=None, noise_per_frame=(), noise_maps=False):
+    """True when the float64 batch (wt_batch64) computes wow over this stack (host logic): an (N, H, W) ndarray the
+    reference computes in float64 (wavelets._result_dtype: native float64, or a type the device widens - int16 /
+    uint16 / int32 / uint32 / int64, '>f4', '>f8'; native float32 stacks are wow_eligible's), a built-in scaling
+    function with its own taps, noise levels that are scalars and not arrays (utils.wow takes a 0-d array as a noise
+    map) or, with noise_maps=True, per-pixel noise maps of the frames' shape, n_scales (already resolved) in 1..24,
+    frames of at least WOW64_MIN_PIXELS pixels whose schedule the batch runs (_lib.batch64_wow_ok: H >= 2, rows the
+    fused passes take at 8 bytes per pixel, fused or single-scale stencil passes, option "stencil64" on) - except
+    stacks of at most WOW64_FEW_FRAMES frames of WOW64_LARGE_PIXELS pixels or more, measured behind the loop.  With
+    `bilateral`, bilateral64_eligible's conditions at level n_scales instead of the schedule's: the transform is the
+    batched float64 march.  Everything else runs the per-frame loop."""
+    if isinstance(n_scales, bool) or not isinstance(n_scales, (int, np.integer)) or n_scales not in WOW_LEVELS:
+        return False
+    if not isinstance(frames, np.ndarray) or frames.ndim != 3:
+        return False
+    noise_per_frame = _maps_admitted(frames, noise_per_frame, noise_maps)
+    if noise_per_frame is not None and any(type(n) is np.ndarray for n in noise_per_frame):
+        return False
+    if _result_dtype(frames) != np.float64:
+        return False
+    if frames.dtype != np.dtype(np.float64) and not _lib.device_widens(frames.dtype):
+        return False
+    if not _family_noise_eligible(scaling_function, None, noise_per_frame):
+        return False
+    N, H, W = frames.shape
+    if N < 1 or H * W < WOW64_MIN_PIXELS:
+        return False
+    if N <= WOW64_FEW_FRAMES and H * W >= WOW64_LARGE_PIXELS:
+        return False
+    fam = _family_of(scaling_function(2))
+    if not _lib.batch64_wow_ok(fam, H, W, int(n_scales)):
+        return False
+    if bilateral is None:
+        return True
+    return bilateral64_eligible(frames, int(n_scales), scaling_function, bilateral, noise_per_frame)
 
 
 def _chunks(frames, level):
@@ -506,7 +559,8 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
               noise=None, bilateral=None, bilateral_scaling=False, soft_threshold=True, preserve_variance=False,
               gamma=3.2, gamma_min=None, gamma_max=None, h=0, out=None, return_coefficients=False):
     """(N, H, W): the wow image of every frame (utils.wow, ref utils.py:105-219), batched - float32 for the stacks
-    the batch computes, the per-frame dtype otherwise.  `noise`: None (each frame's own MAD estimate), a scalar,
+    the float32 batch computes, float64 for the stacks the reference computes in float64 (wow64_eligible: `out`, if
+    given, a C-contiguous float64 array of the result's shape), the per-frame dtype otherwise.  `noise`: None (each frame's own MAD estimate), a scalar,
     or one entry per frame - a level or a per-pixel noise map of the frames' (H, W); an (H, W) ndarray: one map shared
     by the frames.  return_coefficients: (images, planes), planes (N, n_scales + 1, H, W) = the whitened coefficients of
     every frame (wow(...)[1].data)."""
@@ -522,26 +576,36 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
     L = _wow_scale_limit(L, scaling_function, 2, bilateral, denoise_coefficients)
     take_maps = shape[0] * shape[1] >= WOW_MAP_MIN_PIXELS
     bil = bilateral_eligible(fr, L, scaling_function, bilateral, nl, noise_maps=take_maps)
-    if not bil and not wow_eligible(fr, L, scaling_function, bilateral, nl, noise_maps=take_maps):
+    f32 = bil or wow_eligible(fr, L, scaling_function, bilateral, nl, noise_maps=take_maps)
+    f64 = not f32 and wow64_eligible(fr, L, scaling_function, bilateral, nl, noise_maps=take_maps)
+    if not f32 and not f64:
         per = nl if nl is not None else [noise] * N
         res = [wow(f, scaling_function, n_scales, noise=n_i, **kw) for f, n_i in zip(fr, per)]
         images = _hand_over(np.stack([r[0] for r in res]), out)
         return (images, np.stack([r[1].data for r in res])) if return_coefficients else images
     _, H, W = fr.shape
     nplanes = L + 1
-    out = _f32_target(out, (N, H, W))
-    planes = _lib.host_empty((N, nplanes, H, W)) if return_coefficients else None
+    if f64:                                # (checked before any device work)
+        if out is not None and not (isinstance(out, np.ndarray) and out.shape == (N, H, W) and out.dtype == np.float64
+                                    and out.flags.c_contiguous and out.flags.writeable):
+            raise ValueError(f"out: a C-contiguous float64 array of shape {(N, H, W)} expected")
+        out, _ = _f64_target(out, (N, H, W))
+        bil = bilateral is not None
+    else:
+        out = _f32_target(out, (N, H, W))
+    planes = _lib.host_empty((N, nplanes, H, W), dtype=out.dtype) if return_coefficients else None
     ctx = _lib.default_context()
     fam = _family_of(scaling_function(2))
     maps = noise_map_eligible(fr, nl)
     # (the spare plane of the fused update, the gamma plane, the noise plane)
     extra = int(whitening and h < 1) + int(h > 0) + int(maps)
     shared = _shared_map(nl, (H, W))
-    chunks = _lib.batch_chunks(N, H, W, L, extra_planes=extra)
-    bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, fam, L)
+    chunks = _lib.batch_chunks(N, H, W, L, extra_planes=extra, itemsize=8) if f64 else _lib.batch_chunks(N, H, W, L, extra_planes=extra)
+    acquire, release = (_lib.acquire_batch64, _lib.release_batch64) if f64 else (_lib.acquire_batch, _lib.release_batch)
+    bp = acquire(ctx, max(nf for _, nf in chunks), H, W, fam, L)
     try:
         for f0, nf in chunks:
-            bp.upload(PLANE_INPUT, fr[f0:f0 + nf])
+            bp.upload(PLANE_INPUT, fr[f0:f0 + nf])                  # (float64 batch: integer frames are widened on the device)
             if bil:                                                                 # ref:140-151
                 sb = _sigma_bilateral_list(_wow_sigma_bilateral(bilateral, L), L)     # (wow's list, then the transform's)
                 bp.decompose_bilateral(nf, PLANE_INPUT, L, sb, bilateral_scaling)
@@ -557,14 +621,15 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
                 for s in range(nplanes):
                     bp.download(s, nf, out=planes[f0:f0 + nf, s])
     finally:
-        _lib.release_batch(bp)
+        release(bp)
     return (out, planes) if return_coefficients else out
 
 
 def _wow_batch_device(bp, nf, noises, scaling_function, n_scales, weights, whitening, denoise_coefficients,
                       soft_threshold, preserve_variance, gamma, gamma_min, gamma_max, h, bilateral=None):
     """The device-resident part of wow (ref:157-217, utils._wow_device / _wow_scales) for frames 0 .. nf-1 of a
-    batch whose planes 0 .. n_scales hold the transform: whitened planes in place, the images in PLANE_OUT.
+    BatchPlan or BatchPlan64 whose planes 0 .. n_scales hold the transform: whitened planes in place, the images in
+    PLANE_OUT; the factors in the batch's element type, as the per-frame call computes them.
     `noises`: one entry per frame (None: its MAD estimate, taken where the per-frame call's lazy _tau takes it; a
     per-pixel noise map: it lies in the batch's noise plane, _upload_noise_maps, and the scales with a non-zero sigma
     run the updates that read it).
@@ -582,7 +647,7 @@ def _wow_batch_device(bp, nf, noises, scaling_function, n_scales, weights, white
     for s, (_, w, d) in enumerate(zip(range(nplanes), recomposition_weights, sdc)):   # ref:174
         need = _wow_needs_moments(s, n_scales, preserve_variance, whitening, h)
         moments = bp.reduce(nf, s) if need else [None] * nf
-        factors = [_wow_factor(s, n_scales, w, m, npix, preserve_variance, whitening, h, np.float32) for m in moments]
+        factors = [_wow_factor(s, n_scales, w, m, npix, preserve_variance, whitening, h, bp.dtype) for m in moments]
         if s == n_scales:                                                           # ref:185-191, 203
             bp.wow_update(nf, s, [0.0] * nf, soft_threshold, factors, gplane)
             continue

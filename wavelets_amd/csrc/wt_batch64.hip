@@ -12,6 +12,10 @@
 // The MAD median is a per-frame radix select over the 63 magnitude bits of a double (six histogram levels of
 // 11 / 11 / 11 / 11 / 11 / 8 bits, the levels of wt64_abs_median), two ranks per frame for an even pixel count:
 // N exact medians for one host round trip.
+// wow (watroo/utils.py:105-219) runs on the same planes: schedules beyond the fused passes (from 9 scales on) take the
+// batched per-scale stencil for their single-scale passes, the fused update of a scale is ONE launch of that stencil
+// for all frames (wt_stencil64_batch.hip), and the pointwise update, the gamma blend, the moments and the plane sum
+// are the per-frame kernels' texts (wt_wow64.h) with the frame as a grid dimension.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -19,6 +23,8 @@
 #include "wt_host.h"
 #include "wt_fused_decl.h"
 #include "wt_math64.h"
+#include "wt_reduce.h"
+#include "wt_wow64.h"
 #include "wt_unit_probe.h"
 
 WT_UNIT_PROBE_DEFINE
@@ -45,6 +51,18 @@ struct wt_batch64 {
     WtBatch64Sel *h_sel = nullptr;  // pinned copy
     double *d_tau = nullptr;        // [n][3 * WT_MAX_SUM_PLANES]: the thresholds of wt_batch64_denoise_sum, then 1 / tau; wt_batch64_enhance_sum: then the weights
     double *h_tau = nullptr;        // pinned staging of the table
+    // wow: WT_PLANE_SCRATCH(3) = the output plane of wt_batch64_wow_scale (swapped with the coefficient plane, as
+    // wt64_wow_scale does), WT_PLANE_SCRATCH(4) = the gamma accumulator (utils.wow's plane ids)
+    double *spare = nullptr, *gamma = nullptr;
+    // per-frame parameter pairs of one launch ({tau, factor}, {gmin, gmax}): a ring of table slots [n][2], pinned
+    // staging + device copy; a slot is refilled only after the copy that last read it has completed (its event)
+    static constexpr int kTabSlots = 16;
+    double *d_ptab = nullptr, *h_ptab = nullptr;
+    hipEvent_t ptab_ev[kTabSlots] = {};
+    int ptab_next = 0;
+    // wt_batch64_reduce: [n][red_blocks][4] partials + [n][4] results on the device, [n][4] pinned
+    double *d_red = nullptr, *h_red = nullptr;
+    int red_blocks = 0;
 };
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -276,6 +294,60 @@ __global__ __launch_bounds__(256) void wt_batch64_widen_kernel(const I *src, dou
     }
 }
 
+// wt64_wow_kernel (wt_kernels_f64.h) with the frame as grid z: no power plane, the frame's {tau, factor} (wow's last
+// plane, whitening=False, h >= 1 - watroo/utils.py:185-203); `noise`: the batch's noise plane (a frame with a scalar
+// level has ones there: tau * 1.0 is tau) or null.  Same wt64_wow_point: the bits of the per-frame call.
+__global__ __launch_bounds__(256) void wt_batch64_wow_kernel(double *c, const double *noise, double *gamma, int W, int P, int nrows, int64_t fstride,
+                                                             const double *ptab, int soft)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= W) return;
+    const int f = blockIdx.z;
+    const double tau = ptab[2 * f], factor = ptab[2 * f + 1];
+    const int64_t fo = (int64_t)f * fstride;
+    c += fo;
+    if (noise) noise += fo;
+    if (gamma) gamma += fo;
+    for (int y = blockIdx.y; y < nrows; y += gridDim.y) {
+        const int64_t o = (int64_t)y * P + x;
+        c[o] = wt64_wow_point(c[o], false, 0.0, noise, gamma, o, tau, soft, factor);
+    }
+}
+
+// wt64_gamma_kernel (wt_kernels_f64.h, watroo/utils.py:212-217) with the frame as grid z and its own {gmin, gmax}
+__global__ __launch_bounds__(256) void wt_batch64_gamma_kernel(double *recon, const double *gamma, int W, int P, int nrows, int64_t fstride,
+                                                               const double *ptab, double inv_gamma, double h)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= W) return;
+    const int f = blockIdx.z;
+    const double gmin = ptab[2 * f];
+    const double range = ptab[2 * f + 1] - gmin;        // (wt64_gamma_blend: the same subtraction on the host)
+    recon += (int64_t)f * fstride;
+    gamma += (int64_t)f * fstride;
+    for (int y = blockIdx.y; y < nrows; y += gridDim.y) {
+        const int64_t o = (int64_t)y * P + x;
+        recon[o] = wt64_gamma_point(recon[o], gamma[o], gmin, range, inv_gamma, h);
+    }
+}
+
+// wt64_reduce_kernel + wt_reduce_final_kernel per frame (grid y / the final block = the frame): the per-frame split
+// into gridDim.x row-strided blocks and the fold order of wt64_reduce, i.e. the doubles of the per-frame call
+__global__ __launch_bounds__(256) void wt_batch64_reduce_kernel(const double *p, int nrows, int P, int W, int64_t fstride, double *partials)
+{
+    wt64_reduce_rows_block(p + (int64_t)blockIdx.y * fstride, nrows, P, W, partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4);
+}
+__global__ __launch_bounds__(256) void wt_batch64_reduce_final_kernel(const double *partials, int nblocks, double *out)
+{
+    wt_reduce_final_block(partials + (int64_t)blockIdx.x * nblocks * 4, nblocks, out + (int64_t)blockIdx.x * 4);
+}
+
+// wt64_plane_sum_kernel over the frames back to back (one flat range): the additions in plane order
+__global__ __launch_bounds__(256) void wt_batch64_plane_sum_kernel(Sum64Args a, double *dst, int64_t n2)
+{
+    wt64_plane_sum_groups(a, dst, n2);
+}
+
 // ------------------------------------------------------------------------------------------------ host
 static int b64plane(wt_batch64 *b, int id, double **out)
 {
@@ -285,8 +357,10 @@ static int b64plane(wt_batch64 *b, int id, double **out)
     else if (id == WT_PLANE_OUT) slot = &b->out;
     else if (id == WT_PLANE_SCRATCH(0)) slot = &b->scr[0];
     else if (id == WT_PLANE_SCRATCH(1)) slot = &b->scr[1];
+    else if (id == WT_PLANE_SCRATCH(3)) slot = &b->spare;
+    else if (id == WT_PLANE_SCRATCH(4)) slot = &b->gamma;
     else if (id == WT_PLANE_SCRATCH(5)) slot = &b->noise;
-    if (!slot) WT_FAIL("wt_batch64: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1/5)", id, b->max_level);
+    if (!slot) WT_FAIL("wt_batch64: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1/3/4/5)", id, b->max_level);
     if (!*slot) WT_HIP(hipMalloc((void **)slot, (size_t)b->n * (size_t)b->fstride * sizeof(double)));
     *out = *slot;
     return 0;
@@ -318,6 +392,56 @@ extern "C" int wt_batch64_fused_ok(int family, int64_t H, int64_t W, int level, 
     int np = 0;
     *ok = batch64_all_fused(family, H, W, level, tr, &np) ? 1 : 0;
     return 0;
+}
+
+// The wider condition of wow's transform: `level` in 1..24 whose float64 schedule holds, besides fused passes,
+// single-scale passes for the batched per-scale stencil - what fused64_run (wt_f64.h) gives one frame on the
+// per-frame stencil - and the option "stencil64" on: with it off the per-frame call takes the two generic kernels
+// per scale, for the passes and for wt64_wow_scale (stencil64_ok), whose bits differ.
+static bool batch64_wow_shape_ok(int family, int64_t H, int64_t W, int level, int32_t *tr, int *np)
+{
+    if ((family != WT_B3SPLINE && family != WT_TRIANGLE) || H < 2 || W < 1 || H > INT32_MAX || W > INT32_MAX) return false;
+    if (level < 1 || level > 24) return false;
+    if (!wt_fused_supported_bytes((W + 1) / 2 * 2 * 8)) return false;
+    if (!wt_get_stencil64()) return false;
+    if (wt_schedule(family, level, 1, tr, 32, np)) return false;
+    for (int i = 0; i < *np; ++i)
+        if (!wt_fused_has_pass(tr[3 * i], tr[3 * i + 1], family) && tr[3 * i + 1] != 1) return false;
+    return true;
+}
+
+extern "C" int wt_batch64_wow_ok(int family, int64_t H, int64_t W, int level, int *ok)
+{
+    if (!ok) WT_FAIL("wt_batch64_wow_ok: null pointer");
+    int32_t tr[3 * 32];
+    int np = 0;
+    *ok = batch64_wow_shape_ok(family, H, W, level, tr, &np) ? 1 : 0;
+    return 0;
+}
+
+// the frames of a batched stencil launch on the batch's stream: ONE frame's geometry (W, P, nrows, border 0 - what a
+// wt_plan64 of that shape hands wt_launch_stencil, so the kernel choice and the streaming-store flag are its own)
+static StencilCtx batch64_stencil_ctx(const wt_batch64 *b)
+{
+    return StencilCtx{b->ctx, b->ctx->stream, b->geo.g, b->family};
+}
+
+// one single-scale pass of the transform on the batched MODE_DECOMP stencil (fused64_run's smooth64 branch)
+static int batch64_stencil_pass(wt_batch64 *b, int nf, int cur, int nxt, int s0)
+{
+    if (s0 < 0 || s0 > 24 || s0 > b->max_level) WT_FAIL("wt_batch64_decompose: scale %d outside the batch (max_level %d)", s0, b->max_level);
+    if (cur == nxt || cur == s0 || nxt == s0) WT_FAIL("wt_batch64_decompose: input/output planes alias the detail plane of the pass");
+    double *in = nullptr, *oc = nullptr, *ow = nullptr;
+    WT_TRY(b64plane(b, cur, &in));
+    WT_TRY(b64plane(b, nxt, &oc));
+    WT_TRY(b64plane(b, s0, &ow));
+    ChainArgsT<double> a{};
+    a.in = in; a.out_c = oc; a.out_w = ow;
+    a.f1 = 1.0; a.f2 = 1.0;
+    WtFrames fr;
+    fr.n = nf;
+    fr.fstride = b->fstride;
+    return wt64_stencil_batch_launch(batch64_stencil_ctx(b), MODE_DECOMP, a, s0, "wt64_chain_batch_kernel<decomp>", fr);
 }
 
 static int batch64_pass(wt_batch64 *b, int nf, int cur, int nxt, int s0, int ns, int acc, int sum_plane, bool first)
@@ -362,15 +486,18 @@ static int batch64_schedule_run(wt_batch64 *b, int nf, int src, int level, bool 
         WT_FAIL("%s: dst plane %d is an input / output / internal plane of the transform", who, dst);
     int32_t tr[3 * 32];
     int np = 0;
-    if (!batch64_all_fused(b->family, b->geo.g.H, b->geo.g.W, level, tr, &np))
-        WT_FAIL("%s: %d scales have no all-fused float64 schedule for %d x %d frames (wt64_plan_fused_ok): not a batch case", who, level,
-                b->geo.g.H, b->geo.g.W);
+    // (the passes with a sum run fused kernels only; a transform alone also takes single-scale stencil passes)
+    if (!batch64_all_fused(b->family, b->geo.g.H, b->geo.g.W, level, tr, &np) &&
+        (with_sum || !batch64_wow_shape_ok(b->family, b->geo.g.H, b->geo.g.W, level, tr, &np)))
+        WT_FAIL("%s: %d scales have no %s float64 schedule for %d x %d frames (%s): not a batch case", who, level,
+                with_sum ? "all-fused" : "batched", b->geo.g.H, b->geo.g.W, with_sum ? "wt64_plan_fused_ok" : "wt_batch64_wow_ok");
     int cur = src;
     for (int i = 0; i < np; ++i) {
         const int s0 = tr[3 * i], ns = tr[3 * i + 1];
         const bool last = s0 + ns == level;
         const int nxt = last ? level : WT_PLANE_SCRATCH(i & 1);
-        WT_TRY(batch64_pass(b, nf, cur, nxt, s0, ns, with_sum ? (last ? 2 : 1) : 0, dst, i == 0));
+        if (!wt_fused_has_pass(s0, ns, b->family)) WT_TRY(batch64_stencil_pass(b, nf, cur, nxt, s0));
+        else WT_TRY(batch64_pass(b, nf, cur, nxt, s0, ns, with_sum ? (last ? 2 : 1) : 0, dst, i == 0));
         cur = nxt;
     }
     return 0;
@@ -385,12 +512,20 @@ static void batch64_free(wt_batch64 *b, int *bad)
     f(b->scr[0]);
     f(b->scr[1]);
     f(b->noise);
+    f(b->spare);
+    f(b->gamma);
+    f(b->d_ptab);
+    f(b->d_red);
     f(b->istage);
     f(b->d_hist);
     f(b->d_sel);
     f(b->d_tau);
     if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) *bad = 1;
     if (b->h_tau && hipHostFree(b->h_tau) != hipSuccess) *bad = 1;
+    if (b->h_ptab && hipHostFree(b->h_ptab) != hipSuccess) *bad = 1;
+    if (b->h_red && hipHostFree(b->h_red) != hipSuccess) *bad = 1;
+    for (hipEvent_t e : b->ptab_ev)
+        if (e && hipEventDestroy(e) != hipSuccess) *bad = 1;
 }
 
 extern "C" int wt_batch64_create(wt_ctx *ctx, int n, int H, int W, int family, int max_level, wt_batch64 **out)
@@ -886,6 +1021,208 @@ extern "C" int wt_batch64_anscombe(wt_batch64 *b, int nf, int src, int dst, doub
     ProfScope ps(b->ctx, "wt_batch64_anscombe_kernel");
     hipLaunchKernelGGL(wt_batch64_anscombe_kernel, dim3((geo.W + 255) / 256, (unsigned)std::min(nrows, 32768)), dim3(256), 0, b->ctx->stream,
                        (const double *)s, d, geo.W, geo.P, nrows, alpha, g, sigma, inverse);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ wow
+// per-frame parameter pairs (pairs[2 * f], pairs[2 * f + 1]) -> a device table slot, stream-ordered (*dev)
+static int batch64_table(wt_batch64 *b, int nf, const double *pairs, const double **dev)
+{
+    wt_ctx *c = b->ctx;
+    if (!b->d_ptab) {
+        WT_HIP(hipMalloc((void **)&b->d_ptab, (size_t)wt_batch64::kTabSlots * b->n * 2 * sizeof(double)));
+        WT_HIP(hipHostMalloc((void **)&b->h_ptab, (size_t)wt_batch64::kTabSlots * b->n * 2 * sizeof(double), 0));
+    }
+    const int slot = b->ptab_next;
+    b->ptab_next = (slot + 1) % wt_batch64::kTabSlots;
+    if (b->ptab_ev[slot]) WT_HIP(hipEventSynchronize(b->ptab_ev[slot]));    // (the copy of kTabSlots calls ago)
+    else WT_HIP(hipEventCreateWithFlags(&b->ptab_ev[slot], hipEventDisableTiming));
+    double *h = b->h_ptab + (size_t)slot * b->n * 2, *d = b->d_ptab + (size_t)slot * b->n * 2;
+    memcpy(h, pairs, (size_t)nf * 2 * sizeof(double));
+    WT_HIP(hipMemcpyAsync(d, h, (size_t)nf * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    WT_HIP(hipEventRecord(b->ptab_ev[slot], c->stream));
+    *dev = d;
+    return 0;
+}
+
+// {tau[f], factor[f]} of a wow launch: the factors travel as the doubles the host computed (utils._wow_factor)
+static int wow64_pairs(wt_batch64 *b, int nf, const double *tau, const double *factor, const double **dev, const char *who)
+{
+    if (!tau || !factor) WT_FAIL("%s: null tau / factor", who);
+    std::vector<double> pairs((size_t)nf * 2);
+    for (int f = 0; f < nf; ++f) {
+        pairs[2 * f] = tau[f];
+        pairs[2 * f + 1] = factor[f];
+    }
+    return batch64_table(b, nf, pairs.data(), dev);
+}
+
+// grid of the batched pointwise kernels: wt64's (x blocks, rows) per frame, the frame as grid z
+static dim3 batch64_point_grid(const wt_batch64 *b, int nf)
+{
+    const Geo &g = b->geo.g;
+    return dim3((g.W + 255) / 256, (unsigned)std::max(1, std::min(g.H, (4096 + nf - 1) / nf)), (unsigned)nf);
+}
+
+// wt_batch64_wow_update / wt_batch64_wow_update_map: noise_plane == WT_PLANE_NONE runs without a map
+static int batch64_wow_update(wt_batch64 *b, int nf, int plane, const double *tau, int soft, const double *factor, int gamma_plane, int noise_plane,
+                              const char *who)
+{
+    WT_TRY(check_frames64(b, nf, who));
+    WtGuard guard_(b->ctx);
+    if (gamma_plane == plane) WT_FAIL("%s: the gamma plane is the updated plane", who);
+    if (noise_plane != WT_PLANE_NONE && (noise_plane == plane || noise_plane == gamma_plane)) WT_FAIL("%s: the noise plane aliases a plane of the update", who);
+    double *c = nullptr, *gm = nullptr, *nz = nullptr;
+    WT_TRY(b64plane(b, plane, &c));
+    if (gamma_plane != WT_PLANE_NONE) WT_TRY(b64plane(b, gamma_plane, &gm));
+    if (noise_plane != WT_PLANE_NONE) WT_TRY(b64plane(b, noise_plane, &nz));
+    const double *dt = nullptr;
+    WT_TRY(wow64_pairs(b, nf, tau, factor, &dt, who));
+    const Geo &g = b->geo.g;
+    ProfScope ps(b->ctx, nz ? "wt_batch64_wow_map_kernel" : "wt_batch64_wow_kernel");
+    hipLaunchKernelGGL(wt_batch64_wow_kernel, batch64_point_grid(b, nf), dim3(256), 0, b->ctx->stream, c, (const double *)nz, gm, g.W, g.P, g.H,
+                       b->fstride, dt, soft);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch64_wow_update(wt_batch64 *b, int nf, int plane, const double *tau, int soft, const double *factor, int gamma_plane)
+{
+    return batch64_wow_update(b, nf, plane, tau, soft, factor, gamma_plane, WT_PLANE_NONE, "wt_batch64_wow_update");
+}
+
+extern "C" int wt_batch64_wow_update_map(wt_batch64 *b, int nf, int plane, const double *tau, int soft, const double *factor, int gamma_plane,
+                                         int noise_plane)
+{
+    if (noise_plane == WT_PLANE_NONE) WT_FAIL("wt_batch64_wow_update_map: no noise plane (wt_batch64_wow_update is the call without a map)");
+    return batch64_wow_update(b, nf, plane, tau, soft, factor, gamma_plane, noise_plane, "wt_batch64_wow_update_map");
+}
+
+// wt_batch64_wow_scale / wt_batch64_wow_scale_map: noise_plane == WT_PLANE_NONE runs the instantiations without a map
+static int batch64_wow_scale(wt_batch64 *b, int nf, int plane, int s, const double *tau, int soft, const double *factor, int gamma_plane,
+                             int noise_plane, const char *who)
+{
+    WT_TRY(check_frames64(b, nf, who));
+    WtGuard guard_(b->ctx);
+    if (plane < 0 || plane > b->max_level) WT_FAIL("%s: plane %d is not a coefficient plane", who, plane);
+    if (s < 0 || s > 24) WT_FAIL("%s: scale %d out of range", who, s);
+    if (!wt_get_stencil64()) WT_FAIL("%s: option stencil64 is off (the per-frame call runs the generic kernels): not a batch case", who);
+    if (gamma_plane == plane || gamma_plane == WT_PLANE_SCRATCH(3)) WT_FAIL("%s: the gamma plane aliases a plane of the update", who);
+    if (noise_plane != WT_PLANE_NONE && (noise_plane == plane || noise_plane == WT_PLANE_SCRATCH(3) || noise_plane == gamma_plane))
+        WT_FAIL("%s: the noise plane aliases a plane of the update", who);
+    double *c = nullptr, *t = nullptr, *gm = nullptr, *nz = nullptr;
+    WT_TRY(b64plane(b, plane, &c));
+    WT_TRY(b64plane(b, WT_PLANE_SCRATCH(3), &t));
+    if (gamma_plane != WT_PLANE_NONE) WT_TRY(b64plane(b, gamma_plane, &gm));
+    if (noise_plane != WT_PLANE_NONE) WT_TRY(b64plane(b, noise_plane, &nz));
+    const double *dt = nullptr;
+    WT_TRY(wow64_pairs(b, nf, tau, factor, &dt, who));
+    // (wt64_wow_scale's arguments and its choice of instantiation; tau and factor come from the frame's row of the table)
+    ChainArgsT<double> a{};
+    a.in = c; a.out_c = t;
+    a.noise = nz; a.gamma = gm; a.soft = soft; a.whiten = 1;
+    WtFrames fr;
+    fr.n = nf;
+    fr.fstride = b->fstride;
+    fr.ftab = dt;
+    WT_TRY(wt64_stencil_batch_launch(batch64_stencil_ctx(b), !nz && !gm ? MODE_WOW_PLAIN : (!nz ? MODE_WOW_GAMMA : MODE_WOW), a, s,
+                                     "wt64_chain_batch_kernel<wow>", fr));
+    std::swap(b->coef[plane], b->spare);          // (wt64_wow_scale: "in place" at pointer level)
+    return 0;
+}
+
+extern "C" int wt_batch64_wow_scale(wt_batch64 *b, int nf, int plane, int s, const double *tau, int soft, const double *factor, int gamma_plane)
+{
+    return batch64_wow_scale(b, nf, plane, s, tau, soft, factor, gamma_plane, WT_PLANE_NONE, "wt_batch64_wow_scale");
+}
+
+extern "C" int wt_batch64_wow_scale_map(wt_batch64 *b, int nf, int plane, int s, const double *tau, int soft, const double *factor, int gamma_plane,
+                                        int noise_plane)
+{
+    if (noise_plane == WT_PLANE_NONE) WT_FAIL("wt_batch64_wow_scale_map: no noise plane (wt_batch64_wow_scale is the call without a map)");
+    return batch64_wow_scale(b, nf, plane, s, tau, soft, factor, gamma_plane, noise_plane, "wt_batch64_wow_scale_map");
+}
+
+extern "C" int wt_batch64_reduce(wt_batch64 *b, int nf, int plane, double *out)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_reduce"));
+    if (!out) WT_FAIL("wt_batch64_reduce: null pointer");
+    WtGuard guard_(b->ctx);
+    wt_ctx *c = b->ctx;
+    double *q = nullptr;
+    WT_TRY(b64plane(b, plane, &q));
+    const Geo &g = b->geo.g;
+    // (wt64_reduce's split: row-strided blocks, at most partial_blocks of them, per frame)
+    const int blocks = std::min(g.H, c->partial_blocks);
+    if (!b->d_red || b->red_blocks != blocks) {
+        WT_HIP(hipStreamSynchronize(c->stream));
+        (void)hipFree(b->d_red);
+        (void)hipHostFree(b->h_red);
+        b->d_red = nullptr;
+        b->h_red = nullptr;
+        WT_HIP(hipMalloc((void **)&b->d_red, (size_t)b->n * ((size_t)blocks + 1) * 4 * sizeof(double)));
+        WT_HIP(hipHostMalloc((void **)&b->h_red, (size_t)b->n * 4 * sizeof(double), 0));
+        b->red_blocks = blocks;
+    }
+    double *dout = b->d_red + (size_t)b->n * blocks * 4;
+    {
+        ProfScope ps(c, "wt_batch64_reduce_kernel");
+        hipLaunchKernelGGL(wt_batch64_reduce_kernel, dim3(blocks, nf), dim3(256), 0, c->stream, (const double *)q, g.H, g.P, g.W, b->fstride, b->d_red);
+        hipLaunchKernelGGL(wt_batch64_reduce_final_kernel, dim3(nf), dim3(256), 0, c->stream, (const double *)b->d_red, blocks, dout);
+    }
+    WT_HIP(hipGetLastError());
+    WT_HIP(hipMemcpyAsync(b->h_red, dout, (size_t)nf * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    WT_HIP(hipStreamSynchronize(c->stream));               // the one host round trip for all nf frames
+    memcpy(out, b->h_red, (size_t)nf * 4 * sizeof(double));
+    return 0;
+}
+
+extern "C" int wt_batch64_gamma_blend(wt_batch64 *b, int nf, int recon, int gamma_plane, const double *gmin, const double *gmax, double inv_gamma,
+                                      double h)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_gamma_blend"));
+    if (!gmin || !gmax) WT_FAIL("wt_batch64_gamma_blend: null gmin / gmax");
+    WtGuard guard_(b->ctx);
+    if (recon == gamma_plane) WT_FAIL("wt_batch64_gamma_blend: recon and gamma planes must differ");
+    double *r = nullptr, *g = nullptr;
+    WT_TRY(b64plane(b, recon, &r));
+    WT_TRY(b64plane(b, gamma_plane, &g));
+    std::vector<double> pairs((size_t)nf * 2);
+    for (int f = 0; f < nf; ++f) {
+        pairs[2 * f] = gmin[f];
+        pairs[2 * f + 1] = gmax[f];
+    }
+    const double *dt = nullptr;
+    WT_TRY(batch64_table(b, nf, pairs.data(), &dt));
+    const Geo &geo = b->geo.g;
+    ProfScope ps(b->ctx, "wt_batch64_gamma_kernel");
+    hipLaunchKernelGGL(wt_batch64_gamma_kernel, batch64_point_grid(b, nf), dim3(256), 0, b->ctx->stream, r, (const double *)g, geo.W, geo.P, geo.H,
+                       b->fstride, dt, inv_gamma, h);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wt_batch64_plane_sum(wt_batch64 *b, int nf, int first, int count, int dst)
+{
+    WT_TRY(check_frames64(b, nf, "wt_batch64_plane_sum"));
+    WtGuard guard_(b->ctx);
+    if (count < 1 || count > 32) WT_FAIL("wt_batch64_plane_sum: count %d out of range [1,32]", count);
+    if (first < 0 || first + count - 1 > b->max_level) WT_FAIL("wt_batch64_plane_sum: planes [%d,%d) outside [0,%d]", first, first + count, b->max_level);
+    if (dst >= first && dst < first + count) WT_FAIL("wt_batch64_plane_sum: dst plane %d is one of the summed planes", dst);
+    Sum64Args a{};
+    a.n = count;
+    for (int i = 0; i < count; ++i) {
+        double *q = nullptr;
+        WT_TRY(b64plane(b, first + i, &q));
+        a.p[i] = q;
+    }
+    double *o = nullptr;
+    WT_TRY(b64plane(b, dst, &o));
+    // the frames back to back are one flat range: wt64_plane_sum_kernel's groups over all of them
+    const int64_t n2 = (int64_t)nf * b->fstride / 2;
+    ProfScope ps(b->ctx, "wt_batch64_plane_sum_kernel");
+    hipLaunchKernelGGL(wt_batch64_plane_sum_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, b->ctx->stream, a, o, n2);
     WT_HIP(hipGetLastError());
     return 0;
 }

@@ -155,7 +155,7 @@ static const char *wt_lattice_name(int mode)
 
 // One scale of a built-in family: lattice kernel for the large dilations, row kernel where the x halo
 // fits a workgroup, the chain kernel otherwise.  `name`: profiler name of the chain kernel.  BATCH: the same
-// choice for each of the frames `fr` (wt_batch), one launch.
+// choice for each of the frames `fr` (wt_batch, wt_batch64), one launch.
 template <typename T, int MODE, bool BATCH = false>
 static int wt_launch_stencil(const StencilCtx &sc, ChainArgsT<T> a, int s, const char *name, const WtFrames &fr = WtFrames())
 {
@@ -227,3 +227,6 @@ int wt64_bilateral_launch(const StencilCtx &sc, const double *in, const double *
 // one scale of the float64 bilateral transform (variance in the kernel, a.f1 / a.f2) on the frames `fr` of a batch
 // (wt_bilateral64_batch.hip): every frame as wt64_bilateral_march_kernel would run it alone, one launch
 int wt64_bilateral_batch_launch(const StencilCtx &sc, ChainArgsT<double> a, int s, const WtFrames &fr);
+// one scale in `mode` (MODE_DECOMP, MODE_WOW_PLAIN, MODE_WOW_GAMMA, MODE_WOW with a.noise) on the double planes of the frames `fr` of a
+// batch (wt_stencil64_batch.hip): every frame as wt64_stencil_launch would run it alone, one launch; `name`: profiler name of the chain kernel
+int wt64_stencil_batch_launch(const StencilCtx &sc, int mode, const ChainArgsT<double> &a, int s, const char *name, const WtFrames &fr);
