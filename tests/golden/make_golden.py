@@ -44,7 +44,15 @@ def _install_standins():
         mode = {2: "reflect", 4: "mirror"}[borderType]
         k = np.asarray(kernel)
         k = k[None, :] if k.ndim == 1 else k
-        res = ndimage.correlate(np.asarray(src), k.astype(src.dtype), mode=mode) + delta
+        # The border is built by np.pad, which bounces as often as the reach asks for; ndimage.correlate's own 'reflect'
+        # misreads an axis of 2 samples under a kernel that spans it several times (scipy 1.15: correlate([1., 2.],
+        # zero-stuffed B3spline taps at s = 2) gives 0.9375 at the first sample, correlate1d and OpenCV's
+        # borderInterpolate give 1).  Same taps in the same order: results are bit-identical wherever one bounce is enough.
+        src = np.asarray(src)
+        ay, ax = k.shape[0] // 2, k.shape[1] // 2
+        padded = np.pad(src, [(ay, k.shape[0] - 1 - ay), (ax, k.shape[1] - 1 - ax)],
+                        mode={"reflect": "symmetric", "mirror": "reflect"}[mode])
+        res = ndimage.correlate(padded, k.astype(src.dtype), mode="constant")[ay:ay + src.shape[0], ax:ax + src.shape[1]] + delta
         if dst is not None:
             dst[...] = res
             return dst
@@ -887,8 +895,99 @@ def g24_richardson_lucy_fft_non_pow2():
     save("g24_rl_fft_nonpow2", "hard(numpy fft; transform via cv2 stand-in)", **out)
 
 
+ND_EDGE_SIGNALS = (1, 2, 3, 4, 5, 9, 257)
+ND_EDGE_CUBES = ((1, 1, 1), (2, 2, 2), (1, 5, 7), (7, 1, 5), (5, 4, 1), (2, 3, 4), (3, 2, 9),
+                 (6, 3, 130), (3, 5, 257), (33, 3, 5))
+ND_EDGE_WIDE = ((6, 3, 130), (3, 5, 257))     # stored in float32, and fewer keys: they hold 6195 of the 7148 samples
+
+
+def g26_nd_edges():
+    """Signals and (Z, Y, X) cubes at their edge shapes: axes of length 1 and 2, n = 1..3 under the
+    1-D 'mirror' border (scipy: period 2n - 2, a constant for n = 1), Y = 1..5 under a reach of
+    2 * 2**4 = 32 (dozens of bounces inside every slice), widths around the float4 group.
+
+    Inputs are float32 samples.  The reference runs on their float64 copies (same values, float64
+    arithmetic: wavelets.py:319-320 keeps the dtype), except on the two wide cubes of ND_EDGE_WIDE,
+    which run and are stored in float32 to keep the file small.  A transform's detail planes do
+    not depend on the number of levels (:429-442), so levels below the top one are stored as their
+    last plane only ('smooth_*'); that is asserted here, bit for bit.  Where the reference raises,
+    'raises_<key>' holds the exception's class name."""
+    from watroo.wavelets import AbstractScalingFunction, sdev_loc
+
+    class Skew5(AbstractScalingFunction):
+        coefficients_1d = np.array([0.05, 0.25, 0.4, 0.2, 0.1])
+        sigma_e_1d = np.array([0.7, 0.3, 0.2, 0.12, 0.08, 0.06])
+        sigma_e_2d = np.array([0.9, 0.2, 0.09, 0.04, 0.02, 0.01])
+        sigma_e_3d = np.array([0.95, 0.12, 0.04, 0.014, 0.005])
+
+        def __init__(self, *args, **kwargs):
+            super().__init__('skew5', *args, **kwargs)
+
+    class Even4(AbstractScalingFunction):
+        coefficients_1d = np.array([0.1, 0.4, 0.3, 0.2])
+        sigma_e_1d = np.array([0.7, 0.3, 0.2, 0.12, 0.08, 0.06])
+        sigma_e_2d = np.array([0.9, 0.2, 0.09, 0.04, 0.02, 0.01])
+        sigma_e_3d = np.array([0.95, 0.12, 0.04, 0.014, 0.005])
+
+        def __init__(self, *args, **kwargs):
+            super().__init__('even4', *args, **kwargs)
+
+    out = {"skew5_taps": Skew5.coefficients_1d, "even4_taps": Even4.coefficients_1d,
+           "custom_sigma_e_1d": Even4.sigma_e_1d, "custom_sigma_e_3d": Even4.sigma_e_3d,
+           "signals": np.array(ND_EDGE_SIGNALS), "cubes": np.array(ND_EDGE_CUBES)}
+
+    def put(key, fn):
+        try:
+            r = fn()
+            out[key] = np.asarray(r[0] if isinstance(r, tuple) else r)
+            if isinstance(r, tuple):
+                out[key + "_coef"] = r[1].data
+        except Exception as e:                         # noqa: BLE001  (the class name is the recorded result)
+            out["raises_" + key] = np.array(type(e).__name__)
+
+    shapes = [(n,) for n in ND_EDGE_SIGNALS] + list(ND_EDGE_CUBES)
+    for i, shape in enumerate(shapes):
+        tag = "x".join(map(str, shape))
+        a32 = img(shape, 2600 + i)
+        out[f"in_{tag}"] = a32
+        wide = shape in ND_EDGE_WIDE
+        a = a32 if wide else a32.astype(np.float64)
+        nd = len(shape)
+        levels = (1, 3, 7) if nd == 1 else (1, 3, 5)
+        for fam, cls in FAM.items():
+            if wide and fam == "triangle":             # (one plane: the reach of 64 samples on Y = 3 and 5)
+                out[f"conv_{fam}_{tag}_s5"] = convolution(a.copy(), cls(nd), s=5)
+                continue
+            top = AtrousTransform(cls)(a.copy(), levels[-1]).data
+            assert top.dtype == a.dtype
+            out[f"coef_{fam}_{tag}_L{levels[-1]}"] = top
+            for L in levels[:-1]:
+                c = AtrousTransform(cls)(a.copy(), L).data
+                np.testing.assert_array_equal(c[:L], top[:L])
+                out[f"smooth_{fam}_{tag}_L{L}"] = c[L]
+            np.testing.assert_array_equal(convolution(a.copy(), cls(nd), s=0), out[f"smooth_{fam}_{tag}_L1"])
+            if not wide:
+                for s in (2, 5):
+                    out[f"conv_{fam}_{tag}_s{s}"] = convolution(a.copy(), cls(nd), s=s)
+        put(f"noise_{tag}", lambda: np.float64(AtrousTransform(B3spline)(a.copy(), 2).get_noise()))
+        put(f"den_{tag}", lambda: denoise(a.copy(), [4, 2], B3spline))
+        if min(shape) >= (5 if nd == 1 else 2):
+            put(f"wow_{tag}", lambda: wow(a.copy(), denoise_coefficients=[4], n_scales=2))
+            if wide:
+                out.pop(f"wow_{tag}_coef", None)
+        if wide:
+            continue
+        out[f"var_{tag}_s1"] = sdev_loc(a.copy(), B3spline(nd), s=1, variance=True)
+        put(f"bil_{tag}_L3", lambda: AtrousTransform(B3spline, bilateral=1)(a.copy(), 3).data)
+        put(f"rec_{tag}_L3", lambda: AtrousTransform(B3spline)(a.copy(), 3, recursive=True).data)
+        put(f"recbil_{tag}_L3", lambda: AtrousTransform(B3spline, bilateral=1)(a.copy(), 3, recursive=True).data)
+        put(f"skew5_coef_{tag}_L3", lambda: AtrousTransform(Skew5)(a.copy(), 3).data)
+        put(f"even4_recbil_{tag}_L3", lambda: AtrousTransform(Even4, bilateral=1)(a.copy(), 3, recursive=True).data)
+    save("g26_nd_edges", "1-D: hard (numpy + scipy); 3-D: semantic(cv2 stand-in); float64 but for the wide cubes", **out)
+
+
 if __name__ == "__main__":
-    if "--only" in sys.argv:                      # e.g. --only g13_richardson_lucy_fft
+    if "--only" in sys.argv:                    # e.g. --only g13_richardson_lucy_fft
         globals()[sys.argv[sys.argv.index("--only") + 1]]()
     elif REAL_NE:
         assert NE_KIND.startswith("real"), "run with /opt/conda/bin/python3.9"
@@ -916,3 +1015,4 @@ if __name__ == "__main__":
         g22_remaining_refusals()
         g23_richardson_lucy_fft_large_psf()
         g24_richardson_lucy_fft_non_pow2()
+        g26_nd_edges()

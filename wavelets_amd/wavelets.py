@@ -1087,6 +1087,10 @@ class AtrousTransform:
 
         float64 / int inputs (computed in float64 by the reference, ref:297,319-320) run on the
         float64 engine."""
+        if level < 0:
+            # ref:426-427: an empty plane stack, whose plane 0 the reference then writes (wow() asks for -1 scales
+            # when the shortest axis has fewer than 4 samples, utils.py:122-127)
+            raise IndexError(f"index 0 is out of bounds for axis 0 with size {max(level + 1, 0)}")
         if np.ndim(arr) in (1, 2, 3) and _needs_generic(self.scaling_function_class):
             return self._call_generic(arr, level, recursive)
         if _f64 and _is_f64(arr) and np.ndim(arr) in (1, 2, 3):
