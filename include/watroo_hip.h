@@ -586,7 +586,7 @@ int wt64_anscombe(wt_plan64 *plan, int src, int dst, double alpha, double g, dou
  * on all-fused schedules (wt_plan_fused_ok); built-in families only.  Every operation takes the number of
  * ACTIVE frames nf (frames 0 .. nf-1; the last chunk of a stack may be shorter than the batch).
  * Planes: 0..max_level, WT_PLANE_INPUT, WT_PLANE_OUT, WT_PLANE_SCRATCH(0/1) (scratch used internally) and the
- * two planes of wow (WT_PLANE_SCRATCH(3/4), below).  wt_batch_decompose runs a single-scale pass that has no fused
+ * planes of wow and of richardson_lucy (WT_PLANE_SCRATCH(3/4), (6 .. 10), (16 ..), below).  wt_batch_decompose runs a single-scale pass that has no fused
  * kernel on the batched per-scale stencil (levels >= 9); the other passes are fused. */
 typedef struct wt_batch wt_batch;
 int wt_batch_create(wt_ctx *ctx, int n, int H, int W, int family, int max_level, wt_batch **batch);
@@ -675,6 +675,27 @@ int wt_batch_gamma_blend(wt_batch *batch, int nf, int recon, int gamma_plane, co
 /* wt_plane_sum per frame: dst = planes [first, first + count) summed in plane order (np.sum(coefficients, axis=0),
  * watroo/utils.py:205) */
 int wt_batch_plane_sum(wt_batch *batch, int nf, int first, int count, int dst);
+/* ---- richardson_lucy over a batch (watroo/utils.py:222-290, utils.richardson_lucy per frame).  Extra planes, the
+ * per-frame call's ids, allocated on first use: WT_PLANE_SCRATCH(6 .. 10) - data, psi, phi, residual, correlation - and
+ * WT_PLANE_SCRATCH(16 + s), s < max_level, the support plane of scale s.  Every frame gets the bits of the per-frame
+ * call on a wt_plan. */
+/* One PSF operand of the call -> device memory of the batch: slot 0 the forward operand (the flipped PSF of
+ * watroo/utils.py:257), slot 1 the backward one (utils.py:286).  `kernel`: kh * kw host floats, copied before the
+ * call returns.  PSFs wt_filter2d_ex applies in one launch without bands only: kh * kw <= 4096, kw <= 512 and
+ * (64 + kw - 1) * (16 + kh - 1) * 4 <= 96 KB. */
+int wt_batch_set_psf(wt_batch *batch, int slot, const float *kernel, int kh, int kw);
+/* host logic: *ok = 1 when wt_batch_set_psf takes a kh x kw PSF (the rule above; no GPU needed) */
+int wt_batch_psf_ok(int kh, int kw, int *ok);
+/* wt_filter2d_ex per frame with the PSF of `slot` (cv2.filter2D of watroo/utils.py:257,286 with WT_BORDER_SYMMETRIC;
+ * the circular products of utils.py:245-254,284 with WT_BORDER_PERIODIC), anchor (ay, ax) inside the kernel, src != dst:
+ * one launch for all active frames, no stream drain, no PSF copy */
+int wt_batch_filter2d(wt_batch *batch, int nf, int src, int dst, int slot, int ay, int ax, int border);
+/* wt_binary over the active frames: dst = a OP b (watroo/utils.py:259,280-281,288) */
+int wt_batch_binary(wt_batch *batch, int nf, int op, int a, int b, int dst);
+/* wt_mrs_update per frame (watroo/utils.py:263-276) with the frame's tau[f] (<= 0: significance one); scalar noise
+ * only - the noise of richardson_lucy is the data's MAD estimate (utils.py:262) */
+int wt_batch_mrs_update(wt_batch *batch, int nf, int plane, int mrs_plane, const double *tau, int soft,
+                        int persistent, float inv_pow);
 
 /* ---- batches of same-shape frames (float64) ------------------------------------------------
  * A wt_batch64 is the wt_batch of the float64 engine: the stacks the reference computes in float64 (float64

@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""Stacks of float32 frames through richardson_lucy with one PSF: richardson_lucy_stack (the float32 batch: per
+iteration the PSF correlation of all frames in one launch, the operands resident in the batch, one support update per
+scale for all frames) against the per-frame loop on the same frames, same process, same card.  One JSON line per
+shape and PSF (16 x 512^2, 16 x 1024^2, 8 x 2048^2; 9 x 9 and 25 x 25 PSFs; the default three coefficients, 10
+iterations):
+  * host to host through the numpy API: richardson_lucy_stack vs a plain loop of richardson_lucy() (wall clock, each
+    call ends in its download; the two alternate sample by sample; median / min / max, >= 20 samples after warm-up)
+    and whether the two results are the same bits at that shape;
+  * device time of ONE batched correlation (wt_batch_filter2d, HIP events) against the N per-frame ones
+    (wt_filter2d_ex on pre-acquired plans, which drains the stream and copies the PSF on every call), alternating.
+The environment variable WT_BATCH_F2D_SKEW=1 makes the batched kernel use the row-skewed tap loop (one LDS read per
+four FMAs) instead of the per-image one (one per FMA): run the tool once with and once without it to compare the two
+tilings (`--correlation-only` skips the host-to-host part).
+    python tools/bench_rl_stack.py [samples] [--correlation-only]"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import wavelets_amd as W                      # noqa: E402
+from wavelets_amd import _lib as L            # noqa: E402
+from wavelets_amd import batch as B           # noqa: E402
+
+SHAPES = [(16, 512), (16, 1024), (8, 2048)]
+PSFS = [(9, 9), (25, 25)]
+ITERATIONS, COEFFICIENTS = 10, (5, 2, 1)
+
+
+def stats(ms):
+    ms = sorted(ms)
+    return {"median_ms": ms[len(ms) // 2], "min_ms": ms[0], "max_ms": ms[-1], "samples": len(ms)}
+
+
+def alternate(fa, fb, n, clock, warm=2):
+    """n samples of fa and of fb, taken in turns"""
+    for _ in range(warm):
+        fa()
+        fb()
+    a, b = [], []
+    for _ in range(n):
+        a.append(clock(fa))
+        b.append(clock(fb))
+    return a, b
+
+
+def wall(fn):
+    t = time.perf_counter()
+    fn()
+    return (time.perf_counter() - t) * 1e3
+
+
+def frames(N, side):
+    rng = np.random.default_rng(0)
+    ridge = 4 * np.exp(-((np.arange(side) - 0.45 * side) ** 2) / (2 * (0.05 * side) ** 2))[None, :]
+    fr = rng.uniform(0.5, 1.5, (N, side, side)) + ridge
+    return (fr * np.logspace(-1, 1, N)[:, None, None]).astype(np.float32)
+
+
+def make_psf(kh, kw):
+    psf = (np.outer(np.hanning(kh + 2)[1:-1], np.hanning(kw + 2)[1:-1]) + 0.05) \
+        * (1 + 0.3 * np.linspace(-1, 1, kh)[:, None] + 0.2 * np.linspace(-1, 1, kw)[None, :])
+    return (psf / psf.sum()).astype(np.float32)
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    samples = max(20, int(args[0])) if args else 20
+    corr_only = "--correlation-only" in sys.argv
+    ctx = L.default_context()
+    tiling = "row-skewed tap loop" if os.environ.get("WT_BATCH_F2D_SKEW") else "per-image tap loop"
+    for N, side in SHAPES:
+        fr = frames(N, side)
+        for kh, kw in PSFS:
+            psf = make_psf(kh, kw)
+            level = len(COEFFICIENTS)
+            assert B.rl_eligible(fr, psf, level), "not a batch case"
+            rec = {"shape": [N, side, side], "psf": [kh, kw], "iterations": ITERATIONS, "denoise_coefficients": list(COEFFICIENTS),
+                   "batched_tiling": tiling}
+            # ---- one batched correlation against N per-frame ones (device events)
+            S, D = L.PLANE_SCRATCH(7), L.PLANE_SCRATCH(8)
+            bp = L.BatchPlan(ctx, N, side, side, L.B3SPLINE, level)
+            bp.upload(S, fr)
+            bp.set_psf(0, psf)
+            plans = []
+            for f in range(N):
+                p = L.Plan(ctx, side, side, L.B3SPLINE, level)
+                p.upload(S, fr[f])
+                plans.append(p)
+
+            def device(fn):
+                ctx.timer_start()
+                fn()
+                return ctx.timer_stop()
+
+            def batched():
+                bp.filter2d(N, S, D, 0)
+
+            def loop():
+                for p in plans:
+                    p.filter2d(S, D, psf)
+
+            tb, tl = alternate(batched, loop, samples, device)
+            same = all(np.array_equal(bp.download(D, N)[f].view(np.uint32), plans[f].download(D).view(np.uint32)) for f in range(N))
+            b, lp = stats(tb), stats(tl)
+            gfma = N * side * side * kh * kw / 1e9
+            rec["device_correlation"] = {"batched": b, "loop_of_per_frame_calls": lp, "speedup": lp["median_ms"] / b["median_ms"],
+                                         "speedup_range": [lp["min_ms"] / b["max_ms"], lp["max_ms"] / b["min_ms"]],
+                                         "batched_tfma_per_s": gfma / b["median_ms"], "bit_identical": bool(same)}
+            bp.close()
+            for p in plans:
+                p.close()
+            # ---- host to host
+            if not corr_only:
+                kw_rl = dict(iterations=ITERATIONS, denoise_coefficients=COEFFICIENTS)
+                got = W.richardson_lucy_stack(fr, psf, **kw_rl)
+                exp = np.stack([W.richardson_lucy(f, psf, **kw_rl) for f in fr])
+                ts, tl = alternate(lambda: W.richardson_lucy_stack(fr, psf, **kw_rl),
+                                   lambda: [W.richardson_lucy(f, psf, **kw_rl) for f in fr], samples, wall, warm=1)
+                hs, hl = stats(ts), stats(tl)
+                rec["host_to_host"] = {"richardson_lucy_stack": hs, "richardson_lucy_loop": hl, "speedup": hl["median_ms"] / hs["median_ms"],
+                                       "stack_median_below_loop_min": hs["median_ms"] < hl["min_ms"],
+                                       "bit_identical": bool(np.array_equal(got.view(np.uint32), exp.view(np.uint32)))}
+            L.trim_batches()
+            print(json.dumps(rec), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -232,6 +232,12 @@ SIGNATURES = {
     "wt_batch_reduce": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double)]),
     "wt_batch_gamma_blend": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _fp, _fp, _c.c_float, _c.c_float]),
     "wt_batch_plane_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch_set_psf": (_c.c_int, [_vp, _c.c_int, _fp, _c.c_int, _c.c_int]),
+    "wt_batch_psf_ok": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
+    "wt_batch_filter2d": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch_binary": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch_mrs_update": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _c.c_int,
+                                       _c.c_float]),
     # batches of same-shape frames in float64 (wt_batch64)
     "wt_batch64_fused_ok": (_c.c_int, [_c.c_int, _i64, _i64, _c.c_int, _c.POINTER(_c.c_int)]),
     "wt_batch64_create": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_vp)]),
@@ -1010,6 +1016,14 @@ def _enhance_rows(nf, taus, wgts):
     return n, ta, wa
 
 
+def batch_psf_ok(kh, kw):
+    """True when a batch takes a kh x kw PSF (host logic, wt_batch_psf_ok): one Plan.filter2d applies in a single
+    launch without bands - at most 4096 taps in rows of at most 512, an LDS tile of at most 96 KB"""
+    ok = _c.c_int(0)
+    check(load().wt_batch_psf_ok(int(kh), int(kw), _c.byref(ok)))
+    return bool(ok.value)
+
+
 class BatchPlan:
     """Device planes of up to `n` frames of one H x W shape (wt_batch).  Operations take the number of
     active frames `nf` (frames 0 .. nf-1); upload / download move a C-contiguous (nf, H, W) block."""
@@ -1155,6 +1169,30 @@ class BatchPlan:
 
     def plane_sum(self, nf, first, count, dst=PLANE_OUT):
         check(load().wt_batch_plane_sum(self._h, nf, first, count, dst))
+
+    # -- richardson_lucy (wt_batch_set_psf / _filter2d / _binary / _mrs_update)
+    def set_psf(self, slot, kernel):
+        """PSF operand `slot` (0: forward, 1: backward) of the batch <- `kernel`, once per call of the stack function"""
+        k = np.ascontiguousarray(kernel, dtype=np.float32)
+        if k.ndim != 2:
+            raise ValueError("set_psf kernel must be 2-D")
+        check(load().wt_batch_set_psf(self._h, slot, k.ctypes.data_as(_fp), k.shape[0], k.shape[1]))
+        self._psf_shape = getattr(self, "_psf_shape", {})
+        self._psf_shape[slot] = k.shape
+
+    def filter2d(self, nf, src, dst, slot, anchor=None, periodic=False):
+        """Plan.filter2d per frame with the PSF of `slot`: one launch for frames 0 .. nf-1"""
+        kh, kw = getattr(self, "_psf_shape", {}).get(slot, (1, 1))
+        ay, ax = (kh // 2, kw // 2) if anchor is None else anchor
+        check(load().wt_batch_filter2d(self._h, nf, src, dst, slot, ay, ax, 3 if periodic else 0))
+
+    def binary(self, nf, op, a, b, dst):
+        check(load().wt_batch_binary(self._h, nf, {"sub": 0, "add": 1, "mul": 2, "div": 3, "add_div": 4}[op], a, b, dst))
+
+    def mrs_update(self, nf, plane, mrs_plane, taus, soft, persistent, inv_pow):
+        """Plan.mrs_update per frame, scalar noise: taus[f] (0.0: significance one)"""
+        t = self._per_frame(taus, nf, _c.c_double, "mrs_update taus")
+        check(load().wt_batch_mrs_update(self._h, nf, plane, mrs_plane, t, int(soft), int(persistent), float(inv_pow)))
 
 
 def batch64_fused_ok(family, H, W, level):

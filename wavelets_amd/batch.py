@@ -6,6 +6,7 @@ back in one host round trip, and the pointwise steps run once over the stack.
     denoise_stack(frames, weights)      == np.stack([denoise(f, weights, sf, noise_i, ...) for f in frames])
     wow_stack(frames, ...)              == np.stack([wow(f, ..., noise=noise_i, ...)[0] for f in frames])
     enhance_stack(frames, [noise,] ...) == np.stack([enhance(f, [noise_i,] ...) for f in frames])   (gray or colour frames)
+    richardson_lucy_stack(frames, psf, ...) == np.stack([richardson_lucy(f, psf, ...) for f in frames])   (one PSF)
 
 bit for bit.  The sequence of operations per frame is the per-frame path's own (wavelets._interleave_split,
 _tau_row, _noise_from_median, _sigma_bilateral_list; utils._wow_lists, _wow_factor, _gamma_range,
@@ -28,10 +29,12 @@ from . import _lib
 from ._lib import PLANE_INPUT, PLANE_OUT, PLANE_NONE, PLANE_SCRATCH, FLAG_FUSED
 from .wavelets import (AtrousTransform, B3spline, _family_of, _needs_generic, _interleave_split, _tau_row, _map_tau_row,
                        _noise_from_median, _sigma_bilateral_list, _result_dtype, _NOISE_PLANE)
+from . import utils as _utils
+from .utils import (richardson_lucy, _rl_check_fft_width, _rl_direct_operands)
 from .utils import (denoise, wow, enhance, _enhance_lists, _GAMMA_PLANE, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments,
                     _wow_factor, _gamma_range, _wow_sigma_bilateral)
 
-__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'enhance_stack', 'batch_eligible', 'batch64_eligible',
+__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'enhance_stack', 'richardson_lucy_stack', 'rl_eligible', 'batch_eligible', 'batch64_eligible',
            'wow_eligible', 'wow64_eligible', 'bilateral_eligible', 'bilateral64_eligible', 'enhance_eligible',
            'noise_map_eligible']
 
@@ -843,3 +846,102 @@ def _enhance_group(fr, res, per, plans, level, route, atrous, soft_threshold):
                     bp.download(PLANE_OUT, n, out=res[i0:i0 + n] if c is Ellipsis else res[i0:i0 + n, c], f0=j * n)
     finally:
         release(bp)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# richardson_lucy over stacks of frames with one PSF (utils.richardson_lucy, ref utils.py:222-290)
+# ---------------------------------------------------------------------------------------------------------------
+# planes per frame of a richardson_lucy chunk beyond batch_frame_bytes' level + 5: data, psi, phi, residual and
+# correlation, one support plane per scale (2 * level + 9 in all, the input and output planes counted though unused)
+def _rl_extra_planes(level):
+    return level + 4
+
+
+def rl_eligible(frames, psf, level, uniform_init=False, fft=False):
+    """True when the batched engine computes richardson_lucy over this stack (host logic): native float32 frames in
+    an (N, H, W) array (_engine_eligible), level = len(denoise_coefficients) with an all-fused schedule (2..8), no
+    uniform_init, and a 2-D PSF whose two operands (utils._rl_direct_operands: with fft=True an odd height or a
+    one-row PSF adds a zero row) the per-frame call applies in a single launch without bands (_lib.batch_psf_ok:
+    at most 4096 taps in rows of at most 512, an LDS tile of at most 96 KB).  With fft=True also
+    kh * kw < utils._FFT_MIN_TAPS, kh <= H and kw <= W: the per-frame call then takes the direct periodic form (no
+    FFT, and an extended frame is never worth it below that many taps).  Everything else runs the per-frame loop."""
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level not in BATCH_LEVELS:
+        return False
+    if uniform_init:
+        return False
+    if not isinstance(frames, np.ndarray) or not _engine_eligible(frames, B3spline, None, [None] * len(frames)):
+        return False
+    psf = np.asarray(psf)
+    if psf.ndim != 2 or psf.dtype.kind not in "biuf" or psf.size == 0:
+        return False
+    H, W = frames.shape[1:]
+    kh, kw = psf.shape
+    if fft and (kh * kw >= _utils._FFT_MIN_TAPS or kh > H or kw > W):
+        return False
+    (fwd_k, _), (bwd_k, _) = _rl_direct_operands(psf, H, fft)
+    return _lib.batch_psf_ok(*fwd_k.shape) and _lib.batch_psf_ok(*bwd_k.shape)
+
+
+def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2, 1), threshold_type='soft',
+                          uniform_init=False, persistent_mrs=True, fft=False, out=None):
+    """(N, H, W): utils.richardson_lucy of every frame with the one PSF `psf` (ref utils.py:222-290), batched -
+    result[i] equals richardson_lucy(frames[i], psf, iterations, denoise_coefficients, threshold_type, uniform_init,
+    persistent_mrs, fft) bit for bit.
+
+    Per chunk (rl_eligible stacks): upload, transform, the MAD medians of all frames in one round trip, the
+    thresholded sum as the initial estimate; then per iteration the PSF correlation of all frames in one launch
+    (the two operands lie in the batch: no stream drain, no PSF copy), the residual, its transform, one support
+    update per scale with each frame's threshold, the plane sum, the ratio, the second correlation and the product
+    - nothing returns to the host until the chunk's estimates.  Everything else runs the per-frame loop."""
+    fr = _as_frames(frames)
+    if np.ndim(psf) != 2:
+        raise ValueError("psf must be 2-D")
+    _rl_check_fft_width(fft, fr[0].shape[1])
+    level = len(denoise_coefficients)
+    if not rl_eligible(fr, psf, level, uniform_init, fft):
+        return _hand_over(np.stack([richardson_lucy(f, psf, iterations=iterations, denoise_coefficients=denoise_coefficients,
+                                                    threshold_type=threshold_type, uniform_init=uniform_init,
+                                                    persistent_mrs=persistent_mrs, fft=fft) for f in fr]), out)
+    N, H, W = fr.shape
+    out = _f32_target(out, (N, H, W))
+    ctx = _lib.default_context()
+    soft = threshold_type == 'soft'
+    sf = B3spline(2)                                                             # ref:229 default transform
+    sigma_e = sf.sigma_e()
+    DATA, PSI, PHI, RES, CONV = (PLANE_SCRATCH(i) for i in (6, 7, 8, 9, 10))     # (the per-frame call's plane ids)
+    MRS = [PLANE_SCRATCH(16 + s) for s in range(level)]
+    (fwd_k, fwd), (bwd_k, bwd) = _rl_direct_operands(np.ascontiguousarray(psf, dtype=np.float32), H, fft)
+    # Coefficients._denoise_sum(list(denoise_coefficients)): the (scale, sigma, weight) entries of the initial estimate
+    entries = list(zip(range(level + 1), denoise_coefficients, (1,) * level))
+    chunks = _lib.batch_chunks(N, H, W, level, extra_planes=_rl_extra_planes(level))
+    bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, _family_of(sf), level)
+    try:
+        bp.set_psf(0, fwd_k)
+        bp.set_psf(1, bwd_k)
+        for f0, nf in chunks:
+            bp.upload(DATA, fr[f0:f0 + nf])
+            bp.decompose(nf, DATA, level, FLAG_FUSED)                            # ref:230
+            noises = [None] * nf
+            if any(c != 0 for c in denoise_coefficients):                        # ref:131-132 (lazy, Coefficients._tau)
+                noises = [_noise_from_median(m, sigma_e) for m in bp.abs_median(nf, 0)]
+            taus = [_tau_row(entries, n, sigma_e, soft) for n in noises]
+            bp.denoise_sum(nf, level + 1, taus, [w for _, _, w in entries], soft, write_back=True, dst=PSI)   # ref:236-237
+            for m in MRS:                                                        # ref:240-243
+                bp.fill(nf, m, 1.0 if soft else 0.0)
+            # the data's noise serves every iteration (ref:262): one threshold per frame and scale
+            scale_taus = [[_tau_row([(s, c, None)], n, sigma_e, soft)[0] for n in noises]
+                          for s, c in enumerate(denoise_coefficients)]
+            for iteration in range(iterations):                                  # ref:252
+                bp.filter2d(nf, PSI, PHI, 0, **fwd)                              # ref:254-257
+                bp.binary(nf, "sub", DATA, PHI, RES)                             # ref:259
+                bp.decompose(nf, RES, level, FLAG_FUSED)                         # ref:261
+                for s in range(level):                                           # ref:263-276
+                    bp.mrs_update(nf, s, MRS[s], scale_taus[s], soft, persistent_mrs, 1.0 / (iteration + 1))
+                bp.plane_sum(nf, 0, level + 1, RES)                              # ref:278
+                bp.binary(nf, "add_div", RES, PHI, RES)                          # ref:280-281
+                bp.filter2d(nf, RES, CONV, 1, **bwd)                             # ref:284-286
+                bp.binary(nf, "mul", PSI, CONV, PSI)                             # ref:288
+            bp.download(PSI, nf, out=out[f0:f0 + nf])
+    finally:
+        _lib.release_batch(bp)
+    return out

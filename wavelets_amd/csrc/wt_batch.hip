@@ -13,6 +13,9 @@
 // wt_stencil32_batch.hip (the frame's tau and factor from a small device table), the pointwise update, the
 // {sum, sumsq, min, max} moments (one host round trip for all frames), the gamma blend, the fill and the plane
 // sum run once over the stack, each frame with its own parameters and the bits of the per-frame call.
+// richardson_lucy (watroo/utils.py:222-290) runs on a batch as well: the PSF correlation of all frames is one launch
+// (wt_batch_filter2d_kernel, the frame as grid z, the two operands resident in the batch), the binary ops run once
+// over the stack, the support update takes the frame's threshold from a device table.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -20,6 +23,7 @@
 #include "wt_host.h"
 #include "wt_fused_decl.h"
 #include "wt_reduce.h"
+#include "wt_rl_point.h"
 #include "wt_rng.h"
 #include "wt_stencil_launch.h"
 #include "wt_unit_probe.h"
@@ -48,6 +52,13 @@ struct wt_batch {
     // wt_wow_scale does), WT_PLANE_SCRATCH(4) = the gamma accumulator (utils.wow's plane ids)
     float *spare = nullptr, *gamma = nullptr;
     float *noise = nullptr;         // WT_PLANE_SCRATCH(5): the per-pixel noise maps of the frames (Coefficients' noise plane id)
+    // richardson_lucy: WT_PLANE_SCRATCH(6 .. 10) = data, psi, phi, residual, correlation; WT_PLANE_SCRATCH(16 + s) = the
+    // support plane of scale s (utils.richardson_lucy's plane ids); the forward / backward PSF of wt_batch_set_psf
+    float *rl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    std::vector<float *> mrs;       // max_level entries
+    float *d_psf[2] = {nullptr, nullptr};
+    size_t psf_cap[2] = {0, 0};
+    int psf_kh[2] = {0, 0}, psf_kw[2] = {0, 0};
     // per-frame parameter pairs of one launch ({tau, factor}, {gmin, gmax}): a ring of table slots [n][2], pinned
     // staging + device copy; a slot is refilled only after the copy that last read it has completed (its event)
     static constexpr int kTabSlots = 16;
@@ -331,6 +342,63 @@ __global__ __launch_bounds__(256) void wt_batch_replicate_kernel(float *d, int64
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < f4; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
+// wt_filter2d_kernel (wt_kernels_apps.h) for the frames of a batch: grid z = the frame, each its own image (the
+// border rules act at the frame's borders).  Staging, tile geometry and the chain of fmaf per output are
+// wt_rl_point.h's; !SKEW is the per-image tap loop (one LDS read per FMA), the one wt_batch_filter2d launches; SKEW
+// walks every staged row once for the four output rows of a thread (wt_f2d_taps_skewed: one LDS read per four FMAs,
+// measured slower) - identical bits either way.
+template <bool WRAP, bool SKEW>
+__global__ __launch_bounds__(256) void wt_batch_filter2d_kernel(const float *in, float *out, Geo g, int64_t fstride, const float *__restrict__ psf,
+                                                                int kh, int kw, int ay, int ax)
+{
+    extern __shared__ float tile[];
+    in += (int64_t)blockIdx.z * fstride;
+    out += (int64_t)blockIdx.z * fstride;
+    const int tw = WT_F2D_TW + kw - 1, th = WT_F2D_TH + kh - 1;
+    const int x0 = blockIdx.x * WT_F2D_TW, ly0 = blockIdx.y * WT_F2D_TH;
+    wt_f2d_stage<WRAP>(tile, in, g, x0, ly0, tw, th, ay, ax);
+    __syncthreads();
+    const int x = x0 + threadIdx.x;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (SKEW) wt_f2d_taps_skewed(tile, tw, psf, kh, kw, acc);
+    else wt_f2d_taps(tile, tw, psf, kw, kh, kw, acc);
+    if (x < g.W) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ly = ly0 + threadIdx.y * 4 + r;
+            if (ly < g.H) out[(int64_t)ly * g.P + x] = acc[r];
+        }
+    }
+}
+
+// wt_mrs_kernel (wt_kernels_apps.h) with the frame as grid y and its own tau (ptab[2 * f]; <= 0: significance one);
+// no noise map - richardson_lucy's noise is the data's MAD estimate.  Same wt_mrs_point: the bits of the per-frame call.
+__global__ __launch_bounds__(256) void wt_batch_mrs_kernel(float *c, float *mrs, int64_t f4, const double *ptab, int soft, int persistent,
+                                                           float inv_pow)
+{
+    const int f = blockIdx.y;
+    const double tau = ptab[2 * f];
+    const float tauf = (float)tau;
+    float4 *cf = reinterpret_cast<float4 *>(c) + (int64_t)f * f4;
+    float4 *mf = reinterpret_cast<float4 *>(mrs) + (int64_t)f * f4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < f4; i += (int64_t)gridDim.x * blockDim.x) {
+        const float4 v = cf[i];
+        const float4 m4 = mf[i];
+        float cc[4] = {v.x, v.y, v.z, v.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wt_mrs_point(cc[k], mm[k], 1.f, tau, tauf, soft, persistent, inv_pow);
+        cf[i] = make_float4(cc[0], cc[1], cc[2], cc[3]);
+        mf[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+    }
+}
+
+// wt_binary_kernel (wt_kernels_apps.h) over the active frames, one flat range (wt_binary_point4)
+__global__ __launch_bounds__(256) void wt_batch_binary_kernel(const float *a, const float *b, float *dst, int64_t n4, int op)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+        reinterpret_cast<float4 *>(dst)[i] = wt_binary_point4(reinterpret_cast<const float4 *>(a)[i], reinterpret_cast<const float4 *>(b)[i], op);
+}
+
 // wt_reduce_kernel + wt_reduce_final_kernel per frame (grid y / the final block = the frame): the per-frame
 // work split (gridDim.x blocks) and fold order of wt_reduce.h, i.e. the doubles of the per-frame call
 #define WT_REDUCE_KERNEL_NAME wt_batch_reduce_kernel
@@ -355,7 +423,11 @@ static int bplane(wt_batch *b, int id, float **out)
     else if (id == WT_PLANE_SCRATCH(3)) slot = &b->spare;
     else if (id == WT_PLANE_SCRATCH(4)) slot = &b->gamma;
     else if (id == WT_PLANE_SCRATCH(5)) slot = &b->noise;
-    if (!slot) WT_FAIL("wt_batch: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1/3/4/5)", id, b->max_level);
+    else if (id <= WT_PLANE_SCRATCH(6) && id >= WT_PLANE_SCRATCH(10)) slot = &b->rl[WT_PLANE_SCRATCH(6) - id];
+    else if (id <= WT_PLANE_SCRATCH(16) && id > WT_PLANE_SCRATCH(16) - (int)b->mrs.size()) slot = &b->mrs[WT_PLANE_SCRATCH(16) - id];
+    if (!slot)
+        WT_FAIL("wt_batch: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1/3/4/5, 6..10, 16..%d)", id, b->max_level,
+                15 + (int)b->mrs.size());
     if (!*slot) WT_HIP(hipMalloc((void **)slot, (size_t)b->n * (size_t)b->fstride * sizeof(float)));
     *out = *slot;
     return 0;
@@ -496,6 +568,7 @@ extern "C" int wt_batch_create(wt_ctx *ctx, int n, int H, int W, int family, int
     b->geo.g = Geo{W, (W + 3) / 4 * 4, H, 0, H, 0, 0};
     b->fstride = (int64_t)H * b->geo.g.P;
     b->coef.assign(max_level + 1, nullptr);
+    b->mrs.assign(std::min(max_level, WT_NUM_SCRATCH - 16), nullptr);
     if (!wt_fused_supported(&b->geo)) {
         delete b;
         WT_FAIL("wt_batch_create: rows of %d pixels are too wide for the fused passes", W);
@@ -539,6 +612,10 @@ extern "C" int wt_batch_destroy(wt_batch *b)
     f(b->spare);
     f(b->gamma);
     f(b->noise);
+    for (float *q : b->rl) f(q);
+    for (float *q : b->mrs) f(q);
+    f(b->d_psf[0]);
+    f(b->d_psf[1]);
     f(b->d_ptab);
     f(b->d_red);
     if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) bad = 1;
@@ -1041,4 +1118,117 @@ extern "C" int wt_batch_plane_sum(wt_batch *b, int nf, int first, int count, int
     WT_TRY(bplane(b, dst, &o));
     // the frames back to back are one flat range: wt_plane_sum_kernel over all of them
     return launch_plane_sum(b->ctx, planes, count, o, (int64_t)nf * b->fstride / 4);
+}
+
+// ------------------------------------------------------------------------------------------------ richardson_lucy
+// host logic: *ok = 1 when wt_batch_set_psf takes a kh x kw PSF - one wt_filter2d_ex applies in ONE launch
+extern "C" int wt_batch_psf_ok(int kh, int kw, int *ok)
+{
+    if (!ok) WT_FAIL("wt_batch_psf_ok: null pointer");
+    *ok = wt_f2d_single_launch(kh, kw) ? 1 : 0;
+    return 0;
+}
+
+// One of the two PSF operands of a richardson_lucy call (slot 0: forward, watroo/utils.py:257; slot 1: backward,
+// utils.py:286) -> device memory of the batch, once per call: the iterations then correlate without a stream drain
+// and without a PSF copy (wt_filter2d_ex does both on every call - its kernel comes from caller-owned memory).
+extern "C" int wt_batch_set_psf(wt_batch *b, int slot, const float *kernel, int kh, int kw)
+{
+    if (!b || !kernel) WT_FAIL("wt_batch_set_psf: null pointer");
+    WtGuard guard_(b->ctx);
+    if (slot < 0 || slot > 1) WT_FAIL("wt_batch_set_psf: slot %d (0: forward, 1: backward)", slot);
+    if (!wt_f2d_single_launch(kh, kw))
+        WT_FAIL("wt_batch_set_psf: a %d x %d PSF is not applied in one launch (at most %d taps, rows of at most %d, an LDS tile of at most %d KB)",
+                kh, kw, WT_F2D_MAX_TAPS, WT_F2D_MAX_KW, WT_F2D_MAX_LDS / 1024);
+    const size_t ntaps = (size_t)kh * kw;
+    // a launch on the stream may still read the slot, and `kernel` is the caller's: drain, then copy synchronously
+    WT_HIP(hipStreamSynchronize(b->ctx->stream));
+    if (ntaps > b->psf_cap[slot]) {
+        (void)hipFree(b->d_psf[slot]);
+        b->d_psf[slot] = nullptr;
+        b->psf_cap[slot] = 0;
+        b->psf_kh[slot] = b->psf_kw[slot] = 0;
+        WT_HIP(hipMalloc((void **)&b->d_psf[slot], ntaps * sizeof(float)));
+        b->psf_cap[slot] = ntaps;
+    }
+    WT_HIP(hipMemcpy(b->d_psf[slot], kernel, ntaps * sizeof(float), hipMemcpyHostToDevice));
+    b->psf_kh[slot] = kh;
+    b->psf_kw[slot] = kw;
+    return 0;
+}
+
+// wt_filter2d_ex per frame (watroo/utils.py:257,286; periodic: the circular products of utils.py:245-254,284) with
+// the PSF of `slot`: one launch for all active frames
+// (measured, tools/bench_rl_stack.py: the per-image tap loop is about twice as fast as the row-skewed one at every
+//  shape - 10 to 18 against 5 to 10 TFMA/s - so the skewed loop runs only on request, for that measurement)
+static int g_batch_f2d_plain = getenv("WT_BATCH_F2D_SKEW") ? 0 : 1;
+extern "C" int wt_batch_filter2d(wt_batch *b, int nf, int src, int dst, int slot, int ay, int ax, int border)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_filter2d"));
+    WtGuard guard_(b->ctx);
+    if (slot < 0 || slot > 1 || !b->d_psf[slot] || !b->psf_kh[slot]) WT_FAIL("wt_batch_filter2d: PSF slot %d is not set (wt_batch_set_psf)", slot);
+    const int kh = b->psf_kh[slot], kw = b->psf_kw[slot];
+    if (!wt_f2d_single_launch(kh, kw)) WT_FAIL("wt_batch_filter2d: a %d x %d PSF is not applied in one launch", kh, kw);
+    if (ay < 0 || ay >= kh || ax < 0 || ax >= kw) WT_FAIL("wt_batch_filter2d: anchor (%d, %d) outside the %d x %d kernel", ay, ax, kh, kw);
+    if (src == dst) WT_FAIL("wt_batch_filter2d: src and dst must differ");
+    if (border != WT_BORDER_SYMMETRIC && border != WT_BORDER_PERIODIC) WT_FAIL("wt_batch_filter2d: border %d unsupported (symmetric or periodic)", border);
+    const Geo &g = b->geo.g;
+    dim3 grid((g.W + WT_F2D_TW - 1) / WT_F2D_TW, (g.H + WT_F2D_TH - 1) / WT_F2D_TH, nf), block(64, 4);
+    if (grid.y > 65535u) WT_FAIL("wt_batch_filter2d: frames of %d rows are too tall (%u row tiles, at most 65535)", g.H, grid.y);
+    if (grid.z > 65535u) WT_FAIL("wt_batch_filter2d: %d frames in one launch (at most 65535)", nf);
+    float *in = nullptr, *o = nullptr;
+    WT_TRY(bplane(b, src, &in));
+    WT_TRY(bplane(b, dst, &o));
+    const size_t lds = wt_f2d_lds_bytes(kh, kw);
+    ProfScope ps(b->ctx, "wt_batch_filter2d_kernel");
+    #define WT_BF2D_LAUNCH(WRAP, SKEW)                                                                                               \
+        do {                                                                                                                         \
+            if (lds > 64 * 1024)                                                                                                     \
+                WT_HIP(hipFuncSetAttribute((const void *)wt_batch_filter2d_kernel<WRAP, SKEW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            hipLaunchKernelGGL((wt_batch_filter2d_kernel<WRAP, SKEW>), grid, block, lds, b->ctx->stream, (const float *)in, o, g, b->fstride, \
+                               (const float *)b->d_psf[slot], kh, kw, ay, ax);                                                       \
+        } while (0)
+    if (border == WT_BORDER_PERIODIC) { if (g_batch_f2d_plain) WT_BF2D_LAUNCH(true, false); else WT_BF2D_LAUNCH(true, true); }
+    else { if (g_batch_f2d_plain) WT_BF2D_LAUNCH(false, false); else WT_BF2D_LAUNCH(false, true); }
+    #undef WT_BF2D_LAUNCH
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+// wt_binary over the active frames (watroo/utils.py:259,280-281,288)
+extern "C" int wt_batch_binary(wt_batch *b, int nf, int op, int a, int b2, int dst)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_binary"));
+    WtGuard guard_(b->ctx);
+    if (op < 0 || op > WT_OP_ADD_DIV) WT_FAIL("wt_batch_binary: unknown op %d", op);
+    float *pa = nullptr, *pb = nullptr, *pd = nullptr;
+    WT_TRY(bplane(b, a, &pa));
+    WT_TRY(bplane(b, b2, &pb));
+    WT_TRY(bplane(b, dst, &pd));
+    const int64_t n4 = (int64_t)nf * b->fstride / 4;
+    ProfScope ps(b->ctx, "wt_batch_binary_kernel");
+    hipLaunchKernelGGL(wt_batch_binary_kernel, dim3(flat_grid(n4)), dim3(256), 0, b->ctx->stream, (const float *)pa, (const float *)pb, pd, n4, op);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+// wt_mrs_update per frame (watroo/utils.py:263-276) with the frame's tau[f]; scalar noise only
+extern "C" int wt_batch_mrs_update(wt_batch *b, int nf, int plane, int mrs_plane, const double *tau, int soft, int persistent, float inv_pow)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_mrs_update"));
+    WtGuard guard_(b->ctx);
+    if (!tau) WT_FAIL("wt_batch_mrs_update: null tau");
+    if (plane == mrs_plane) WT_FAIL("wt_batch_mrs_update: plane and mrs_plane must differ");
+    float *c = nullptr, *m = nullptr;
+    WT_TRY(bplane(b, plane, &c));
+    WT_TRY(bplane(b, mrs_plane, &m));
+    std::vector<double> pairs((size_t)nf * 2, 0.0);
+    for (int f = 0; f < nf; ++f) pairs[2 * f] = tau[f];
+    const double *dt = nullptr;
+    WT_TRY(batch_table(b, nf, pairs.data(), &dt));
+    ProfScope ps(b->ctx, "wt_batch_mrs_kernel");
+    hipLaunchKernelGGL(wt_batch_mrs_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, c, m, b->fstride / 4, dt, soft, persistent,
+                       inv_pow);
+    WT_HIP(hipGetLastError());
+    return 0;
 }

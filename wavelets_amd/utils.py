@@ -523,6 +523,31 @@ class _ExtendedFFT:
             self.big = None
 
 
+def _rl_check_fft_width(fft, W):
+    """richardson_lucy(fft=True) on an odd image width: the reference's own failure, as a ValueError"""
+    if fft and W % 2:
+        raise ValueError("richardson_lucy(fft=True) needs an even image width (numpy.fft.irfft2 "
+                         "returns W - 1 columns in the reference)")
+
+
+def _rl_direct_operands(psf, H, fft):
+    """((forward kernel, filter2d keywords), (backward kernel, filter2d keywords)) of richardson_lucy's two direct
+    PSF products on images of H rows (ref:255-257, 284-286): correlation with the flipped PSF, then with the PSF,
+    symmetric border, anchor at the centre.
+    fft=True: psi (*) psf circular with the PSF centre psf.shape // 2 at the origin (ref:246-250)
+    = periodic correlation with the flipped PSF anchored at k - 1 - k // 2; the second product
+    with conj(fft_psf) (ref:284) = periodic correlation with the PSF anchored at k // 2.  For an
+    ODD image height the reference's two rolls by H // 2 leave the PSF centre one row above the
+    origin, which moves the row anchors by one (g17_rl_fft_odd.npz)."""
+    psf_flipped = np.ascontiguousarray(psf[::-1, ::-1])
+    if not fft:
+        return (psf_flipped, {}), (psf, {})
+    kh, kw = psf.shape
+    e = H % 2
+    return (_periodic_operand(psf_flipped, kh - 1 - kh // 2 - e, kw - 1 - kw // 2),
+            _periodic_operand(psf, kh // 2 + e, kw // 2))
+
+
 def richardson_lucy(data, psf,
                     iterations=10, denoise_coefficients=(5, 2, 1),
                     threshold_type='soft', uniform_init=False, persistent_mrs=True, fft=False):
@@ -566,18 +591,10 @@ def richardson_lucy(data, psf,
         plan.copy(PLANE_OUT, PSI)
     for m in MRS:                                                        # ref:240-243
         plan.fill(m, 1.0 if soft else 0.0)
-    psf_flipped = np.ascontiguousarray(psf[::-1, ::-1])
     kh, kw = psf.shape
-    # fft=True: psi (*) psf circular with the PSF centre psf.shape // 2 at the origin (ref:246-250)
-    # = periodic correlation with the flipped PSF anchored at k - 1 - k // 2; the second product
-    # with conj(fft_psf) (ref:284) = periodic correlation with the PSF anchored at k // 2.  For an
-    # ODD image height the reference's two rolls by H // 2 leave the PSF centre one row above the
-    # origin, which moves the row anchors by one (g17_rl_fft_odd.npz); odd widths are not valid
-    # in the reference (irfft2 returns W - 1 columns).
-    if fft and img.shape[1] % 2:
-        raise ValueError("richardson_lucy(fft=True) needs an even image width (numpy.fft.irfft2 "
-                         "returns W - 1 columns in the reference)")
-    e = img.shape[0] % 2
+    # (the direct products' operands and anchors: _rl_direct_operands; odd widths are not valid with fft=True
+    #  in the reference - irfft2 returns W - 1 columns)
+    _rl_check_fft_width(fft, img.shape[1])
     # Large PSFs on images with 5-smooth sides: the products run through the engine's own FFT (wt_fft_apply:
     # row FFTs in LDS, transposes, the spectrum product fused into the first inverse pass) instead of
     # the direct periodic form, which costs kh * kw taps per pixel.  The periodic kernel image is built
@@ -604,9 +621,7 @@ def richardson_lucy(data, psf,
         fwd_k = bwd_k = None
         fwd = bwd = {}
     else:
-        fwd_k, fwd = _periodic_operand(psf_flipped, kh - 1 - kh // 2 - e, kw - 1 - kw // 2) if fft \
-            else (psf_flipped, {})
-        bwd_k, bwd = _periodic_operand(psf, kh // 2 + e, kw // 2) if fft else (psf, {})
+        (fwd_k, fwd), (bwd_k, bwd) = _rl_direct_operands(psf, img.shape[0], fft)
     data_noise = coefficients.noise       # None with uniform_init: every iteration then estimates
     try:
         for iteration in range(iterations):                                  # ref:252
