@@ -696,6 +696,19 @@ int wt_batch_binary(wt_batch *batch, int nf, int op, int a, int b, int dst);
  * only - the noise of richardson_lucy is the data's MAD estimate (utils.py:262) */
 int wt_batch_mrs_update(wt_batch *batch, int nf, int plane, int mrs_plane, const double *tau, int soft,
                         int persistent, float inv_pow);
+/* The circular products of richardson_lucy(fft=True) for PSFs the per-frame call hands to wt_fft_apply
+ * (watroo/utils.py:245-254, 284), over a batch: the FFT kernels of wt_fft_spectrum / wt_fft_apply with the frame as a
+ * grid dimension and ONE kernel spectrum for all frames.  Work buffers (two complex arrays of n * H * W, one H * W
+ * spectrum, two twiddle tables) are allocated by the first wt_batch_fft_spectrum and freed with the batch. */
+/* host logic: *ok = 1 when batches of H x W frames take these products (wt_fft_supported's rule; no GPU needed) */
+int wt_batch_fft_ok(int64_t H, int64_t W, int *ok);
+/* the kernel spectrum of the batch <- the forward transform of FRAME 0 of plane src, where the caller uploaded the PSF
+ * placed periodically (fft_psf of watroo/utils.py:246-251); once per call of the stack function, every chunk reuses it */
+int wt_batch_fft_spectrum(wt_batch *batch, int src);
+/* wt_fft_apply per frame: dst = irfft2(rfft2(src) * K) (watroo/utils.py:254) or, conj, * conj(K) (utils.py:284) for
+ * frames 0 .. nf-1, src != dst, after wt_batch_fft_spectrum: six launches whatever nf is, no stream drain, no host
+ * round trip */
+int wt_batch_fft_apply(wt_batch *batch, int nf, int src, int dst, int conj);
 
 /* ---- batches of same-shape frames (float64) ------------------------------------------------
  * A wt_batch64 is the wt_batch of the float64 engine: the stacks the reference computes in float64 (float64

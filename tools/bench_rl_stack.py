@@ -12,7 +12,11 @@ iterations):
 The environment variable WT_BATCH_F2D_SKEW=1 makes the batched kernel use the row-skewed tap loop (one LDS read per
 four FMAs) instead of the per-image one (one per FMA): run the tool once with and once without it to compare the two
 tilings (`--correlation-only` skips the host-to-host part).
-    python tools/bench_rl_stack.py [samples] [--correlation-only]"""
+`--fft`: the same two measurements for fft=True with PSFs the per-frame call hands to the engine's FFT (16 x 512^2 with
+33 x 33, 16 x 1024^2 with 65 x 65, 8 x 2048^2 with 129 x 129): richardson_lucy_stack(fft=True) on the batched FFT
+products against the loop of richardson_lucy(fft=True), and ONE batched product of the whole stack (wt_batch_fft_apply,
+six launches) against N wt_fft_apply calls on pre-acquired plans (HIP events).
+    python tools/bench_rl_stack.py [samples] [--correlation-only] [--fft]"""
 import json
 import os
 import sys
@@ -25,9 +29,11 @@ sys.path.insert(0, ROOT)
 import wavelets_amd as W                      # noqa: E402
 from wavelets_amd import _lib as L            # noqa: E402
 from wavelets_amd import batch as B           # noqa: E402
+from wavelets_amd import utils as U           # noqa: E402
 
 SHAPES = [(16, 512), (16, 1024), (8, 2048)]
 PSFS = [(9, 9), (25, 25)]
+FFT_PSFS = {512: (33, 33), 1024: (65, 65), 2048: (129, 129)}
 ITERATIONS, COEFFICIENTS = 10, (5, 2, 1)
 
 
@@ -71,25 +77,39 @@ def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     samples = max(20, int(args[0])) if args else 20
     corr_only = "--correlation-only" in sys.argv
+    fft = "--fft" in sys.argv
     ctx = L.default_context()
     tiling = "row-skewed tap loop" if os.environ.get("WT_BATCH_F2D_SKEW") else "per-image tap loop"
     for N, side in SHAPES:
         fr = frames(N, side)
-        for kh, kw in PSFS:
+        for kh, kw in ([FFT_PSFS[side]] if fft else PSFS):
             psf = make_psf(kh, kw)
             level = len(COEFFICIENTS)
-            assert B.rl_eligible(fr, psf, level), "not a batch case"
+            if fft:
+                assert B.rl_fft_eligible(fr, psf, level) and not B.rl_eligible(fr, psf, level, fft=True), "not a batched FFT case"
+            else:
+                assert B.rl_eligible(fr, psf, level), "not a batch case"
             rec = {"shape": [N, side, side], "psf": [kh, kw], "iterations": ITERATIONS, "denoise_coefficients": list(COEFFICIENTS),
                    "batched_tiling": tiling}
+            if fft:
+                rec["batched_tiling"] = "fft"
             # ---- one batched correlation against N per-frame ones (device events)
-            S, D = L.PLANE_SCRATCH(7), L.PLANE_SCRATCH(8)
+            S, D, K = L.PLANE_SCRATCH(7), L.PLANE_SCRATCH(8), L.PLANE_SCRATCH(10)
             bp = L.BatchPlan(ctx, N, side, side, L.B3SPLINE, level)
             bp.upload(S, fr)
-            bp.set_psf(0, psf)
+            kimg = U._rl_fft_kernel_image(psf, side, side) if fft else None
+            if fft:
+                bp.upload(K, kimg[None])
+                bp.fft_spectrum(K)
+            else:
+                bp.set_psf(0, psf)
             plans = []
             for f in range(N):
                 p = L.Plan(ctx, side, side, L.B3SPLINE, level)
                 p.upload(S, fr[f])
+                if fft:
+                    p.upload(K, kimg)
+                    p.fft_spectrum(K)
                 plans.append(p)
 
             def device(fn):
@@ -98,11 +118,17 @@ def main():
                 return ctx.timer_stop()
 
             def batched():
-                bp.filter2d(N, S, D, 0)
+                if fft:
+                    bp.fft_apply(N, S, D, False)
+                else:
+                    bp.filter2d(N, S, D, 0)
 
             def loop():
                 for p in plans:
-                    p.filter2d(S, D, psf)
+                    if fft:
+                        p.fft_apply(S, D, False)
+                    else:
+                        p.filter2d(S, D, psf)
 
             tb, tl = alternate(batched, loop, samples, device)
             same = all(np.array_equal(bp.download(D, N)[f].view(np.uint32), plans[f].download(D).view(np.uint32)) for f in range(N))
@@ -111,12 +137,15 @@ def main():
             rec["device_correlation"] = {"batched": b, "loop_of_per_frame_calls": lp, "speedup": lp["median_ms"] / b["median_ms"],
                                          "speedup_range": [lp["min_ms"] / b["max_ms"], lp["max_ms"] / b["min_ms"]],
                                          "batched_tfma_per_s": gfma / b["median_ms"], "bit_identical": bool(same)}
+            if fft:      # (no tap count to rate: the six kernels move 8-byte complex elements; pixels per second instead)
+                del rec["device_correlation"]["batched_tfma_per_s"]
+                rec["device_correlation"]["batched_gpix_per_s"] = N * side * side / 1e6 / b["median_ms"]
             bp.close()
             for p in plans:
                 p.close()
             # ---- host to host
             if not corr_only:
-                kw_rl = dict(iterations=ITERATIONS, denoise_coefficients=COEFFICIENTS)
+                kw_rl = dict(iterations=ITERATIONS, denoise_coefficients=COEFFICIENTS, fft=fft)
                 got = W.richardson_lucy_stack(fr, psf, **kw_rl)
                 exp = np.stack([W.richardson_lucy(f, psf, **kw_rl) for f in fr])
                 ts, tl = alternate(lambda: W.richardson_lucy_stack(fr, psf, **kw_rl),

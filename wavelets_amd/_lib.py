@@ -238,6 +238,9 @@ SIGNATURES = {
     "wt_batch_binary": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "wt_batch_mrs_update": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _c.c_int,
                                        _c.c_float]),
+    "wt_batch_fft_ok": (_c.c_int, [_i64, _i64, _c.POINTER(_c.c_int)]),
+    "wt_batch_fft_spectrum": (_c.c_int, [_vp, _c.c_int]),
+    "wt_batch_fft_apply": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     # batches of same-shape frames in float64 (wt_batch64)
     "wt_batch64_fused_ok": (_c.c_int, [_c.c_int, _i64, _i64, _c.c_int, _c.POINTER(_c.c_int)]),
     "wt_batch64_create": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_vp)]),
@@ -1024,6 +1027,14 @@ def batch_psf_ok(kh, kw):
     return bool(ok.value)
 
 
+def batch_fft_ok(H, W):
+    """True when a batch of H x W frames takes the circular products through the FFT (host logic, wt_batch_fft_ok):
+    fft_supported's rule on the frame shape - sides 2 .. 8192 without a prime factor above 5"""
+    ok = _c.c_int(0)
+    check(load().wt_batch_fft_ok(int(H), int(W), _c.byref(ok)))
+    return bool(ok.value)
+
+
 class BatchPlan:
     """Device planes of up to `n` frames of one H x W shape (wt_batch).  Operations take the number of
     active frames `nf` (frames 0 .. nf-1); upload / download move a C-contiguous (nf, H, W) block."""
@@ -1193,6 +1204,15 @@ class BatchPlan:
         """Plan.mrs_update per frame, scalar noise: taus[f] (0.0: significance one)"""
         t = self._per_frame(taus, nf, _c.c_double, "mrs_update taus")
         check(load().wt_batch_mrs_update(self._h, nf, plane, mrs_plane, t, int(soft), int(persistent), float(inv_pow)))
+
+    # -- richardson_lucy(fft=True), large PSFs (wt_batch_fft_spectrum / wt_batch_fft_apply)
+    def fft_spectrum(self, src):
+        """kernel spectrum of the batch <- FFT2 of FRAME 0 of plane src, once per call of the stack function"""
+        check(load().wt_batch_fft_spectrum(self._h, src))
+
+    def fft_apply(self, nf, src, dst, conj=False):
+        """Plan.fft_apply per frame with the batch's one kernel spectrum: six launches for frames 0 .. nf-1"""
+        check(load().wt_batch_fft_apply(self._h, nf, src, dst, int(conj)))
 
 
 def batch64_fused_ok(family, H, W, level):

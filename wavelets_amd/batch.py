@@ -30,11 +30,11 @@ from ._lib import PLANE_INPUT, PLANE_OUT, PLANE_NONE, PLANE_SCRATCH, FLAG_FUSED
 from .wavelets import (AtrousTransform, B3spline, _family_of, _needs_generic, _interleave_split, _tau_row, _map_tau_row,
                        _noise_from_median, _sigma_bilateral_list, _result_dtype, _NOISE_PLANE)
 from . import utils as _utils
-from .utils import (richardson_lucy, _rl_check_fft_width, _rl_direct_operands)
+from .utils import (richardson_lucy, _rl_check_fft_width, _rl_direct_operands, _rl_uses_fft, _rl_fft_kernel_image)
 from .utils import (denoise, wow, enhance, _enhance_lists, _GAMMA_PLANE, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments,
                     _wow_factor, _gamma_range, _wow_sigma_bilateral)
 
-__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'enhance_stack', 'richardson_lucy_stack', 'rl_eligible', 'batch_eligible', 'batch64_eligible',
+__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'enhance_stack', 'richardson_lucy_stack', 'rl_eligible', 'rl_fft_eligible', 'batch_eligible', 'batch64_eligible',
            'wow_eligible', 'wow64_eligible', 'bilateral_eligible', 'bilateral64_eligible', 'enhance_eligible',
            'noise_map_eligible']
 
@@ -857,6 +857,21 @@ def _rl_extra_planes(level):
     return level + 4
 
 
+# ... and of the FFT route: the two complex work arrays of wt_batch_fft_apply on top, 8 * H * W bytes per frame each -
+# at most two real planes of 4 * H * P bytes (P >= W), four in all (the one spectrum and the twiddles are not per frame)
+def _rl_fft_extra_planes(level):
+    return _rl_extra_planes(level) + 4
+
+
+def _rl_frames_eligible(frames, level, uniform_init):
+    """the clauses rl_eligible and rl_fft_eligible share: level, uniform_init, native float32 (N, H, W) frames"""
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level not in BATCH_LEVELS:
+        return False
+    if uniform_init:
+        return False
+    return isinstance(frames, np.ndarray) and _engine_eligible(frames, B3spline, None, [None] * len(frames))
+
+
 def rl_eligible(frames, psf, level, uniform_init=False, fft=False):
     """True when the batched engine computes richardson_lucy over this stack (host logic): native float32 frames in
     an (N, H, W) array (_engine_eligible), level = len(denoise_coefficients) with an all-fused schedule (2..8), no
@@ -864,12 +879,9 @@ def rl_eligible(frames, psf, level, uniform_init=False, fft=False):
     one-row PSF adds a zero row) the per-frame call applies in a single launch without bands (_lib.batch_psf_ok:
     at most 4096 taps in rows of at most 512, an LDS tile of at most 96 KB).  With fft=True also
     kh * kw < utils._FFT_MIN_TAPS, kh <= H and kw <= W: the per-frame call then takes the direct periodic form (no
-    FFT, and an extended frame is never worth it below that many taps).  Everything else runs the per-frame loop."""
-    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level not in BATCH_LEVELS:
-        return False
-    if uniform_init:
-        return False
-    if not isinstance(frames, np.ndarray) or not _engine_eligible(frames, B3spline, None, [None] * len(frames)):
+    FFT, and an extended frame is never worth it below that many taps).  Everything else runs the per-frame loop
+    (large PSFs with fft=True: rl_fft_eligible, the batched FFT products)."""
+    if not _rl_frames_eligible(frames, level, uniform_init):
         return False
     psf = np.asarray(psf)
     if psf.ndim != 2 or psf.dtype.kind not in "biuf" or psf.size == 0:
@@ -882,6 +894,25 @@ def rl_eligible(frames, psf, level, uniform_init=False, fft=False):
     return _lib.batch_psf_ok(*fwd_k.shape) and _lib.batch_psf_ok(*bwd_k.shape)
 
 
+def rl_fft_eligible(frames, psf, level, uniform_init=False):
+    """True when the batched engine computes richardson_lucy(fft=True) over this stack through the batched FFT
+    products (host logic; BatchPlan.fft_spectrum / fft_apply): rl_eligible's clauses on frames, level and uniform_init,
+    and a 2-D numeric PSF the per-frame call hands to the engine's FFT on the image itself (utils._rl_uses_fft, the
+    per-frame call's own rule): kh * kw >= utils._FFT_MIN_TAPS (read when called), kh <= H, kw <= W, sides the FFT
+    takes (_lib.batch_fft_ok: 2 .. 8192, no prime factor above 5), no forced extended frame - and an even width, the
+    only one fft=True is defined for.  Sides with a larger prime factor (the periodically extended frame), float64 and
+    integer stacks, per-frame PSFs and uniform_init keep the per-frame loop."""
+    if not _rl_frames_eligible(frames, level, uniform_init):
+        return False
+    psf = np.asarray(psf)
+    if psf.ndim != 2 or psf.dtype.kind not in "biuf" or psf.size == 0:
+        return False
+    H, W = frames.shape[1:]
+    if W % 2:
+        return False
+    return _rl_uses_fft(True, H, W, psf.shape[0], psf.shape[1], sides_ok=_lib.batch_fft_ok)
+
+
 def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2, 1), threshold_type='soft',
                           uniform_init=False, persistent_mrs=True, fft=False, out=None):
     """(N, H, W): utils.richardson_lucy of every frame with the one PSF `psf` (ref utils.py:222-290), batched -
@@ -892,13 +923,18 @@ def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2
     thresholded sum as the initial estimate; then per iteration the PSF correlation of all frames in one launch
     (the two operands lie in the batch: no stream drain, no PSF copy), the residual, its transform, one support
     update per scale with each frame's threshold, the plane sum, the ratio, the second correlation and the product
-    - nothing returns to the host until the chunk's estimates.  Everything else runs the per-frame loop."""
+    - nothing returns to the host until the chunk's estimates.  fft=True with a PSF of utils._FFT_MIN_TAPS taps or
+    more (rl_fft_eligible stacks): the same chunk loop with the two products through the batched FFT - the spectrum
+    of the periodically placed PSF once per call, then six launches per product for all frames of a chunk.
+    Everything else runs the per-frame loop."""
     fr = _as_frames(frames)
     if np.ndim(psf) != 2:
         raise ValueError("psf must be 2-D")
     _rl_check_fft_width(fft, fr[0].shape[1])
     level = len(denoise_coefficients)
-    if not rl_eligible(fr, psf, level, uniform_init, fft):
+    direct = rl_eligible(fr, psf, level, uniform_init, fft)
+    by_fft = not direct and bool(fft) and rl_fft_eligible(fr, psf, level, uniform_init)
+    if not direct and not by_fft:
         return _hand_over(np.stack([richardson_lucy(f, psf, iterations=iterations, denoise_coefficients=denoise_coefficients,
                                                     threshold_type=threshold_type, uniform_init=uniform_init,
                                                     persistent_mrs=persistent_mrs, fft=fft) for f in fr]), out)
@@ -910,14 +946,20 @@ def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2
     sigma_e = sf.sigma_e()
     DATA, PSI, PHI, RES, CONV = (PLANE_SCRATCH(i) for i in (6, 7, 8, 9, 10))     # (the per-frame call's plane ids)
     MRS = [PLANE_SCRATCH(16 + s) for s in range(level)]
-    (fwd_k, fwd), (bwd_k, bwd) = _rl_direct_operands(np.ascontiguousarray(psf, dtype=np.float32), H, fft)
+    psf32 = np.ascontiguousarray(psf, dtype=np.float32)
+    if direct:
+        (fwd_k, fwd), (bwd_k, bwd) = _rl_direct_operands(psf32, H, fft)
     # Coefficients._denoise_sum(list(denoise_coefficients)): the (scale, sigma, weight) entries of the initial estimate
     entries = list(zip(range(level + 1), denoise_coefficients, (1,) * level))
-    chunks = _lib.batch_chunks(N, H, W, level, extra_planes=_rl_extra_planes(level))
+    chunks = _lib.batch_chunks(N, H, W, level, extra_planes=(_rl_extra_planes if direct else _rl_fft_extra_planes)(level))
     bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, _family_of(sf), level)
     try:
-        bp.set_psf(0, fwd_k)
-        bp.set_psf(1, bwd_k)
+        if direct:
+            bp.set_psf(0, fwd_k)
+            bp.set_psf(1, bwd_k)
+        else:                                                                    # ref:246-251, once for every chunk
+            bp.upload(CONV, _rl_fft_kernel_image(psf32, H, W)[None])
+            bp.fft_spectrum(CONV)
         for f0, nf in chunks:
             bp.upload(DATA, fr[f0:f0 + nf])
             bp.decompose(nf, DATA, level, FLAG_FUSED)                            # ref:230
@@ -932,14 +974,20 @@ def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2
             scale_taus = [[_tau_row([(s, c, None)], n, sigma_e, soft)[0] for n in noises]
                           for s, c in enumerate(denoise_coefficients)]
             for iteration in range(iterations):                                  # ref:252
-                bp.filter2d(nf, PSI, PHI, 0, **fwd)                              # ref:254-257
+                if direct:
+                    bp.filter2d(nf, PSI, PHI, 0, **fwd)                          # ref:254-257
+                else:
+                    bp.fft_apply(nf, PSI, PHI, False)                            # ref:254
                 bp.binary(nf, "sub", DATA, PHI, RES)                             # ref:259
                 bp.decompose(nf, RES, level, FLAG_FUSED)                         # ref:261
                 for s in range(level):                                           # ref:263-276
                     bp.mrs_update(nf, s, MRS[s], scale_taus[s], soft, persistent_mrs, 1.0 / (iteration + 1))
                 bp.plane_sum(nf, 0, level + 1, RES)                              # ref:278
                 bp.binary(nf, "add_div", RES, PHI, RES)                          # ref:280-281
-                bp.filter2d(nf, RES, CONV, 1, **bwd)                             # ref:284-286
+                if direct:
+                    bp.filter2d(nf, RES, CONV, 1, **bwd)                         # ref:284-286
+                else:
+                    bp.fft_apply(nf, RES, CONV, True)                            # ref:284
                 bp.binary(nf, "mul", PSI, CONV, PSI)                             # ref:288
             bp.download(PSI, nf, out=out[f0:f0 + nf])
     finally:

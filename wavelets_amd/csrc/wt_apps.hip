@@ -544,6 +544,17 @@ extern "C" int wt_fft_apply(wt_plan *p, int src, int dst, int conj)
     return wt_fft_apply_t<float>(p->ctx, p->fft, s, d, p->g.P, conj);
 }
 
+// the same float kernels for the frames of a wt_batch (wt_batch_fft_spectrum / wt_batch_fft_apply, wt_batch.hip)
+int wt_fft32_prepare(wt_ctx *c, WtFftState &f, int H, int W, std::vector<void *> &owner, int nframes)
+{
+    return wt_fft_prepare<float>(c, f, H, W, owner, nframes);
+}
+int wt_fft32_spectrum(wt_ctx *c, WtFftState &f, const float *src, int P) { return wt_fft_set_spectrum<float>(c, f, src, P); }
+int wt_fft32_apply(wt_ctx *c, WtFftState &f, const float *src, float *dst, int P, int conj, int nf, int64_t fstride)
+{
+    return wt_fft_apply_t<float>(c, f, src, dst, P, conj, nf, fstride);
+}
+
 extern "C" int wt_filter2d(wt_plan *p, int src, int dst, const float *kernel, int kh, int kw, int flags)
 {
     WtGuard guard_(ctx_of(p));

@@ -15,7 +15,9 @@
 // sum run once over the stack, each frame with its own parameters and the bits of the per-frame call.
 // richardson_lucy (watroo/utils.py:222-290) runs on a batch as well: the PSF correlation of all frames is one launch
 // (wt_batch_filter2d_kernel, the frame as grid z, the two operands resident in the batch), the binary ops run once
-// over the stack, the support update takes the frame's threshold from a device table.
+// over the stack, the support update takes the frame's threshold from a device table.  With fft=True and a large PSF
+// the two products of an iteration are wt_fft.h's six launches over all frames against one kernel spectrum
+// (wt_batch_fft_spectrum / wt_batch_fft_apply).
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -59,6 +61,10 @@ struct wt_batch {
     float *d_psf[2] = {nullptr, nullptr};
     size_t psf_cap[2] = {0, 0};
     int psf_kh[2] = {0, 0}, psf_kw[2] = {0, 0};
+    // richardson_lucy(fft=True): two complex work arrays of n frames, ONE kernel spectrum and the twiddle tables
+    // (wt_fft.h), allocated by the first wt_batch_fft_spectrum
+    WtFftState fft;
+    std::vector<void *> fft_allocs;
     // per-frame parameter pairs of one launch ({tau, factor}, {gmin, gmax}): a ring of table slots [n][2], pinned
     // staging + device copy; a slot is refilled only after the copy that last read it has completed (its event)
     static constexpr int kTabSlots = 16;
@@ -616,6 +622,7 @@ extern "C" int wt_batch_destroy(wt_batch *b)
     for (float *q : b->mrs) f(q);
     f(b->d_psf[0]);
     f(b->d_psf[1]);
+    for (void *q : b->fft_allocs) f(q);
     f(b->d_ptab);
     f(b->d_red);
     if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) bad = 1;
@@ -1231,4 +1238,43 @@ extern "C" int wt_batch_mrs_update(wt_batch *b, int nf, int plane, int mrs_plane
                        inv_pow);
     WT_HIP(hipGetLastError());
     return 0;
+}
+
+// ---- the circular products of richardson_lucy(fft=True) through the FFT (wt_fft.h; watroo/utils.py:245-254, 284)
+// host logic: *ok = 1 when a batch of H x W frames takes them - wt_fft_supported's rule on the frame shape
+extern "C" int wt_batch_fft_ok(int64_t H, int64_t W, int *ok)
+{
+    if (!ok) WT_FAIL("wt_batch_fft_ok: null pointer");
+    return wt_fft_supported(H, W, ok);
+}
+
+// The kernel spectrum of the batch <- FFT2 of FRAME 0 of plane `src` (fft_psf of watroo/utils.py:246-251: the caller
+// uploads the periodically placed PSF there), once per call of the stack function: every chunk multiplies by it.
+extern "C" int wt_batch_fft_spectrum(wt_batch *b, int src)
+{
+    if (!b) WT_FAIL("wt_batch_fft_spectrum: null batch");
+    WtGuard guard_(b->ctx);
+    const Geo &g = b->geo.g;
+    int ok = 0;
+    WT_TRY(wt_fft_supported(g.H, g.W, &ok));
+    if (!ok) WT_FAIL("wt_batch_fft_spectrum: a side of the %d x %d frames has a prime factor above 5 (or lies outside 2 .. 8192)", g.H, g.W);
+    float *s = nullptr;
+    WT_TRY(bplane(b, src, &s));
+    b->fft.have_spec = false;
+    WT_TRY(wt_fft32_prepare(b->ctx, b->fft, g.H, g.W, b->fft_allocs, b->n));
+    return wt_fft32_spectrum(b->ctx, b->fft, s, g.P);
+}
+
+// wt_fft_apply per frame (watroo/utils.py:254: irfft2(rfft2(psi) * fft_psf); conj, utils.py:284: * conj(fft_psf)) with
+// the batch's one kernel spectrum: six launches for all active frames, no stream drain, no host round trip
+extern "C" int wt_batch_fft_apply(wt_batch *b, int nf, int src, int dst, int conj)
+{
+    WT_TRY(check_frames(b, nf, "wt_batch_fft_apply"));
+    WtGuard guard_(b->ctx);
+    if (src == dst) WT_FAIL("wt_batch_fft_apply: src and dst must differ");
+    float *s = nullptr, *d = nullptr;
+    WT_TRY(bplane(b, src, &s));
+    WT_TRY(bplane(b, dst, &d));
+    if (!b->fft.have_spec) WT_FAIL("wt_batch_fft_apply: the batch has no kernel spectrum (wt_batch_fft_spectrum first)");
+    return wt_fft32_apply(b->ctx, b->fft, s, d, b->geo.g.P, conj, nf, b->fstride);
 }

@@ -10,6 +10,9 @@
 // kernels over 8 (float) or 16 (double) bytes per pixel against a direct form that is compute-bound by
 // three orders of magnitude more work; simplicity wins).  Twiddles exp(-2 pi i k / n) come from a table
 // computed in double on the host.  Templated on the element type: wt_plan (float) and wt_plan64 (double).
+// Frames: every kernel takes the frame as a grid dimension (rows: y, transpose: z) and a frame stride per array, so
+// the products of a whole wt_batch chunk are the same six launches against ONE kernel spectrum (wt_batch_fft_apply);
+// a plan is the one-frame case of the same kernels, and a frame of a batch has the bits of wt_fft_apply on a plan.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,24 +34,27 @@ __device__ __forceinline__ double2 wt_cmake(double x, double y) { return make_do
 #define WT_FFT_MUL 4          // multiply the loaded element by mul[...] ...
 #define WT_FFT_MUL_CONJ 8     // ... or by its conjugate
 
-// One FFT of length n per workgroup (row `blockIdx.x`), radix-2 decimation in time in LDS: the row is
-// loaded in bit-reversed order, log2(n) butterfly stages with one barrier each, then stored.  INV: the
-// conjugate twiddles (the caller folds the 1 / n factors into `scale`).
+// One FFT of length n per workgroup (row `blockIdx.x` of frame `blockIdx.y`), radix-2 decimation in time in LDS: the
+// row is loaded in bit-reversed order, log2(n) butterfly stages with one barrier each, then stored.  INV: the
+// conjugate twiddles (the caller folds the 1 / n factors into `scale`).  Frames lie in_fs / out_fs ELEMENTS of the
+// array's own type apart; `mul` is one spectrum for all frames, indexed by the row within the frame.
 template <typename T, bool INV>
 __global__ __launch_bounds__(512) void wt_fft_rows_kernel(const void *in, void *out, int n, int log2n, int in_pitch, int out_pitch,
-                                                          const typename WtCx<T>::C *tw, const typename WtCx<T>::C *mul, int flags, T scale)
+                                                          int64_t in_fs, int64_t out_fs, const typename WtCx<T>::C *tw,
+                                                          const typename WtCx<T>::C *mul, int flags, T scale)
 {
     typedef typename WtCx<T>::C C;
     extern __shared__ unsigned char wt_fft_lds[];
     C *s = reinterpret_cast<C *>(wt_fft_lds);
     const int row = blockIdx.x, nt = blockDim.x;
+    const int64_t in0 = (int64_t)blockIdx.y * in_fs + (int64_t)row * in_pitch, out0 = (int64_t)blockIdx.y * out_fs + (int64_t)row * out_pitch;
     for (int i = threadIdx.x; i < n; i += nt) {
         C v;
         if (flags & WT_FFT_IN_REAL) {
-            v.x = reinterpret_cast<const T *>(in)[(int64_t)row * in_pitch + i];
+            v.x = reinterpret_cast<const T *>(in)[in0 + i];
             v.y = (T)0;
         } else {
-            v = reinterpret_cast<const C *>(in)[(int64_t)row * in_pitch + i];
+            v = reinterpret_cast<const C *>(in)[in0 + i];
         }
         if (flags & (WT_FFT_MUL | WT_FFT_MUL_CONJ)) {
             C m = mul[(int64_t)row * n + i];
@@ -72,8 +78,8 @@ __global__ __launch_bounds__(512) void wt_fft_rows_kernel(const void *in, void *
     }
     for (int i = threadIdx.x; i < n; i += nt) {
         const C v = s[i];
-        if (flags & WT_FFT_OUT_REAL) reinterpret_cast<T *>(out)[(int64_t)row * out_pitch + i] = v.x * scale;
-        else reinterpret_cast<C *>(out)[(int64_t)row * out_pitch + i] = wt_cmake(v.x * scale, v.y * scale);
+        if (flags & WT_FFT_OUT_REAL) reinterpret_cast<T *>(out)[out0 + i] = v.x * scale;
+        else reinterpret_cast<C *>(out)[out0 + i] = wt_cmake(v.x * scale, v.y * scale);
     }
 }
 
@@ -127,19 +133,21 @@ __device__ __forceinline__ void wt_fft_butterfly(C *s, int base, int L, int k, i
 
 template <typename T, bool INV>
 __global__ __launch_bounds__(512) void wt_fft_rows_mixed_kernel(const void *in, void *out, int n, WtFftFactors fa, int in_pitch, int out_pitch,
-                                                                const typename WtCx<T>::C *tw, const typename WtCx<T>::C *mul, int flags, T scale)
+                                                                int64_t in_fs, int64_t out_fs, const typename WtCx<T>::C *tw,
+                                                                const typename WtCx<T>::C *mul, int flags, T scale)
 {
     typedef typename WtCx<T>::C C;
     extern __shared__ unsigned char wt_fft_lds[];
     C *s = reinterpret_cast<C *>(wt_fft_lds);
     const int row = blockIdx.x, nt = blockDim.x;
+    const int64_t in0 = (int64_t)blockIdx.y * in_fs + (int64_t)row * in_pitch, out0 = (int64_t)blockIdx.y * out_fs + (int64_t)row * out_pitch;
     for (int i = threadIdx.x; i < n; i += nt) {
         C v;
         if (flags & WT_FFT_IN_REAL) {
-            v.x = reinterpret_cast<const T *>(in)[(int64_t)row * in_pitch + i];
+            v.x = reinterpret_cast<const T *>(in)[in0 + i];
             v.y = (T)0;
         } else {
-            v = reinterpret_cast<const C *>(in)[(int64_t)row * in_pitch + i];
+            v = reinterpret_cast<const C *>(in)[in0 + i];
         }
         if (flags & (WT_FFT_MUL | WT_FFT_MUL_CONJ)) {
             C m = mul[(int64_t)row * n + i];
@@ -176,17 +184,20 @@ __global__ __launch_bounds__(512) void wt_fft_rows_mixed_kernel(const void *in, 
     }
     for (int i = threadIdx.x; i < n; i += nt) {
         const C v = s[i];
-        if (flags & WT_FFT_OUT_REAL) reinterpret_cast<T *>(out)[(int64_t)row * out_pitch + i] = v.x * scale;
-        else reinterpret_cast<C *>(out)[(int64_t)row * out_pitch + i] = wt_cmake(v.x * scale, v.y * scale);
+        if (flags & WT_FFT_OUT_REAL) reinterpret_cast<T *>(out)[out0 + i] = v.x * scale;
+        else reinterpret_cast<C *>(out)[out0 + i] = wt_cmake(v.x * scale, v.y * scale);
     }
 }
 
-// out[c][r] = in[r][c] for a rows x cols complex array (32 x 32 tiles through LDS, padded against bank conflicts)
+// out[c][r] = in[r][c] for a rows x cols complex array (32 x 32 tiles through LDS, padded against bank conflicts);
+// grid z = the frame, each its own rows * cols array: the tiles are clipped at the frame's edges
 template <typename T>
 __global__ __launch_bounds__(256) void wt_fft_transpose_kernel(const typename WtCx<T>::C *in, typename WtCx<T>::C *out, int rows, int cols)
 {
     typedef typename WtCx<T>::C C;
     __shared__ C tile[32][33];
+    in += (int64_t)blockIdx.z * rows * cols;
+    out += (int64_t)blockIdx.z * rows * cols;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8 threads
     const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
     for (int k = ty; k < 32; k += 8)
@@ -218,11 +229,12 @@ static inline bool wt_fft_size_ok(int H, int W)
 }
 static inline int wt_ilog2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
 
+// Buffers of the state, once: two work arrays of nframes * H * W complex elements, one H * W spectrum, two tables
 template <typename T>
-static int wt_fft_prepare(wt_ctx *c, WtFftState &f, int H, int W, std::vector<void *> &owner)
+static int wt_fft_prepare(wt_ctx *c, WtFftState &f, int H, int W, std::vector<void *> &owner, int nframes = 1)
 {
     typedef typename WtCx<T>::C C;
-    if (f.a && f.H == H && f.W == W) return 0;
+    if (f.a && f.H == H && f.W == W && f.nframes == nframes) return 0;
     if (f.a) WT_FAIL("wt_fft: the plan's geometry changed");
     if (!wt_fft_size_ok(H, W)) WT_FAIL("wt_fft: a side of the %d x %d image has a prime factor above 5 (or lies outside 2 .. %d)", H, W, WT_FFT_MAX_N);
     WT_HIP(hipSetDevice(c->device));
@@ -232,8 +244,8 @@ static int wt_fft_prepare(wt_ctx *c, WtFftState &f, int H, int W, std::vector<vo
         return 0;
     };
     const size_t nc = (size_t)H * W * sizeof(C);
-    WT_TRY(alloc(&f.a, nc));
-    WT_TRY(alloc(&f.b, nc));
+    WT_TRY(alloc(&f.a, nc * (size_t)nframes));
+    WT_TRY(alloc(&f.b, nc * (size_t)nframes));
     WT_TRY(alloc(&f.spec, nc));
     auto table = [&](void **p, int n) -> int {          // exp(-2 pi i k / n), k < n, in double on the host
         std::vector<C> t((size_t)n);
@@ -250,12 +262,14 @@ static int wt_fft_prepare(wt_ctx *c, WtFftState &f, int H, int W, std::vector<vo
     WT_TRY(table(&f.tw_h, H));
     f.H = H;
     f.W = W;
+    f.nframes = nframes;
     return 0;
 }
 
+// nf frames of nrows rows each, in_fs / out_fs elements apart (one plan: nf = 1)
 template <typename T, bool INV>
-static int wt_fft_rows(wt_ctx *c, const void *in, void *out, int nrows, int n, int in_pitch, int out_pitch, const void *tw, const void *mul,
-                       int flags, T scale)
+static int wt_fft_rows(wt_ctx *c, const void *in, void *out, int nf, int nrows, int n, int in_pitch, int out_pitch, int64_t in_fs, int64_t out_fs,
+                       const void *tw, const void *mul, int flags, T scale)
 {
     typedef typename WtCx<T>::C C;
     const size_t lds = (size_t)n * sizeof(C);
@@ -263,33 +277,35 @@ static int wt_fft_rows(wt_ctx *c, const void *in, void *out, int nrows, int n, i
     if ((n & (n - 1)) == 0) {                            // powers of two: the radix-2 kernel
         if (lds > 64 * 1024)
             WT_HIP(hipFuncSetAttribute((const void *)wt_fft_rows_kernel<T, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((wt_fft_rows_kernel<T, INV>), dim3(nrows), dim3(threads), lds, c->stream, in, out, n, wt_ilog2(n), in_pitch, out_pitch,
-                           (const C *)tw, (const C *)mul, flags, scale);
+        hipLaunchKernelGGL((wt_fft_rows_kernel<T, INV>), dim3(nrows, nf), dim3(threads), lds, c->stream, in, out, n, wt_ilog2(n), in_pitch, out_pitch,
+                           in_fs, out_fs, (const C *)tw, (const C *)mul, flags, scale);
     } else {
         WtFftFactors fa;
         if (!wt_fft_factor(n, fa)) WT_FAIL("wt_fft: length %d has a prime factor above 5", n);
         if (lds > 64 * 1024)
             WT_HIP(hipFuncSetAttribute((const void *)wt_fft_rows_mixed_kernel<T, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((wt_fft_rows_mixed_kernel<T, INV>), dim3(nrows), dim3(threads), lds, c->stream, in, out, n, fa, in_pitch, out_pitch,
-                           (const C *)tw, (const C *)mul, flags, scale);
+        hipLaunchKernelGGL((wt_fft_rows_mixed_kernel<T, INV>), dim3(nrows, nf), dim3(threads), lds, c->stream, in, out, n, fa, in_pitch, out_pitch,
+                           in_fs, out_fs, (const C *)tw, (const C *)mul, flags, scale);
     }
     WT_HIP(hipGetLastError());
     return 0;
 }
 
-// spectrum (transposed, W x H) of the real H x W plane `src` (pitch P) -> dstC
+// spectra (transposed, W x H each) of the nf real H x W frames of `src` (pitch P, fstride floats apart) -> dstC;
+// the work arrays a and b hold nf frames (dstC may be a)
 template <typename T>
-static int wt_fft_forward(wt_ctx *c, WtFftState &f, const T *src, int P, void *dstC)
+static int wt_fft_forward(wt_ctx *c, WtFftState &f, const T *src, int P, void *dstC, int nf = 1, int64_t fstride = 0)
 {
     typedef typename WtCx<T>::C C;
     const int H = f.H, W = f.W;
-    WT_TRY((wt_fft_rows<T, false>(c, src, f.a, H, W, P, W, f.tw_w, nullptr, WT_FFT_IN_REAL, (T)1)));
-    hipLaunchKernelGGL(wt_fft_transpose_kernel<T>, dim3((W + 31) / 32, (H + 31) / 32), dim3(256), 0, c->stream, (const C *)f.a, (C *)f.b, H, W);
+    const int64_t cs = (int64_t)H * W;
+    WT_TRY((wt_fft_rows<T, false>(c, src, f.a, nf, H, W, P, W, fstride, cs, f.tw_w, nullptr, WT_FFT_IN_REAL, (T)1)));
+    hipLaunchKernelGGL(wt_fft_transpose_kernel<T>, dim3((W + 31) / 32, (H + 31) / 32, nf), dim3(256), 0, c->stream, (const C *)f.a, (C *)f.b, H, W);
     WT_HIP(hipGetLastError());
-    return wt_fft_rows<T, false>(c, f.b, dstC, W, H, H, H, f.tw_h, nullptr, 0, (T)1);
+    return wt_fft_rows<T, false>(c, f.b, dstC, nf, W, H, H, H, cs, cs, f.tw_h, nullptr, 0, (T)1);
 }
 
-// The kernel spectrum of the plan <- FFT2 of the real plane `src` (the PSF placed periodically by the caller)
+// The kernel spectrum of the state <- FFT2 of the real plane `src` (the PSF placed periodically by the caller)
 template <typename T>
 static int wt_fft_set_spectrum(wt_ctx *c, WtFftState &f, const T *src, int P)
 {
@@ -299,18 +315,20 @@ static int wt_fft_set_spectrum(wt_ctx *c, WtFftState &f, const T *src, int P)
     return 0;
 }
 
-// dst = real(IFFT2(FFT2(src) * K))  (conj: * conj(K)), K the plan's kernel spectrum
+// dst = real(IFFT2(FFT2(src) * K))  (conj: * conj(K)), K the state's kernel spectrum, for nf frames fstride apart
 template <typename T>
-static int wt_fft_apply_t(wt_ctx *c, WtFftState &f, const T *src, T *dst, int P, int conj)
+static int wt_fft_apply_t(wt_ctx *c, WtFftState &f, const T *src, T *dst, int P, int conj, int nf = 1, int64_t fstride = 0)
 {
     typedef typename WtCx<T>::C C;
     if (!f.have_spec) WT_FAIL("wt_fft_apply: no kernel spectrum (wt_fft_spectrum first)");
+    if (nf < 1 || nf > f.nframes) WT_FAIL("wt_fft_apply: %d frames (work arrays of %d)", nf, f.nframes);
     const int H = f.H, W = f.W;
+    const int64_t cs = (int64_t)H * W;
     ProfScope ps(c, "wt_fft_kernels");
-    WT_TRY(wt_fft_forward<T>(c, f, src, P, f.a));                     // a: W x H spectrum of src  (uses a, b, then a)
-    // first inverse pass: rows of the transposed spectrum (length H), times the kernel spectrum
-    WT_TRY((wt_fft_rows<T, true>(c, f.a, f.b, W, H, H, H, f.tw_h, f.spec, conj ? WT_FFT_MUL_CONJ : WT_FFT_MUL, (T)1)));
-    hipLaunchKernelGGL(wt_fft_transpose_kernel<T>, dim3((H + 31) / 32, (W + 31) / 32), dim3(256), 0, c->stream, (const C *)f.b, (C *)f.a, W, H);
+    WT_TRY(wt_fft_forward<T>(c, f, src, P, f.a, nf, fstride));        // a: W x H spectra of src  (uses a, b, then a)
+    // first inverse pass: rows of the transposed spectra (length H), times the kernel spectrum (the row within the frame)
+    WT_TRY((wt_fft_rows<T, true>(c, f.a, f.b, nf, W, H, H, H, cs, cs, f.tw_h, f.spec, conj ? WT_FFT_MUL_CONJ : WT_FFT_MUL, (T)1)));
+    hipLaunchKernelGGL(wt_fft_transpose_kernel<T>, dim3((H + 31) / 32, (W + 31) / 32, nf), dim3(256), 0, c->stream, (const C *)f.b, (C *)f.a, W, H);
     WT_HIP(hipGetLastError());
-    return wt_fft_rows<T, true>(c, f.a, dst, H, W, W, P, f.tw_w, nullptr, WT_FFT_OUT_REAL, (T)(1.0 / ((double)H * (double)W)));
+    return wt_fft_rows<T, true>(c, f.a, dst, nf, H, W, W, P, cs, fstride, f.tw_w, nullptr, WT_FFT_OUT_REAL, (T)(1.0 / ((double)H * (double)W)));
 }

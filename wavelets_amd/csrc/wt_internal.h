@@ -143,9 +143,10 @@ struct wt_ctx {
 #define WT_MAX_SUM_PLANES 16      // planes one wt_plane_sum / wt_denoise_sum launch folds
 
 // Device state of the FFT path of one plan: twiddle tables of both lengths, two work arrays and the
-// kernel spectrum (stored TRANSPOSED, W x H, the layout the forward transform ends in).
+// kernel spectrum (stored TRANSPOSED, W x H, the layout the forward transform ends in).  A wt_batch holds one too:
+// its work arrays take `nframes` frames, the spectrum is one for all of them.
 struct WtFftState {
-    int H = 0, W = 0;
+    int H = 0, W = 0, nframes = 1;
     void *tw_w = nullptr, *tw_h = nullptr, *a = nullptr, *b = nullptr, *spec = nullptr;
     bool have_spec = false;
 };
@@ -235,6 +236,13 @@ struct WtSideScope {                                // RAII form (on = false: no
     WtSideScope &operator=(const WtSideScope &) = delete;
     bool ok() const { return rc == 0; }
 };
+// ------------------------------------------------------------------ FFT products of a frame stack (wt_apps.hip)
+// wt_fft.h's float instantiation for a wt_batch (wt_batch.hip): the kernels stay in the one unit that has them.
+// Buffers for `nframes` frames of H x W (owner gets what hipFree takes); the spectrum of one real plane; the product
+// of nf frames `fstride` floats apart.
+int wt_fft32_prepare(wt_ctx *c, WtFftState &f, int H, int W, std::vector<void *> &owner, int nframes);
+int wt_fft32_spectrum(wt_ctx *c, WtFftState &f, const float *src, int P);
+int wt_fft32_apply(wt_ctx *c, WtFftState &f, const float *src, float *dst, int P, int conj, int nf, int64_t fstride);
 bool wt_wow_overlap_enabled();
 int wt_scale_events(wt_ctx *c, std::vector<hipEvent_t> &ev, int n);   // at least n events in ev
 

@@ -548,6 +548,25 @@ def _rl_direct_operands(psf, H, fft):
             _periodic_operand(psf, kh // 2 + e, kw // 2))
 
 
+def _rl_uses_fft(fft, H, W, kh, kw, sides_ok=None):
+    """True when richardson_lucy(fft=...) on H x W images runs its two products through the engine's own FFT on the
+    image itself (wt_fft_apply): fft=True, a PSF of _FFT_MIN_TAPS taps or more (read at call time) that is no larger
+    than the image, sides the FFT takes (`sides_ok`: _lib.fft_supported; the stack route asks _lib.batch_fft_ok)
+    and no forced extended frame.  The one copy of the rule: richardson_lucy and batch.rl_fft_eligible call it."""
+    sides_ok = _lib.fft_supported if sides_ok is None else sides_ok
+    return bool(fft) and kh * kw >= _FFT_MIN_TAPS and kh <= H and kw <= W and bool(sides_ok(H, W)) and not _FFT_FORCE_EXTENDED
+
+
+def _rl_fft_kernel_image(psf, H, W):
+    """The PSF as the reference lays it out for rfft2 (ref:246-250): centred in a zero H x W image, then rolled by
+    (H // 2, W // 2) - its centre at the origin (one row above it for an odd H).  wt_fft_spectrum / wt_batch_fft_spectrum
+    transform it once per call."""
+    kh, kw = psf.shape
+    padded_psf = np.zeros((H, W), dtype=psf.dtype)
+    padded_psf[H // 2 - kh // 2:H // 2 - kh // 2 + kh, W // 2 - kw // 2:W // 2 - kw // 2 + kw] = psf     # ref:247-249
+    return np.roll(padded_psf, (H // 2, W // 2), axis=(0, 1))                                                # ref:250
+
+
 def richardson_lucy(data, psf,
                     iterations=10, denoise_coefficients=(5, 2, 1),
                     threshold_type='soft', uniform_init=False, persistent_mrs=True, fft=False):
@@ -600,7 +619,7 @@ def richardson_lucy(data, psf,
     # the direct periodic form, which costs kh * kw taps per pixel.  The periodic kernel image is built
     # as the reference builds it (ref:246-250) and transformed once.
     own_sides = _lib.fft_supported(img.shape[0], img.shape[1]) and not _FFT_FORCE_EXTENDED
-    use_fft = bool(fft) and kh * kw >= _FFT_MIN_TAPS and kh <= img.shape[0] and kw <= img.shape[1] and own_sides
+    use_fft = _rl_uses_fft(fft, img.shape[0], img.shape[1], kh, kw)
     ext = None
     if fft and not use_fft and kh <= img.shape[0] and kw <= img.shape[1] and not own_sides:
         # a side with a prime factor above 5: the same FFT on a periodically extended frame
@@ -613,10 +632,7 @@ def richardson_lucy(data, psf,
         fwd_k = bwd_k = None
         fwd = bwd = {}
     elif use_fft:
-        H, W = img.shape
-        padded_psf = np.zeros((H, W), dtype=ft)
-        padded_psf[H // 2 - kh // 2:H // 2 - kh // 2 + kh, W // 2 - kw // 2:W // 2 - kw // 2 + kw] = psf     # ref:247-249
-        plan.upload(CONV, np.roll(padded_psf, (H // 2, W // 2), axis=(0, 1)))                                    # ref:250
+        plan.upload(CONV, _rl_fft_kernel_image(psf, img.shape[0], img.shape[1]))                             # ref:246-250
         plan.fft_spectrum(CONV)
         fwd_k = bwd_k = None
         fwd = bwd = {}
