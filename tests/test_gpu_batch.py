@@ -233,3 +233,36 @@ def test_denoise_stack_zero_frame_and_pipelined_reference():
         per = list(noise) if isinstance(noise, np.ndarray) else [noise] * 2
         exp = np.stack([W.denoise(f, [5, 3, 2], noise=n) for f, n in zip(big, per)])
         assert np.array_equal(_bits(got), _bits(exp))
+
+
+@pytest.mark.parametrize("name", ["BatchPlan", "BatchPlan64"])
+def test_upload_download_round_trip_of_both_batches(name):
+    """3 frames of 5 x 7: the odd width pads the rows of both pitches (4 floats, 2 doubles), H >= 2 as the float64
+    batch needs.  What goes up comes back bit for bit: into a fresh block, into a cube[:, s] view, and after an upload
+    of one frame at f0 = 1; the float64 batch also widens int16 and '>f4' frames to frames.astype(np.float64)."""
+    from wavelets_amd import _lib as L
+    cls = getattr(L, name)
+    rng = np.random.default_rng(31)
+    fr = rng.standard_normal((3, 5, 7)).astype(cls.dtype)
+    bp = cls(L.default_context(), 3, 5, 7, L.B3SPLINE, 2)
+    try:
+        assert bp.pitch == 8 and bp.frame_stride >= 5 * 8
+        bp.upload(L.PLANE_INPUT, fr)
+        got = bp.download(L.PLANE_INPUT, 3)
+        assert got.dtype == cls.dtype and np.array_equal(got, fr)
+        cube = np.full((3, 4, 5, 7), -1, cls.dtype)
+        bp.download(L.PLANE_INPUT, 3, out=cube[:, 2])
+        assert np.array_equal(cube[:, 2], fr) and np.all(cube[:, [0, 1, 3]] == -1)
+        other = rng.standard_normal((1, 5, 7)).astype(cls.dtype)
+        bp.upload(L.PLANE_INPUT, other, f0=1)
+        want = fr.copy()
+        want[1] = other[0]
+        assert np.array_equal(bp.download(L.PLANE_INPUT, 3), want)
+        assert np.array_equal(bp.download(L.PLANE_INPUT, 2, f0=1), want[1:])
+        if cls is L.BatchPlan64:
+            for dt in (np.int16, ">f4"):
+                typed = (rng.standard_normal((3, 5, 7)) * 300).astype(dt)
+                bp.upload(L.PLANE_INPUT, typed)
+                assert np.array_equal(bp.download(L.PLANE_INPUT, 3), typed.astype(np.float64))
+    finally:
+        bp.close()

@@ -1035,25 +1035,31 @@ def batch_fft_ok(H, W):
     return bool(ok.value)
 
 
-class BatchPlan:
-    """Device planes of up to `n` frames of one H x W shape (wt_batch).  Operations take the number of
-    active frames `nf` (frames 0 .. nf-1); upload / download move a C-contiguous (nf, H, W) block."""
+class _BatchBase:
+    """What BatchPlan and BatchPlan64 share, written once: device planes of up to `n` frames of one H x W shape.
+    Operations take the number of active frames `nf` (frames 0 .. nf-1); upload / download move a C-contiguous
+    (nf, H, W) block.  A subclass names the library's entries (`_prefix`), the element type of its planes (`dtype`)
+    and that type in C (`_real`: the transfers, the medians, the per-frame factor and gamma tables; thresholds are
+    doubles in both)."""
 
-    dtype = np.float32
+    _prefix = dtype = _real = None
+
+    def _call(self, name, *args):
+        check(getattr(load(), self._prefix + name)(self._h, *args))
 
     def __init__(self, ctx, n, H, W, family, max_level):
         self._h = _vp()
         self.ctx = ctx
-        check(load().wt_batch_create(ctx._h, n, H, W, family, max_level, _c.byref(self._h)))
+        check(getattr(load(), self._prefix + "create")(ctx._h, n, H, W, family, max_level, _c.byref(self._h)))
         info = (_i64 * 7)()
-        check(load().wt_batch_info(self._h, info))
+        self._call("info", info)
         (self.n, self.H, self.W, self.pitch, self.frame_stride, self.max_level, self.family) = [int(v) for v in info]
         _live.add(self)
 
     def close(self):
         if self._h:
             h, self._h = self._h, _vp()
-            check(load().wt_batch_destroy(h))
+            check(getattr(load(), self._prefix + "destroy")(h))
 
     def __del__(self):
         try:
@@ -1061,125 +1067,147 @@ class BatchPlan:
         except Exception:
             pass
 
-    def upload(self, plane, frames, f0=0):
-        a = np.ascontiguousarray(frames, dtype=np.float32)
+    def _check_frames(self, a):
         if a.ndim != 3 or a.shape[1:] != (self.H, self.W):
             raise ValueError(f"frames of shape {a.shape[1:]} != batch frame shape {(self.H, self.W)}")
-        check(load().wt_batch_upload(self._h, plane, f0, a.shape[0], a.ctypes.data_as(_fp), 0))
+
+    def upload(self, plane, frames, f0=0):
+        a = np.ascontiguousarray(frames, dtype=self.dtype)
+        self._check_frames(a)
+        self._call("upload", plane, f0, a.shape[0], a.ctypes.data_as(_c.POINTER(self._real)), 0)
 
     def download(self, plane, nf, out=None, f0=0):
-        """(nf, H, W) float32; `out` may be any (nf, H, W) view whose frames are C-contiguous (e.g. cube[:, s] of
-        an (N, L, H, W) array): the frames land in place, page-locked result blocks by default (host_empty)"""
+        """(nf, H, W) of the batch's element type; `out` may be any (nf, H, W) view of that type whose frames are
+        C-contiguous (e.g. cube[:, s] of an (N, L, H, W) array): the frames land in place, page-locked result blocks
+        by default (host_empty)"""
+        item = np.dtype(self.dtype).itemsize
         if out is None:
-            out = host_empty((nf, self.H, self.W), self.ctx)
-        assert out.dtype == np.float32 and out.shape == (nf, self.H, self.W) and out.flags.writeable
-        assert out.strides[1:] == (self.W * 4, 4) and out.strides[0] % 4 == 0 and out.strides[0] >= self.H * self.W * 4
-        check(load().wt_batch_download(self._h, plane, f0, nf, out.ctypes.data_as(_fp), out.strides[0] // 4))
+            out = host_empty((nf, self.H, self.W), self.ctx, self.dtype)
+        assert out.dtype == self.dtype and out.shape == (nf, self.H, self.W) and out.flags.writeable
+        assert out.strides[1:] == (self.W * item, item) and out.strides[0] % item == 0 \
+            and out.strides[0] >= self.H * self.W * item
+        self._call("download", plane, f0, nf, out.ctypes.data_as(_c.POINTER(self._real)), out.strides[0] // item)
         return out
 
     def plane_ptr(self, plane):
-        """(device pointer of frame 0, frame stride in floats)"""
+        """(device pointer of frame 0, frame stride in elements)"""
         p, st = _vp(), _i64()
-        check(load().wt_batch_plane_ptr(self._h, plane, _c.byref(p), _c.byref(st)))
+        self._call("plane_ptr", plane, _c.byref(p), _c.byref(st))
         return p.value, int(st.value)
 
     def decompose(self, nf, src, level, flags=FLAG_FUSED):
-        check(load().wt_batch_decompose(self._h, nf, src, level, flags))
+        self._call("decompose", nf, src, level, flags)
 
     def decompose_bilateral(self, nf, src, level, sigma_b, bilateral_scaling=False, flags=0):
-        """Plan.decompose_bilateral for frames 0 .. nf-1: one launch of the batched march per scale"""
+        """Plan.decompose_bilateral / Plan64.decompose_bilateral for frames 0 .. nf-1: one launch of the batched
+        march per scale"""
         arr = (_c.c_double * max(level, 1))(*[float(v) for v in sigma_b[:level]])
-        check(load().wt_batch_decompose_bilateral(self._h, nf, src, level, arr, int(bilateral_scaling), flags))
+        self._call("decompose_bilateral", nf, src, level, arr, int(bilateral_scaling), flags)
 
     def decompose_sum(self, nf, src, level, dst=PLANE_OUT, flags=FLAG_FUSED):
-        check(load().wt_batch_decompose_sum(self._h, nf, src, level, dst, flags))
+        self._call("decompose_sum", nf, src, level, dst, flags)
 
     def decompose_pass(self, nf, cur, nxt, s0, ns, flags=FLAG_FUSED):
-        check(load().wt_batch_decompose_pass(self._h, nf, cur, nxt, s0, ns, flags))
+        self._call("decompose_pass", nf, cur, nxt, s0, ns, flags)
 
     def decompose_pass_sum(self, nf, cur, nxt, s0, ns, flags, sum_plane, first, last):
-        check(load().wt_batch_decompose_pass_sum(self._h, nf, cur, nxt, s0, ns, flags, sum_plane, int(first), int(last)))
+        self._call("decompose_pass_sum", nf, cur, nxt, s0, ns, flags, sum_plane, int(first), int(last))
 
     def abs_median(self, nf, plane):
-        """np.median(np.abs(frame)) of `plane` for frames 0 .. nf-1 (np.float32 each)"""
-        m = (_c.c_float * nf)()
-        check(load().wt_batch_abs_median(self._h, nf, plane, m))
-        return [np.float32(v) for v in m]
+        """np.median(np.abs(frame)) of `plane` for frames 0 .. nf-1, each in the batch's element type (np.float32 /
+        np.float64, as Plan.abs_median / Plan64.abs_median)"""
+        m = (self._real * nf)()
+        self._call("abs_median", nf, plane, m)
+        return [self.dtype(v) for v in m]
+
+    def _map_flags(self, has_map, nf):
+        """the arguments of the denoise_sum_map entry after the noise plane: none (`has_map` is the float64 batch's)"""
+        return ()
 
     def denoise_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT, noise_plane=PLANE_NONE,
                     has_map=None):
         """`taus`: one row of thresholds per active frame (all rows of one length n_den).  `noise_plane`: the plane
-        of per-pixel noise maps, one per active frame (ones for a frame with a scalar noise level; `has_map` is the
-        float64 batch's)"""
+        of per-pixel noise maps, one per active frame (ones for a frame with a scalar noise level).  `has_map`, read
+        by the float64 batch only: per active frame, whether it has a map (None: all) - a frame without keeps the
+        arithmetic of the call without a noise plane"""
         n = len(wgts)
         if len(taus) != nf or any(len(t) != n for t in taus):
             raise ValueError("denoise_sum: one row of len(wgts) thresholds per frame")
         ta = (_c.c_double * max(nf * n, 1))(*[float(t) for row in taus for t in row])
         wa = (_c.c_double * max(n, 1))(*[float(w) for w in wgts])
         if noise_plane != PLANE_NONE:
-            check(load().wt_batch_denoise_sum_map(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back), noise_plane))
+            self._call("denoise_sum_map", nf, count, dst, n, ta, wa, int(soft), int(write_back), noise_plane,
+                       *self._map_flags(has_map, nf))
             return
-        check(load().wt_batch_denoise_sum(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back)))
+        self._call("denoise_sum", nf, count, dst, n, ta, wa, int(soft), int(write_back))
 
     def enhance_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT):
         """denoise_sum with one row of weights per active frame as well (utils.enhance: a colour image's channels
         are frames with their own sigmas and weights); all rows of one length n_den >= 1"""
-        check(load().wt_batch_enhance_sum(self._h, nf, count, dst, *_enhance_rows(nf, taus, wgts), int(soft), int(write_back)))
+        self._call("enhance_sum", nf, count, dst, *_enhance_rows(nf, taus, wgts), int(soft), int(write_back))
 
     def anscombe(self, nf, src, dst, alpha=1.0, g=0.0, sigma=0.0, inverse=False):
-        check(load().wt_batch_anscombe(self._h, nf, src, dst, alpha, g, sigma, int(inverse)))
+        self._call("anscombe", nf, src, dst, alpha, g, sigma, int(inverse))
 
-    # -- wow (wt_batch_wow_*): per-frame parameters are sequences of nf values
+    def fill(self, nf, plane, value):
+        self._call("fill", nf, plane, value)
+
+    def replicate(self, nf, plane):
+        """frame 0 of `plane` -> frames 1 .. nf-1, on the device (a noise map shared by the frames)"""
+        self._call("replicate", nf, plane)
+
+    # -- wow (wow_update / wow_scale / reduce / gamma_blend / plane_sum): per-frame parameters are sequences of nf
+    # values, the factors and the gamma range in the batch's element type
     @staticmethod
     def _per_frame(values, nf, ctype, what):
         if len(values) != nf:
             raise ValueError(f"{what}: one value per active frame ({nf} frames, {len(values)} values)")
         return (ctype * nf)(*[float(v) for v in values])
 
-    def fill(self, nf, plane, value):
-        check(load().wt_batch_fill(self._h, nf, plane, value))
-
-    def replicate(self, nf, plane):
-        """frame 0 of `plane` -> frames 1 .. nf-1, on the device (a noise map shared by the frames)"""
-        check(load().wt_batch_replicate(self._h, nf, plane))
-
-    def fill_normal(self, nf, plane, seed, first_trial=0):
-        """frame f of `plane` <- Plan.fill_normal(plane, seed, first_trial + f), frames 0 .. nf-1 (rng.py: the layout)"""
-        check(load().wt_batch_fill_normal(self._h, nf, plane, _seed64(seed), _trial32(first_trial)))
-
     def wow_update(self, nf, plane, taus, soft, factors, gamma_plane=PLANE_NONE, noise_plane=PLANE_NONE):
-        """Plan.wow_update per frame without power plane: taus[f] (0.0: significance one), factors[f]; `noise_plane`:
-        the plane of per-pixel noise maps, one per active frame"""
+        """Plan.wow_update / Plan64.wow_update per frame without power plane: taus[f] (0.0: significance one),
+        factors[f]; `noise_plane`: the plane of per-pixel noise maps, one per active frame"""
         t = self._per_frame(taus, nf, _c.c_double, "wow_update taus")
-        f = self._per_frame(factors, nf, _c.c_float, "wow_update factors")
+        f = self._per_frame(factors, nf, self._real, "wow_update factors")
         if noise_plane != PLANE_NONE:
-            check(load().wt_batch_wow_update_map(self._h, nf, plane, t, int(soft), f, gamma_plane, noise_plane))
+            self._call("wow_update_map", nf, plane, t, int(soft), f, gamma_plane, noise_plane)
             return
-        check(load().wt_batch_wow_update(self._h, nf, plane, t, int(soft), f, gamma_plane))
+        self._call("wow_update", nf, plane, t, int(soft), f, gamma_plane)
 
     def wow_scale(self, nf, plane, s, taus, soft, factors, gamma_plane=PLANE_NONE, noise_plane=PLANE_NONE):
-        """Plan.wow_scale per frame: local power, significance, gamma sum and whitening, in place; `noise_plane`: the
-        plane of per-pixel noise maps, one per active frame"""
+        """Plan.wow_scale / Plan64.wow_scale per frame: local power, significance, gamma sum and whitening, in place;
+        `noise_plane`: the plane of per-pixel noise maps, one per active frame"""
         t = self._per_frame(taus, nf, _c.c_double, "wow_scale taus")
-        f = self._per_frame(factors, nf, _c.c_float, "wow_scale factors")
+        f = self._per_frame(factors, nf, self._real, "wow_scale factors")
         if noise_plane != PLANE_NONE:
-            check(load().wt_batch_wow_scale_map(self._h, nf, plane, s, t, int(soft), f, gamma_plane, noise_plane))
+            self._call("wow_scale_map", nf, plane, s, t, int(soft), f, gamma_plane, noise_plane)
             return
-        check(load().wt_batch_wow_scale(self._h, nf, plane, s, t, int(soft), f, gamma_plane))
+        self._call("wow_scale", nf, plane, s, t, int(soft), f, gamma_plane)
 
     def reduce(self, nf, plane):
-        """[(sum, sumsq, min, max)] of every active frame, fp64 (Plan.reduce's doubles)"""
+        """[(sum, sumsq, min, max)] of every active frame, fp64 (Plan.reduce's / Plan64.reduce's doubles)"""
         out = (_c.c_double * (4 * nf))()
-        check(load().wt_batch_reduce(self._h, nf, plane, out))
+        self._call("reduce", nf, plane, out)
         return [tuple(out[4 * f:4 * f + 4]) for f in range(nf)]
 
     def gamma_blend(self, nf, recon, gamma_plane, gmins, gmaxs, inv_gamma, h):
-        lo = self._per_frame(gmins, nf, _c.c_float, "gamma_blend gmins")
-        hi = self._per_frame(gmaxs, nf, _c.c_float, "gamma_blend gmaxs")
-        check(load().wt_batch_gamma_blend(self._h, nf, recon, gamma_plane, lo, hi, inv_gamma, h))
+        lo = self._per_frame(gmins, nf, self._real, "gamma_blend gmins")
+        hi = self._per_frame(gmaxs, nf, self._real, "gamma_blend gmaxs")
+        self._call("gamma_blend", nf, recon, gamma_plane, lo, hi, inv_gamma, h)
 
     def plane_sum(self, nf, first, count, dst=PLANE_OUT):
-        check(load().wt_batch_plane_sum(self._h, nf, first, count, dst))
+        self._call("plane_sum", nf, first, count, dst)
+
+
+class BatchPlan(_BatchBase):
+    """Device planes of up to `n` frames of one H x W shape (wt_batch): _BatchBase's operations in float32, and the
+    ones only the float32 batch has - the seeded normal fill and richardson_lucy's PSF and FFT products."""
+
+    _prefix, dtype, _real = "wt_batch_", np.float32, _c.c_float
+
+    def fill_normal(self, nf, plane, seed, first_trial=0):
+        """frame f of `plane` <- Plan.fill_normal(plane, seed, first_trial + f), frames 0 .. nf-1 (rng.py: the layout)"""
+        self._call("fill_normal", nf, plane, _seed64(seed), _trial32(first_trial))
 
     # -- richardson_lucy (wt_batch_set_psf / _filter2d / _binary / _mrs_update)
     def set_psf(self, slot, kernel):
@@ -1187,7 +1215,7 @@ class BatchPlan:
         k = np.ascontiguousarray(kernel, dtype=np.float32)
         if k.ndim != 2:
             raise ValueError("set_psf kernel must be 2-D")
-        check(load().wt_batch_set_psf(self._h, slot, k.ctypes.data_as(_fp), k.shape[0], k.shape[1]))
+        self._call("set_psf", slot, k.ctypes.data_as(_fp), k.shape[0], k.shape[1])
         self._psf_shape = getattr(self, "_psf_shape", {})
         self._psf_shape[slot] = k.shape
 
@@ -1195,24 +1223,24 @@ class BatchPlan:
         """Plan.filter2d per frame with the PSF of `slot`: one launch for frames 0 .. nf-1"""
         kh, kw = getattr(self, "_psf_shape", {}).get(slot, (1, 1))
         ay, ax = (kh // 2, kw // 2) if anchor is None else anchor
-        check(load().wt_batch_filter2d(self._h, nf, src, dst, slot, ay, ax, 3 if periodic else 0))
+        self._call("filter2d", nf, src, dst, slot, ay, ax, 3 if periodic else 0)
 
     def binary(self, nf, op, a, b, dst):
-        check(load().wt_batch_binary(self._h, nf, {"sub": 0, "add": 1, "mul": 2, "div": 3, "add_div": 4}[op], a, b, dst))
+        self._call("binary", nf, {"sub": 0, "add": 1, "mul": 2, "div": 3, "add_div": 4}[op], a, b, dst)
 
     def mrs_update(self, nf, plane, mrs_plane, taus, soft, persistent, inv_pow):
         """Plan.mrs_update per frame, scalar noise: taus[f] (0.0: significance one)"""
         t = self._per_frame(taus, nf, _c.c_double, "mrs_update taus")
-        check(load().wt_batch_mrs_update(self._h, nf, plane, mrs_plane, t, int(soft), int(persistent), float(inv_pow)))
+        self._call("mrs_update", nf, plane, mrs_plane, t, int(soft), int(persistent), float(inv_pow))
 
     # -- richardson_lucy(fft=True), large PSFs (wt_batch_fft_spectrum / wt_batch_fft_apply)
     def fft_spectrum(self, src):
         """kernel spectrum of the batch <- FFT2 of FRAME 0 of plane src, once per call of the stack function"""
-        check(load().wt_batch_fft_spectrum(self._h, src))
+        self._call("fft_spectrum", src)
 
     def fft_apply(self, nf, src, dst, conj=False):
         """Plan.fft_apply per frame with the batch's one kernel spectrum: six launches for frames 0 .. nf-1"""
-        check(load().wt_batch_fft_apply(self._h, nf, src, dst, int(conj)))
+        self._call("fft_apply", nf, src, dst, int(conj))
 
 
 def batch64_fused_ok(family, H, W, level):
@@ -1241,104 +1269,22 @@ def batch64_wow_ok(family, H, W, level):
     return bool(ok.value)
 
 
-class BatchPlan64:
-    """Double-precision planes of up to `n` frames of one H x W shape (wt_batch64): BatchPlan's operations for the
-    stacks the reference computes in float64.  upload / download move a C-contiguous (nf, H, W) block; integer
-    and big-endian frames cross as they are and are widened on the device (device_widens)."""
+class BatchPlan64(_BatchBase):
+    """Double-precision planes of up to `n` frames of one H x W shape (wt_batch64): _BatchBase's operations for the
+    stacks the reference computes in float64.  Integer and big-endian frames cross as they are and are widened on
+    the device (device_widens).  It has none of the operations that only the float32 batch has: no wt_batch64 entry
+    stands behind them."""
 
-    dtype = np.float64
-
-    def __init__(self, ctx, n, H, W, family, max_level):
-        self._h = _vp()
-        self.ctx = ctx
-        check(load().wt_batch64_create(ctx._h, n, H, W, family, max_level, _c.byref(self._h)))
-        info = (_i64 * 7)()
-        check(load().wt_batch64_info(self._h, info))
-        (self.n, self.H, self.W, self.pitch, self.frame_stride, self.max_level, self.family) = [int(v) for v in info]
-        _live.add(self)
-
-    def close(self):
-        if self._h:
-            h, self._h = self._h, _vp()
-            check(load().wt_batch64_destroy(h))
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _prefix, dtype, _real = "wt_batch64_", np.float64, _c.c_double
 
     def upload(self, plane, frames, f0=0):
         a = np.asarray(frames)
-        if a.ndim != 3 or a.shape[1:] != (self.H, self.W):
-            raise ValueError(f"frames of shape {a.shape[1:]} != batch frame shape {(self.H, self.W)}")
-        if a.dtype != np.float64 and device_widens(a.dtype):
-            a = np.ascontiguousarray(a)
-            code = _ELEM_CODES[a.dtype.str[1:]] | (16 if not a.dtype.isnative and a.itemsize > 1 else 0)
-            check(load().wt_batch64_upload_elems(self._h, plane, f0, a.shape[0], _vp(a.ctypes.data), code))
-            return
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        check(load().wt_batch64_upload(self._h, plane, f0, a.shape[0], a.ctypes.data_as(_dp), 0))
-
-    def download(self, plane, nf, out=None, f0=0):
-        """(nf, H, W) float64; `out` may be any (nf, H, W) float64 view whose frames are C-contiguous: the frames
-        land in place, page-locked result blocks by default (host_empty)"""
-        if out is None:
-            out = host_empty((nf, self.H, self.W), self.ctx, np.float64)
-        assert out.dtype == np.float64 and out.shape == (nf, self.H, self.W) and out.flags.writeable
-        assert out.strides[1:] == (self.W * 8, 8) and out.strides[0] % 8 == 0 and out.strides[0] >= self.H * self.W * 8
-        check(load().wt_batch64_download(self._h, plane, f0, nf, out.ctypes.data_as(_dp), out.strides[0] // 8))
-        return out
-
-    def plane_ptr(self, plane):
-        """(device pointer of frame 0, frame stride in doubles)"""
-        p, st = _vp(), _i64()
-        check(load().wt_batch64_plane_ptr(self._h, plane, _c.byref(p), _c.byref(st)))
-        return p.value, int(st.value)
-
-    def decompose(self, nf, src, level, flags=FLAG_FUSED):
-        check(load().wt_batch64_decompose(self._h, nf, src, level, flags))
-
-    def decompose_bilateral(self, nf, src, level, sigma_b, bilateral_scaling=False, flags=0):
-        """Plan64.decompose_bilateral for frames 0 .. nf-1: one launch of the batched float64 march per scale"""
-        arr = (_c.c_double * max(level, 1))(*[float(v) for v in sigma_b[:level]])
-        check(load().wt_batch64_decompose_bilateral(self._h, nf, src, level, arr, int(bilateral_scaling), flags))
-
-    def decompose_sum(self, nf, src, level, dst=PLANE_OUT, flags=FLAG_FUSED):
-        check(load().wt_batch64_decompose_sum(self._h, nf, src, level, dst, flags))
-
-    def decompose_pass(self, nf, cur, nxt, s0, ns, flags=FLAG_FUSED):
-        check(load().wt_batch64_decompose_pass(self._h, nf, cur, nxt, s0, ns, flags))
-
-    def decompose_pass_sum(self, nf, cur, nxt, s0, ns, flags, sum_plane, first, last):
-        check(load().wt_batch64_decompose_pass_sum(self._h, nf, cur, nxt, s0, ns, flags, sum_plane, int(first), int(last)))
-
-    def abs_median(self, nf, plane):
-        """np.median(np.abs(frame)) of `plane` for frames 0 .. nf-1 (np.float64 each, as Plan64.abs_median)"""
-        m = (_c.c_double * nf)()
-        check(load().wt_batch64_abs_median(self._h, nf, plane, m))
-        return [np.float64(v) for v in m]
-
-    def denoise_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT, noise_plane=PLANE_NONE,
-                    has_map=None):
-        """`taus`: one row of thresholds per active frame (all rows of one length n_den).  `noise_plane`: the plane
-        of per-pixel float64 noise maps; `has_map`: per active frame, whether it has one (None: all) - a frame
-        without keeps the arithmetic of the call without a noise plane"""
-        n = len(wgts)
-        if len(taus) != nf or any(len(t) != n for t in taus):
-            raise ValueError("denoise_sum: one row of len(wgts) thresholds per frame")
-        ta = (_c.c_double * max(nf * n, 1))(*[float(t) for row in taus for t in row])
-        wa = (_c.c_double * max(n, 1))(*[float(w) for w in wgts])
-        if noise_plane != PLANE_NONE:
-            hm = None if has_map is None else self._has_map(has_map, nf)
-            check(load().wt_batch64_denoise_sum_map(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back), noise_plane, hm))
-            return
-        check(load().wt_batch64_denoise_sum(self._h, nf, count, dst, n, ta, wa, int(soft), int(write_back)))
-
-    def enhance_sum(self, nf, count, taus, wgts, soft=True, write_back=False, dst=PLANE_OUT):
-        """denoise_sum with one row of weights per active frame as well (utils.enhance: a colour image's channels
-        are frames with their own sigmas and weights); all rows of one length n_den >= 1"""
-        check(load().wt_batch64_enhance_sum(self._h, nf, count, dst, *_enhance_rows(nf, taus, wgts), int(soft), int(write_back)))
+        if a.dtype == np.float64 or not device_widens(a.dtype):
+            return super().upload(plane, a, f0)
+        self._check_frames(a)
+        a = np.ascontiguousarray(a)
+        code = _ELEM_CODES[a.dtype.str[1:]] | (16 if not a.dtype.isnative and a.itemsize > 1 else 0)
+        self._call("upload_elems", plane, f0, a.shape[0], _vp(a.ctypes.data), code)
 
     @staticmethod
     def _has_map(has_map, nf):
@@ -1346,52 +1292,9 @@ class BatchPlan64:
             raise ValueError(f"denoise_sum has_map: one flag per active frame ({nf} frames, {len(has_map)} flags)")
         return (_c.c_int * nf)(*[int(bool(v)) for v in has_map])
 
-    def fill(self, nf, plane, value):
-        check(load().wt_batch64_fill(self._h, nf, plane, value))
-
-    def replicate(self, nf, plane):
-        """frame 0 of `plane` -> frames 1 .. nf-1, on the device (a noise map shared by the frames)"""
-        check(load().wt_batch64_replicate(self._h, nf, plane))
-
-    def anscombe(self, nf, src, dst, alpha=1.0, g=0.0, sigma=0.0, inverse=False):
-        check(load().wt_batch64_anscombe(self._h, nf, src, dst, alpha, g, sigma, int(inverse)))
-
-    # -- wow (wt_batch64_wow_*): BatchPlan's methods, the per-frame parameters as doubles
-    _per_frame = staticmethod(BatchPlan._per_frame)
-
-    def wow_update(self, nf, plane, taus, soft, factors, gamma_plane=PLANE_NONE, noise_plane=PLANE_NONE):
-        """Plan64.wow_update per frame without power plane: taus[f] (0.0: significance one), factors[f]; `noise_plane`:
-        the plane of per-pixel noise maps, one per active frame"""
-        t = self._per_frame(taus, nf, _c.c_double, "wow_update taus")
-        f = self._per_frame(factors, nf, _c.c_double, "wow_update factors")
-        if noise_plane != PLANE_NONE:
-            check(load().wt_batch64_wow_update_map(self._h, nf, plane, t, int(soft), f, gamma_plane, noise_plane))
-            return
-        check(load().wt_batch64_wow_update(self._h, nf, plane, t, int(soft), f, gamma_plane))
-
-    def wow_scale(self, nf, plane, s, taus, soft, factors, gamma_plane=PLANE_NONE, noise_plane=PLANE_NONE):
-        """Plan64.wow_scale per frame: local power, significance, gamma sum and whitening, in place; `noise_plane`: the
-        plane of per-pixel noise maps, one per active frame"""
-        t = self._per_frame(taus, nf, _c.c_double, "wow_scale taus")
-        f = self._per_frame(factors, nf, _c.c_double, "wow_scale factors")
-        if noise_plane != PLANE_NONE:
-            check(load().wt_batch64_wow_scale_map(self._h, nf, plane, s, t, int(soft), f, gamma_plane, noise_plane))
-            return
-        check(load().wt_batch64_wow_scale(self._h, nf, plane, s, t, int(soft), f, gamma_plane))
-
-    def reduce(self, nf, plane):
-        """[(sum, sumsq, min, max)] of every active frame (Plan64.reduce's doubles)"""
-        out = (_c.c_double * (4 * nf))()
-        check(load().wt_batch64_reduce(self._h, nf, plane, out))
-        return [tuple(out[4 * f:4 * f + 4]) for f in range(nf)]
-
-    def gamma_blend(self, nf, recon, gamma_plane, gmins, gmaxs, inv_gamma, h):
-        lo = self._per_frame(gmins, nf, _c.c_double, "gamma_blend gmins")
-        hi = self._per_frame(gmaxs, nf, _c.c_double, "gamma_blend gmaxs")
-        check(load().wt_batch64_gamma_blend(self._h, nf, recon, gamma_plane, lo, hi, inv_gamma, h))
-
-    def plane_sum(self, nf, first, count, dst=PLANE_OUT):
-        check(load().wt_batch64_plane_sum(self._h, nf, first, count, dst))
+    def _map_flags(self, has_map, nf):
+        """one int per active frame, or NULL: every frame has a map"""
+        return (None if has_map is None else self._has_map(has_map, nf),)
 
 
 _batch_cache = {}        # id(ctx) -> [BatchPlan / BatchPlan64], most recently used last (its own small cache: not the plan pool)

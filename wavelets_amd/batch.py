@@ -10,19 +10,26 @@ back in one host round trip, and the pointwise steps run once over the stack.
 
 bit for bit.  The sequence of operations per frame is the per-frame path's own (wavelets._interleave_split,
 _tau_row, _noise_from_median, _sigma_bilateral_list; utils._wow_lists, _wow_factor, _gamma_range,
-_wow_sigma_bilateral).  With bilateral= the transform is the batched bilateral march (one launch per scale for
-all frames, bilateral_eligible).  Stacks the reference
-computes in float64 (float64 frames; int16 .. int64 and big-endian frames, which it recasts) run transform_stack
-and denoise_stack on the float64 batch (wt_batch64, batch64_eligible), with bilateral= behind the batched float64
-march (bilateral64_eligible), and wow_stack on the same batch (wow64_eligible: the transform's scales beyond the fused
-passes and the fused update of every scale on the batched float64 per-scale stencil, one launch per scale for all
-frames; moments, medians and the gamma range of all frames in one host round trip each).  `noise` may hold per-pixel noise maps (ref wavelets.py:133-141) - one (H, W) ndarray
-shared by the frames, or one entry per frame, maps mixed with levels and None: they lie in one more plane of the batch,
-the noise plane (noise_map_eligible, _upload_noise_maps; a shared map crosses PCIe once and is replicated on the device),
-read by the map forms of the thresholded sum and of wow's updates (both batches); a frame with a level has
-ones there and keeps its map-free arithmetic.  Inputs the batched engines do not cover run the per-frame loop
-(batch_eligible / batch64_eligible / wow_eligible / wow64_eligible / bilateral_eligible / bilateral64_eligible say
-which)."""
+_wow_sigma_bilateral).  With bilateral= the transform is the batched bilateral march: one launch per scale for all
+frames (bilateral_eligible).
+
+Stacks the reference computes in float64 - float64 frames; int16 .. int64 and big-endian frames, which it recasts -
+run on the float64 batch (wt_batch64).  transform_stack and denoise_stack take it under batch64_eligible, and with
+bilateral= behind the batched float64 march under bilateral64_eligible.  wow_stack takes the same batch under
+wow64_eligible: the transform's scales beyond the fused passes and the fused update of every scale run on the batched
+float64 per-scale stencil, one launch per scale for all frames; the moments, the medians and the gamma range of all
+frames come back in one host round trip each.
+
+`noise` may hold per-pixel noise maps (ref wavelets.py:133-141): one (H, W) ndarray shared by the frames, or one entry
+per frame, maps mixed with levels and None.  The maps lie in one more plane of the batch, the noise plane
+(noise_map_eligible, _upload_noise_maps); a shared map crosses PCIe once and is replicated on the device.  The map
+forms of the thresholded sum and of wow's updates read it, on both batches; a frame with a level has ones there and
+keeps its map-free arithmetic.
+
+Inputs the batched engines do not cover run the per-frame loop; batch_eligible, batch64_eligible, wow_eligible,
+wow64_eligible, bilateral_eligible and bilateral64_eligible say which."""
+from contextlib import contextmanager
+
 import numpy as np
 
 from . import _lib
@@ -205,6 +212,14 @@ def _family_noise_eligible(scaling_function, bilateral, noise_per_frame):
     return noise_per_frame is not None and not any(n is not None and np.ndim(n) != 0 for n in noise_per_frame)
 
 
+def _float64_frames(frames):
+    """True for an (N, H, W) ndarray the reference computes in float64 that the device takes: native float64, or a
+    type of wavelets._RECAST that the device widens on upload (wavelets._result_dtype, _lib.device_widens)"""
+    if not isinstance(frames, np.ndarray) or frames.ndim != 3 or _result_dtype(frames) != np.float64:
+        return False
+    return frames.dtype == np.dtype(np.float64) or _lib.device_widens(frames.dtype)
+
+
 def batch64_eligible(frames, level, scaling_function=B3spline, bilateral=None, noise_per_frame=(), noise_maps=False):
     """True when the float64 batch (wt_batch64) computes this stack (host logic): an (N, H, W) ndarray the
     reference computes in float64 (wavelets._result_dtype: native float64, or a type of wavelets._RECAST that the
@@ -213,13 +228,9 @@ def batch64_eligible(frames, level, scaling_function=B3spline, bilateral=None, n
     is all fused passes (images, H >= 2, rows the fused passes take at 8 bytes per pixel: _lib.batch64_fused_ok,
     i.e. what wt64_plan_fused_ok answers for one frame).  noise_maps=True: per-pixel noise maps of the frames' shape
     are taken too.  Everything else keeps its route."""
-    if not isinstance(frames, np.ndarray) or frames.ndim != 3:
+    if not _float64_frames(frames):
         return False
     noise_per_frame = _maps_admitted(frames, noise_per_frame, noise_maps)
-    if _result_dtype(frames) != np.float64:
-        return False
-    if frames.dtype != np.dtype(np.float64) and not _lib.device_widens(frames.dtype):
-        return False
     if not _family_noise_eligible(scaling_function, bilateral, noise_per_frame):
         return False
     if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
@@ -241,11 +252,7 @@ def bilateral64_eligible(frames, level, scaling_function=B3spline, bilateral=Non
     noise_per_frame = _maps_admitted(frames, noise_per_frame, noise_maps)
     if not _bilateral_call_eligible(level, bilateral, noise_per_frame):
         return False
-    if not isinstance(frames, np.ndarray) or frames.ndim != 3:
-        return False
-    if _result_dtype(frames) != np.float64:
-        return False
-    if frames.dtype != np.dtype(np.float64) and not _lib.device_widens(frames.dtype):
+    if not _float64_frames(frames):
         return False
     if not _family_noise_eligible(scaling_function, None, noise_per_frame):
         return False
@@ -280,14 +287,10 @@ def wow64_eligible(frames, n_scales, scaling_function=B3spline, bilateral=None, 
     batched float64 march.  Everything else runs the per-frame loop."""
     if isinstance(n_scales, bool) or not isinstance(n_scales, (int, np.integer)) or n_scales not in WOW_LEVELS:
         return False
-    if not isinstance(frames, np.ndarray) or frames.ndim != 3:
+    if not _float64_frames(frames):
         return False
     noise_per_frame = _maps_admitted(frames, noise_per_frame, noise_maps)
     if noise_per_frame is not None and any(type(n) is np.ndarray for n in noise_per_frame):
-        return False
-    if _result_dtype(frames) != np.float64:
-        return False
-    if frames.dtype != np.dtype(np.float64) and not _lib.device_widens(frames.dtype):
         return False
     if not _family_noise_eligible(scaling_function, None, noise_per_frame):
         return False
@@ -304,9 +307,40 @@ def wow64_eligible(frames, n_scales, scaling_function=B3spline, bilateral=None, 
     return bilateral64_eligible(frames, int(n_scales), scaling_function, bilateral, noise_per_frame)
 
 
-def _chunks(frames, level):
-    N, H, W = frames.shape
-    return _lib.batch_chunks(N, H, W, level)
+def _plan_chunks(n, H, W, level, f64, extra_planes=0):
+    """_lib.batch_chunks of a stack of `n` frames on the float32 batch or, `f64`, the float64 batch (8 bytes per
+    pixel); `extra_planes`: the planes per frame beyond the transform's"""
+    kw = dict(extra_planes=extra_planes) if extra_planes else {}
+    if f64:
+        kw["itemsize"] = 8
+    return _lib.batch_chunks(n, H, W, level, **kw)
+
+
+@contextmanager
+def _batch(f64, n, H, W, family, level):
+    """a BatchPlan or, `f64`, a BatchPlan64 of at least `n` frames from the cache of the default context, handed
+    back to the cache on the way out"""
+    acquire, release = (_lib.acquire_batch64, _lib.release_batch64) if f64 else (_lib.acquire_batch, _lib.release_batch)
+    bp = acquire(_lib.default_context(), n, H, W, family, level)
+    try:
+        yield bp
+    finally:
+        release(bp)
+
+
+def _stack_route(fr, level, scaling_function, bilateral, noise_per_frame=(), noise_maps=False):
+    """(the float64 batch?, the bilateral march?) of transform_stack / denoise_stack, or None: the per-frame loop.
+    The predicates overlap at their edges; the order in which they are asked is the tie-break."""
+    args = (fr, level, scaling_function, bilateral, noise_per_frame, noise_maps)
+    if batch64_eligible(*args):
+        return True, False
+    if bilateral64_eligible(*args):
+        return True, True
+    if bilateral_eligible(*args):
+        return False, True
+    if batch_eligible(*args):
+        return False, False
+    return None
 
 
 def _f32_target(out, shape):
@@ -320,7 +354,7 @@ def _f32_target(out, shape):
 
 
 def _hand_over(res, out):
-    """the per-frame loop's result: as it is, or filled into the caller's `out`"""
+    """the per-frame loop's result, or a float64 batch's (_f64_target): as it is, or filled into the caller's `out`"""
     if out is None:
         return res
     out[...] = res
@@ -346,67 +380,36 @@ def _f64_target(out, shape):
     return _lib.host_empty(shape, dtype=np.float64), out
 
 
+def _target(f64, out, shape):
+    """(array the batch downloads into, the caller's `out` to fill afterwards or None), checked before any device work:
+    _f32_target's contract for a float32 batch, _f64_target's for a float64 batch"""
+    return _f64_target(out, shape) if f64 else (_f32_target(out, shape), None)
+
+
 def transform_stack(frames, level, scaling_function=B3spline, out=None, bilateral=None, bilateral_scaling=False):
     """(N, level+1, H, W) float32 (float64 for the stacks the reference computes in float64): the standard
     transform of every frame (AtrousTransform(scaling_function, bilateral, bilateral_scaling)(frame, level).data,
     ref:307-328), batched."""
     fr = _as_frames(frames)
-    if batch64_eligible(fr, level, scaling_function, bilateral):
-        return _transform_stack64(fr, level, scaling_function, out)
-    if bilateral64_eligible(fr, level, scaling_function, bilateral):
-        return _transform_stack64(fr, level, scaling_function, out, bilateral, bilateral_scaling)
-    bil = bilateral_eligible(fr, level, scaling_function, bilateral)
-    if not bil and not batch_eligible(fr, level, scaling_function, bilateral):
+    route = _stack_route(fr, level, scaling_function, bilateral)
+    if route is None:
         return _hand_over(np.stack([AtrousTransform(scaling_function, bilateral, bilateral_scaling)(f, level).data
                                     for f in fr]), out)
+    f64, bil = route                   # per frame: AtrousTransform._run's or, float64, AtrousTransform._call_f64's passes
     N, H, W = fr.shape
-    out = _f32_target(out, (N, level + 1, H, W))
-    if N == 0:
-        return out
-    ctx = _lib.default_context()
-    fam = _family_of(scaling_function(2))
-    chunks = _chunks(fr, level)
-    bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, fam, level)
-    try:
-        for f0, nf in chunks:
-            bp.upload(PLANE_INPUT, fr[f0:f0 + nf])
-            if bil:                                                # ref:433-442, AtrousTransform._run
-                sb = _sigma_bilateral_list(bilateral, level)
-                bp.decompose_bilateral(nf, PLANE_INPUT, level, sb, bilateral_scaling)
-            else:
-                bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
-            for s in range(level + 1):
-                bp.download(s, nf, out=out[f0:f0 + nf, s])         # straight into the caller's cube
-    finally:
-        _lib.release_batch(bp)
-    return out
-
-
-def _transform_stack64(fr, level, scaling_function, out, bilateral=None, bilateral_scaling=False):
-    """transform_stack on the float64 batch: per frame, AtrousTransform._call_f64's fused passes (batch64_eligible)
-    or, with `bilateral`, its one march per scale (bilateral64_eligible; ref:433-442)"""
-    N, H, W = fr.shape
-    res, fill = _f64_target(out, (N, level + 1, H, W))
-    ctx = _lib.default_context()
-    fam = _family_of(scaling_function(2))
-    chunks = _lib.batch_chunks(N, H, W, level, itemsize=8)
-    bp = _lib.acquire_batch64(ctx, max(nf for _, nf in chunks), H, W, fam, level)
-    try:
+    res, fill = _target(f64, out, (N, level + 1, H, W))
+    chunks = _plan_chunks(N, H, W, level, f64)
+    with _batch(f64, max(nf for _, nf in chunks), H, W, _family_of(scaling_function(2)), level) as bp:
         for f0, nf in chunks:
             bp.upload(PLANE_INPUT, fr[f0:f0 + nf])               # (integer / big-endian frames: widened on the device)
-            if bilateral is not None:
+            if bil:                                                # ref:433-442
                 sb = _sigma_bilateral_list(bilateral, level)
                 bp.decompose_bilateral(nf, PLANE_INPUT, level, sb, bilateral_scaling)
             else:
                 bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
             for s in range(level + 1):
-                bp.download(s, nf, out=res[f0:f0 + nf, s])
-    finally:
-        _lib.release_batch64(bp)
-    if fill is not None:
-        fill[...] = res
-        return fill
-    return res
+                bp.download(s, nf, out=res[f0:f0 + nf, s])         # straight into the caller's cube
+    return _hand_over(res, fill)
 
 
 def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_threshold=True, anscombe=False,
@@ -418,43 +421,20 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
     N = len(fr)
     nl = _noise_list(noise, N, fr[0].shape)
     level = len(weights)
-    maps = int(noise_map_eligible(fr, nl))                 # (the noise plane: one more plane per frame)
-    b64 = batch64_eligible(fr, level, scaling_function, bilateral, nl, noise_maps=True)
-    bil64 = not b64 and bilateral64_eligible(fr, level, scaling_function, bilateral, nl, noise_maps=True)
-    if b64 or bil64:
-        _, H, W = fr.shape
-        res, fill = _f64_target(out, (N, H, W))
-        fam = _family_of(scaling_function(2))
-        chunks = _lib.batch_chunks(N, H, W, level, extra_planes=maps, itemsize=8)
-        bp = _lib.acquire_batch64(_lib.default_context(), max(nf for _, nf in chunks), H, W, fam, level)
-        try:
-            _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe,
-                            bilateral if bil64 else None, res)
-        finally:
-            _lib.release_batch64(bp)
-        if fill is not None:
-            fill[...] = res
-            return fill
-        return res
-    bil = bilateral_eligible(fr, level, scaling_function, bilateral, nl, noise_maps=True)
-    if not bil and not batch_eligible(fr, level, scaling_function, bilateral, nl, noise_maps=True):
+    route = _stack_route(fr, level, scaling_function, bilateral, nl, noise_maps=True)
+    if route is None:
         per = nl if nl is not None else [noise] * N
         return _hand_over(np.stack([denoise(f, weights, scaling_function, n_i, bilateral, soft_threshold, anscombe)
                                     for f, n_i in zip(fr, per)]), out)
+    f64, bil = route
     _, H, W = fr.shape
-    out = _f32_target(out, (N, H, W))
-    if N == 0:
-        return out
-    ctx = _lib.default_context()
-    fam = _family_of(scaling_function(2))
-    chunks = _lib.batch_chunks(N, H, W, level, extra_planes=maps) if maps else _chunks(fr, level)
-    bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, fam, level)
-    try:
+    res, fill = _target(f64, out, (N, H, W))
+    maps = int(noise_map_eligible(fr, nl))                 # (the noise plane: one more plane per frame)
+    chunks = _plan_chunks(N, H, W, level, f64, maps)
+    with _batch(f64, max(nf for _, nf in chunks), H, W, _family_of(scaling_function(2)), level) as bp:
         _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe, bilateral if bil else None,
-                        out)
-    finally:
-        _lib.release_batch(bp)
-    return out
+                        res)
+    return _hand_over(res, fill)
 
 
 def _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe, bilateral, out):
@@ -592,21 +572,15 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
         if out is not None and not (isinstance(out, np.ndarray) and out.shape == (N, H, W) and out.dtype == np.float64
                                     and out.flags.c_contiguous and out.flags.writeable):
             raise ValueError(f"out: a C-contiguous float64 array of shape {(N, H, W)} expected")
-        out, _ = _f64_target(out, (N, H, W))
         bil = bilateral is not None
-    else:
-        out = _f32_target(out, (N, H, W))
+    out, _ = _target(f64, out, (N, H, W))
     planes = _lib.host_empty((N, nplanes, H, W), dtype=out.dtype) if return_coefficients else None
-    ctx = _lib.default_context()
-    fam = _family_of(scaling_function(2))
     maps = noise_map_eligible(fr, nl)
     # (the spare plane of the fused update, the gamma plane, the noise plane)
     extra = int(whitening and h < 1) + int(h > 0) + int(maps)
     shared = _shared_map(nl, (H, W))
-    chunks = _lib.batch_chunks(N, H, W, L, extra_planes=extra, itemsize=8) if f64 else _lib.batch_chunks(N, H, W, L, extra_planes=extra)
-    acquire, release = (_lib.acquire_batch64, _lib.release_batch64) if f64 else (_lib.acquire_batch, _lib.release_batch)
-    bp = acquire(ctx, max(nf for _, nf in chunks), H, W, fam, L)
-    try:
+    chunks = _plan_chunks(N, H, W, L, f64, extra)
+    with _batch(f64, max(nf for _, nf in chunks), H, W, _family_of(scaling_function(2)), L) as bp:
         for f0, nf in chunks:
             bp.upload(PLANE_INPUT, fr[f0:f0 + nf])                  # (float64 batch: integer frames are widened on the device)
             if bil:                                                                 # ref:140-151
@@ -623,8 +597,6 @@ def wow_stack(frames, scaling_function=B3spline, n_scales=None, weights=[], whit
             if return_coefficients:
                 for s in range(nplanes):
                     bp.download(s, nf, out=planes[f0:f0 + nf, s])
-    finally:
-        release(bp)
     return (out, planes) if return_coefficients else out
 
 
@@ -781,17 +753,10 @@ def enhance_stack(frames, noise=None, *, weights=None, denoise=None, soft_thresh
         res = np.stack([enhance(f, **kw) if per is None else enhance(f, n_i, **kw) for f, n_i in zip(fr, per or [None] * N)])
         return _hand_over(res, out)
     f64 = 'batch64' in routes.values()                     # (one element type: every group takes the same engine)
-    fill = None
-    if f64:
-        res, fill = _f64_target(out, fr.shape)
-    else:
-        res = _f32_target(out, fr.shape)
+    res, fill = _target(f64, out, fr.shape)
     for level, chans in groups.items():
         _enhance_group(fr, res, per, [p for p in plans if p[0] in chans], level, routes[level], atrous, soft_threshold)
-    if fill is not None:
-        fill[...] = res
-        return fill
-    return res
+    return _hand_over(res, fill)
 
 
 def _enhance_group(fr, res, per, plans, level, route, atrous, soft_threshold):
@@ -813,11 +778,9 @@ def _enhance_group(fr, res, per, plans, level, route, atrous, soft_threshold):
     entries = [e + [(s, 0, 1) for s in range(len(e), level)] for e in entries]
     wrows = [[w for _, _, w in e] for e in entries]
     whole = k == 3 and fr.flags.c_contiguous and res.flags.c_contiguous
-    frames_max = _lib.batch_chunks(N * k, H, W, level, itemsize=8 if f64 else 4)[0][1]
+    frames_max = _plan_chunks(N * k, H, W, level, f64)[0][1]
     m = max(1, frames_max // k)                                      # images per chunk
-    acquire, release = (_lib.acquire_batch64, _lib.release_batch64) if f64 else (_lib.acquire_batch, _lib.release_batch)
-    bp = acquire(_lib.default_context(), min(m, N) * k, H, W, fam, level)
-    try:
+    with _batch(f64, min(m, N) * k, H, W, fam, level) as bp:
         for i0 in range(0, N, m):
             n = min(m, N - i0)
             nf = n * k
@@ -844,8 +807,6 @@ def _enhance_group(fr, res, per, plans, level, route, atrous, soft_threshold):
             else:
                 for j, (c, _, _) in enumerate(plans):
                     bp.download(PLANE_OUT, n, out=res[i0:i0 + n] if c is Ellipsis else res[i0:i0 + n, c], f0=j * n)
-    finally:
-        release(bp)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -939,8 +900,7 @@ def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2
                                                     threshold_type=threshold_type, uniform_init=uniform_init,
                                                     persistent_mrs=persistent_mrs, fft=fft) for f in fr]), out)
     N, H, W = fr.shape
-    out = _f32_target(out, (N, H, W))
-    ctx = _lib.default_context()
+    out, _ = _target(False, out, (N, H, W))
     soft = threshold_type == 'soft'
     sf = B3spline(2)                                                             # ref:229 default transform
     sigma_e = sf.sigma_e()
@@ -951,9 +911,8 @@ def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2
         (fwd_k, fwd), (bwd_k, bwd) = _rl_direct_operands(psf32, H, fft)
     # Coefficients._denoise_sum(list(denoise_coefficients)): the (scale, sigma, weight) entries of the initial estimate
     entries = list(zip(range(level + 1), denoise_coefficients, (1,) * level))
-    chunks = _lib.batch_chunks(N, H, W, level, extra_planes=(_rl_extra_planes if direct else _rl_fft_extra_planes)(level))
-    bp = _lib.acquire_batch(ctx, max(nf for _, nf in chunks), H, W, _family_of(sf), level)
-    try:
+    chunks = _plan_chunks(N, H, W, level, False, (_rl_extra_planes if direct else _rl_fft_extra_planes)(level))
+    with _batch(False, max(nf for _, nf in chunks), H, W, _family_of(sf), level) as bp:
         if direct:
             bp.set_psf(0, fwd_k)
             bp.set_psf(1, bwd_k)
@@ -990,6 +949,4 @@ def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2
                     bp.fft_apply(nf, RES, CONV, True)                            # ref:284
                 bp.binary(nf, "mul", PSI, CONV, PSI)                             # ref:288
             bp.download(PSI, nf, out=out[f0:f0 + nf])
-    finally:
-        _lib.release_batch(bp)
     return out
