@@ -22,8 +22,7 @@
 #include <cstring>
 #include <vector>
 
-#include "wt_host.h"
-#include "wt_fused_decl.h"
+#include "wt_batch_core.h"
 #include "wt_reduce.h"
 #include "wt_rl_point.h"
 #include "wt_rng.h"
@@ -38,22 +37,13 @@ struct WtBatchSel {                 // select state of one rank of one frame
     uint32_t nan;                   // NaN pixels of the frame (counted by the first level)
 };
 
-struct wt_batch {
-    wt_ctx *ctx = nullptr;
+struct wt_batch : WtBatchCore<float> {
+    wt_batch() : WtBatchCore<float>("wt_batch") {}
     wt_plan geo;                    // ONE frame's geometry, context and family: what the fused launches read (no planes)
-    int n = 0, max_level = 0;
-    int64_t fstride = 0;            // floats from one frame to the next (H * P)
-    std::vector<float *> coef;      // planes 0 .. max_level
-    float *input = nullptr, *out = nullptr, *scr[2] = {nullptr, nullptr};
     uint32_t *d_hist = nullptr;     // [n][2 ranks][WT_HIST_BINS]
     WtBatchSel *d_sel = nullptr;    // [n][2 ranks]
     WtBatchSel *h_sel = nullptr;    // pinned copy
-    double *d_tau = nullptr;        // [n][2 * WT_MAX_SUM_PLANES]: thresholds of wt_batch_denoise_sum; wt_batch_enhance_sum: then the weights
-    double *h_tau = nullptr;        // pinned staging of the table
-    // wow: WT_PLANE_SCRATCH(3) = the output plane of wt_batch_wow_scale (swapped with the coefficient plane, as
-    // wt_wow_scale does), WT_PLANE_SCRATCH(4) = the gamma accumulator (utils.wow's plane ids)
-    float *spare = nullptr, *gamma = nullptr;
-    float *noise = nullptr;         // WT_PLANE_SCRATCH(5): the per-pixel noise maps of the frames (Coefficients' noise plane id)
+    // (d_tau: [n][2 * WT_MAX_SUM_PLANES], the thresholds of wt_batch_denoise_sum; wt_batch_enhance_sum: then the weights)
     // richardson_lucy: WT_PLANE_SCRATCH(6 .. 10) = data, psi, phi, residual, correlation; WT_PLANE_SCRATCH(16 + s) = the
     // support plane of scale s (utils.richardson_lucy's plane ids); the forward / backward PSF of wt_batch_set_psf
     float *rl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -65,15 +55,6 @@ struct wt_batch {
     // (wt_fft.h), allocated by the first wt_batch_fft_spectrum
     WtFftState fft;
     std::vector<void *> fft_allocs;
-    // per-frame parameter pairs of one launch ({tau, factor}, {gmin, gmax}): a ring of table slots [n][2], pinned
-    // staging + device copy; a slot is refilled only after the copy that last read it has completed (its event)
-    static constexpr int kTabSlots = 16;
-    double *d_ptab = nullptr, *h_ptab = nullptr;
-    hipEvent_t ptab_ev[kTabSlots] = {};
-    int ptab_next = 0;
-    // wt_batch_reduce: [n][red_blocks][4] partials + [n][4] results on the device, [n][4] pinned
-    double *d_red = nullptr, *h_red = nullptr;
-    int red_blocks = 0;
 };
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -418,87 +399,24 @@ __global__ __launch_bounds__(256) void wt_batch_reduce_final_kernel(const double
 }
 
 // ------------------------------------------------------------------------------------------------ host
-static int bplane(wt_batch *b, int id, float **out)
+// the planes only the float32 batch has (WtBatchCore::extra_plane): richardson_lucy's
+static float **batch_rl_plane(WtBatchCore<float> *core, int id)
 {
-    float **slot = nullptr;
-    if (id >= 0 && id <= b->max_level) slot = &b->coef[id];
-    else if (id == WT_PLANE_INPUT) slot = &b->input;
-    else if (id == WT_PLANE_OUT) slot = &b->out;
-    else if (id == WT_PLANE_SCRATCH(0)) slot = &b->scr[0];
-    else if (id == WT_PLANE_SCRATCH(1)) slot = &b->scr[1];
-    else if (id == WT_PLANE_SCRATCH(3)) slot = &b->spare;
-    else if (id == WT_PLANE_SCRATCH(4)) slot = &b->gamma;
-    else if (id == WT_PLANE_SCRATCH(5)) slot = &b->noise;
-    else if (id <= WT_PLANE_SCRATCH(6) && id >= WT_PLANE_SCRATCH(10)) slot = &b->rl[WT_PLANE_SCRATCH(6) - id];
-    else if (id <= WT_PLANE_SCRATCH(16) && id > WT_PLANE_SCRATCH(16) - (int)b->mrs.size()) slot = &b->mrs[WT_PLANE_SCRATCH(16) - id];
-    if (!slot)
-        WT_FAIL("wt_batch: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1/3/4/5, 6..10, 16..%d)", id, b->max_level,
-                15 + (int)b->mrs.size());
-    if (!*slot) WT_HIP(hipMalloc((void **)slot, (size_t)b->n * (size_t)b->fstride * sizeof(float)));
-    *out = *slot;
-    return 0;
-}
-
-static int check_frames(const wt_batch *b, int nf, const char *who)
-{
-    if (!b) WT_FAIL("%s: null batch", who);
-    if (nf < 1 || nf > b->n) WT_FAIL("%s: %d active frames (batch of %d)", who, nf, b->n);
-    return 0;
+    wt_batch *b = static_cast<wt_batch *>(core);
+    if (id <= WT_PLANE_SCRATCH(6) && id >= WT_PLANE_SCRATCH(10)) return &b->rl[WT_PLANE_SCRATCH(6) - id];
+    if (id <= WT_PLANE_SCRATCH(16) && id > WT_PLANE_SCRATCH(16) - (int)b->mrs.size()) return &b->mrs[WT_PLANE_SCRATCH(16) - id];
+    return nullptr;
 }
 
 // the fused schedule of `level` scales, or an error: the passes with a sum run fused kernels only; `single`: a
 // single-scale pass without a fused kernel runs the batched MODE_DECOMP stencil (as wt_decompose_pass on a plan)
-static int batch_schedule(wt_batch *b, int level, int32_t *tr, int *np, const char *who, bool single = false)
+static int batch_schedule(wt_batch *b, int level, int32_t *tr, int *np, const char *who, bool single)
 {
     if (level < 1 || level > b->max_level) WT_FAIL("%s: level %d outside [1, %d]", who, level, b->max_level);
-    WT_TRY(wt_schedule(b->geo.family, level, 1, tr, 32, np));
+    WT_TRY(wt_schedule(b->family, level, 1, tr, 32, np));
     for (int i = 0; i < *np; ++i)
-        if (!wt_fused_has_pass(tr[3 * i], tr[3 * i + 1], b->geo.family) && !(single && tr[3 * i + 1] == 1))
+        if (!wt_fused_has_pass(tr[3 * i], tr[3 * i + 1], b->family) && !(single && tr[3 * i + 1] == 1))
             WT_FAIL("%s: %d scales have no all-fused schedule (wt_plan_fused_ok): not a batch case", who, level);
-    return 0;
-}
-
-// the frames of a batched stencil launch on the batch's stream
-static StencilCtx batch_stencil_ctx(const wt_batch *b)
-{
-    return StencilCtx{b->ctx, b->ctx->stream, b->geo.g, b->geo.family};
-}
-
-// one single-scale pass of the transform on the batched MODE_DECOMP stencil (decompose_pass_impl's per-scale branch)
-static int batch_stencil_pass(wt_batch *b, int nf, int cur, int nxt, int s0)
-{
-    if (s0 < 0 || s0 > 24 || s0 > b->max_level) WT_FAIL("wt_batch_decompose: scale %d outside the batch (max_level %d)", s0, b->max_level);
-    if (cur == nxt || cur == s0 || nxt == s0) WT_FAIL("wt_batch_decompose: input/output planes alias the detail plane of the pass");
-    float *in = nullptr, *oc = nullptr, *ow = nullptr;
-    WT_TRY(bplane(b, cur, &in));
-    WT_TRY(bplane(b, nxt, &oc));
-    WT_TRY(bplane(b, s0, &ow));
-    ChainArgs a{};
-    a.in = in; a.out_c = oc; a.out_w = ow; a.aux = nullptr;
-    a.f1 = 1.f; a.f2 = 1.f; a.take_sqrt = 0;
-    WtFrames fr;
-    fr.n = nf;
-    fr.fstride = b->fstride;
-    return wt32_stencil_batch_launch(batch_stencil_ctx(b), MODE_DECOMP, a, s0, "wt_chain_batch_kernel<decomp>", fr);
-}
-
-// per-frame parameter pairs (pairs[2 * f], pairs[2 * f + 1]) -> a device table slot, stream-ordered (*dev)
-static int batch_table(wt_batch *b, int nf, const double *pairs, const double **dev)
-{
-    wt_ctx *c = b->ctx;
-    if (!b->d_ptab) {
-        WT_HIP(hipMalloc((void **)&b->d_ptab, (size_t)wt_batch::kTabSlots * b->n * 2 * sizeof(double)));
-        WT_HIP(hipHostMalloc((void **)&b->h_ptab, (size_t)wt_batch::kTabSlots * b->n * 2 * sizeof(double), 0));
-    }
-    const int slot = b->ptab_next;
-    b->ptab_next = (slot + 1) % wt_batch::kTabSlots;
-    if (b->ptab_ev[slot]) WT_HIP(hipEventSynchronize(b->ptab_ev[slot]));    // (the copy of kTabSlots calls ago)
-    else WT_HIP(hipEventCreateWithFlags(&b->ptab_ev[slot], hipEventDisableTiming));
-    double *h = b->h_ptab + (size_t)slot * b->n * 2, *d = b->d_ptab + (size_t)slot * b->n * 2;
-    memcpy(h, pairs, (size_t)nf * 2 * sizeof(double));
-    WT_HIP(hipMemcpyAsync(d, h, (size_t)nf * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    WT_HIP(hipEventRecord(b->ptab_ev[slot], c->stream));
-    *dev = d;
     return 0;
 }
 
@@ -511,91 +429,69 @@ static unsigned batch_flat_blocks(const wt_batch *b, int nf)
 
 static int batch_pass(wt_batch *b, int nf, int cur, int nxt, int s0, int ns, int acc, int sum_plane, bool first)
 {
-    if (ns < 1 || ns > WT_FUSED_MAX_SCALES || s0 < 0 || s0 + ns - 1 > b->max_level)
-        WT_FAIL("wt_batch_decompose_pass: scales [%d,%d) outside the batch (max_level %d)", s0, s0 + ns, b->max_level);
-    if (cur == nxt || (cur >= s0 && cur < s0 + ns) || (nxt >= s0 && nxt < s0 + ns))
-        WT_FAIL("wt_batch_decompose_pass: input/output planes alias the detail planes of the pass");
-    if (!wt_fused_has_pass(s0, ns, b->geo.family)) WT_FAIL("wt_batch_decompose_pass: no fused kernel for first scale %d x %d scales", s0, ns);
-    if (acc && first != (s0 == 0))
-        WT_FAIL("wt_batch_decompose_pass_sum: first must be set for the pass that starts at scale 0 and only for it (got first=%d, s0=%d)", (int)first, s0);
-    float *in = nullptr, *oc = nullptr, *ps = nullptr;
-    WT_TRY(bplane(b, cur, &in));
-    WT_TRY(bplane(b, nxt, &oc));
-    float *ow[WT_FUSED_MAX_SCALES] = {nullptr};
-    for (int k = 0; k < ns; ++k) WT_TRY(bplane(b, s0 + k, &ow[k]));
-    if (acc) {
-        if (sum_plane == cur || sum_plane == nxt || (sum_plane >= s0 && sum_plane < s0 + ns))
-            WT_FAIL("wt_batch_decompose_pass_sum: the sum plane aliases a plane of the pass");
-        WT_TRY(bplane(b, sum_plane, &ps));
-    }
+    float *in = nullptr, *oc = nullptr, *ps = nullptr, *ow[WT_FUSED_MAX_SCALES] = {nullptr};
+    WT_TRY(batch_pass_planes(b, cur, nxt, s0, ns, acc, sum_plane, first, &in, &oc, ow, &ps));
     FusedRows rows;
     rows.frames = nf;
     rows.fstride = b->fstride;
     return wt_fused_launch(&b->geo, in, oc, ow, s0, ns, acc, first ? nullptr : ps, ps, rows);
 }
 
-static int batch_schedule_run(wt_batch *b, int nf, int src, int level, bool with_sum, int dst, const char *who)
+static int batch_run(wt_batch *b, int nf, int src, int level, bool with_sum, int dst, const char *who)
 {
-    if (src >= 0 && src <= level) WT_FAIL("%s: src plane %d is one of the output planes", who, src);
-    if (src == WT_PLANE_SCRATCH(0) || src == WT_PLANE_SCRATCH(1)) WT_FAIL("%s: scratch planes 0/1 are used internally", who);
-    if (with_sum && ((dst >= 0 && dst <= level) || dst == src || dst == WT_PLANE_SCRATCH(0) || dst == WT_PLANE_SCRATCH(1)))
-        WT_FAIL("%s: dst plane %d is an input / output / internal plane of the transform", who, dst);
-    int32_t tr[3 * 32];
-    int np = 0;
-    WT_TRY(batch_schedule(b, level, tr, &np, who, !with_sum));
-    int cur = src;
-    for (int i = 0; i < np; ++i) {
-        const int s0 = tr[3 * i], ns = tr[3 * i + 1];
-        const bool last = s0 + ns == level;
-        const int nxt = last ? level : WT_PLANE_SCRATCH(i & 1);
-        if (!with_sum && ns == 1 && !wt_fused_has_pass(s0, 1, b->geo.family)) WT_TRY(batch_stencil_pass(b, nf, cur, nxt, s0));
-        else WT_TRY(batch_pass(b, nf, cur, nxt, s0, ns, with_sum ? (last ? 2 : 1) : 0, dst, i == 0));
-        cur = nxt;
-    }
-    return 0;
+    return batch_schedule_run(
+        b, nf, src, level, with_sum, dst, who,
+        [b](int lv, bool sum, int32_t *tr, int *np, const char *w) { return batch_schedule(b, lv, tr, np, w, !sum); },
+        [b](int frames, int cur, int nxt, int s0, int ns, int acc, int sum_plane, bool first) {
+            return batch_pass(b, frames, cur, nxt, s0, ns, acc, sum_plane, first);
+        });
+}
+
+// every buffer of the batch back to the runtime: the core's and the float32 engine's own
+static void batch_free(wt_batch *b, int *bad)
+{
+    batch_release(b, bad);
+    auto f = [&](void *q) { if (q && hipFree(q) != hipSuccess) *bad = 1; };
+    f(b->d_hist);
+    f(b->d_sel);
+    for (float *q : b->rl) f(q);
+    for (float *q : b->mrs) f(q);
+    f(b->d_psf[0]);
+    f(b->d_psf[1]);
+    for (void *q : b->fft_allocs) f(q);
+    if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) *bad = 1;
 }
 
 extern "C" int wt_batch_create(wt_ctx *ctx, int n, int H, int W, int family, int max_level, wt_batch **out)
 {
     WtGuard guard_(ctx);
-    if (!ctx || !out) WT_FAIL("wt_batch_create: null pointer");
-    *out = nullptr;
-    if (n < 1 || n > 65535) WT_FAIL("wt_batch_create: %d frames (1..65535 per batch)", n);
-    if (H < 1 || W < 1) WT_FAIL("wt_batch_create: frame %d x %d", H, W);
-    if (family != WT_B3SPLINE && family != WT_TRIANGLE) WT_FAIL("wt_batch_create: family %d (built-in families only)", family);
-    if (max_level < 0 || max_level > 30) WT_FAIL("wt_batch_create: max_level %d", max_level);
+    WT_TRY(batch_check_create(ctx, out, n, H, W, family, max_level, "wt_batch_create"));
     wt_batch *b = new wt_batch;
-    b->ctx = ctx;
-    b->n = n;
-    b->max_level = max_level;
+    batch_init(b, ctx, n, H, W, (W + 3) / 4 * 4, family, max_level);
     b->geo.ctx = ctx;
     b->geo.family = family;
     b->geo.max_level = max_level;
-    b->geo.g = Geo{W, (W + 3) / 4 * 4, H, 0, H, 0, 0};
-    b->fstride = (int64_t)H * b->geo.g.P;
-    b->coef.assign(max_level + 1, nullptr);
+    b->geo.g = b->g;
     b->mrs.assign(std::min(max_level, WT_NUM_SCRATCH - 16), nullptr);
+    b->extra_plane = batch_rl_plane;
+    b->extra_planes = ", 6..10, 16.." + std::to_string(15 + (int)b->mrs.size());
     if (!wt_fused_supported(&b->geo)) {
         delete b;
         WT_FAIL("wt_batch_create: rows of %d pixels are too wide for the fused passes", W);
     }
-    auto fail = [&](hipError_t e) -> int {
-        (void)hipFree(b->d_hist);
-        (void)hipFree(b->d_sel);
-        (void)hipFree(b->d_tau);
-        (void)hipHostFree(b->h_sel);
-        (void)hipHostFree(b->h_tau);
-        delete b;
-        wt_set_error("wt_batch_create: HIP error %d (%s)", (int)e, hipGetErrorString(e));
-        return 2;
-    };
     hipError_t e = hipMalloc((void **)&b->d_hist, (size_t)n * 2 * WT_HIST_BINS * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_sel, (size_t)n * 2 * sizeof(WtBatchSel));
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_tau, (size_t)n * 2 * WT_MAX_SUM_PLANES * sizeof(double));
     if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_sel, (size_t)n * 2 * sizeof(WtBatchSel), 0);
     if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_tau, (size_t)n * 2 * WT_MAX_SUM_PLANES * sizeof(double), 0);
     if (e == hipSuccess) e = hipMemsetAsync(b->d_hist, 0, (size_t)n * 2 * WT_HIST_BINS * sizeof(uint32_t), ctx->stream);
-    if (e != hipSuccess) return fail(e);
+    if (e != hipSuccess) {
+        int bad = 0;
+        batch_free(b, &bad);
+        delete b;
+        wt_set_error("wt_batch_create: HIP error %d (%s)", (int)e, hipGetErrorString(e));
+        return 2;
+    }
     *out = b;
     return 0;
 }
@@ -606,31 +502,7 @@ extern "C" int wt_batch_destroy(wt_batch *b)
     WtGuard guard_(b->ctx);
     (void)hipStreamSynchronize(b->ctx->stream);
     int bad = 0;
-    auto f = [&](void *q) { if (q && hipFree(q) != hipSuccess) bad = 1; };
-    for (float *q : b->coef) f(q);
-    f(b->input);
-    f(b->out);
-    f(b->scr[0]);
-    f(b->scr[1]);
-    f(b->d_hist);
-    f(b->d_sel);
-    f(b->d_tau);
-    f(b->spare);
-    f(b->gamma);
-    f(b->noise);
-    for (float *q : b->rl) f(q);
-    for (float *q : b->mrs) f(q);
-    f(b->d_psf[0]);
-    f(b->d_psf[1]);
-    for (void *q : b->fft_allocs) f(q);
-    f(b->d_ptab);
-    f(b->d_red);
-    if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) bad = 1;
-    if (b->h_tau && hipHostFree(b->h_tau) != hipSuccess) bad = 1;
-    if (b->h_ptab && hipHostFree(b->h_ptab) != hipSuccess) bad = 1;
-    if (b->h_red && hipHostFree(b->h_red) != hipSuccess) bad = 1;
-    for (hipEvent_t e : b->ptab_ev)
-        if (e && hipEventDestroy(e) != hipSuccess) bad = 1;
+    batch_free(b, &bad);
     delete b;
     if (bad) WT_FAIL("wt_batch_destroy: a device buffer could not be released");
     return 0;
@@ -638,54 +510,12 @@ extern "C" int wt_batch_destroy(wt_batch *b)
 
 extern "C" int wt_batch_info(wt_batch *b, int64_t *info)
 {
-    if (!b || !info) WT_FAIL("wt_batch_info: null pointer");
-    const Geo &g = b->geo.g;
-    const int64_t v[7] = {b->n, g.H, g.W, g.P, b->fstride, b->max_level, b->geo.family};
-    memcpy(info, v, sizeof v);
-    return 0;
+    return batch_info(b, info, "wt_batch_info");
 }
 
 extern "C" int wt_batch_plane_ptr(wt_batch *b, int plane, void **ptr, int64_t *frame_stride)
 {
-    if (!b || !ptr || !frame_stride) WT_FAIL("wt_batch_plane_ptr: null pointer");
-    WtGuard guard_(b->ctx);
-    float *q = nullptr;
-    WT_TRY(bplane(b, plane, &q));
-    *ptr = q;
-    *frame_stride = b->fstride;
-    return 0;
-}
-
-// frames [f0, f0 + nf) of a plane <-> host frames `hstride` floats apart (rows of W floats back to back within a frame)
-static int batch_copy(wt_batch *b, int plane, int f0, int nf, float *host, int64_t hstride, bool up, const char *who)
-{
-    if (!b || !host) WT_FAIL("%s: null pointer", who);
-    if (f0 < 0 || nf < 1 || f0 + nf > b->n) WT_FAIL("%s: frames [%d, %d) outside the batch of %d", who, f0, f0 + nf, b->n);
-    const Geo &g = b->geo.g;
-    const int64_t fpx = (int64_t)g.H * g.W;
-    if (hstride == 0) hstride = fpx;
-    if (hstride < fpx) WT_FAIL("%s: host frame stride %lld below the %lld pixels of a frame", who, (long long)hstride, (long long)fpx);
-    WtGuard guard_(b->ctx);
-    WT_TRY(wt_side_join(b->ctx));
-    float *q = nullptr;
-    WT_TRY(bplane(b, plane, &q));
-    float *dev = q + (int64_t)f0 * b->fstride;
-    const size_t span = ((size_t)(nf - 1) * (size_t)hstride + (size_t)fpx) * 4;
-    const bool pinned = try_pin(host, span);     // (no-op for page-locked blocks: _lib.host_empty)
-    hipError_t e = hipSuccess;
-    // contiguous frames are one tall image of nf * H rows; else one 2-D copy per frame
-    const int pieces = hstride == fpx ? 1 : nf;
-    const size_t rows = (size_t)g.H * (size_t)(hstride == fpx ? nf : 1);
-    for (int i = 0; i < pieces && e == hipSuccess; ++i) {
-        float *d = dev + (int64_t)i * b->fstride, *h = host + (int64_t)i * hstride;
-        e = up ? hipMemcpy2DAsync(d, (size_t)g.P * 4, h, (size_t)g.W * 4, (size_t)g.W * 4, rows, hipMemcpyHostToDevice, b->ctx->stream)
-               : hipMemcpy2DAsync(h, (size_t)g.W * 4, d, (size_t)g.P * 4, (size_t)g.W * 4, rows, hipMemcpyDeviceToHost, b->ctx->stream);
-    }
-    hipError_t e2 = hipStreamSynchronize(b->ctx->stream);
-    if (e == hipSuccess) e = e2;
-    if (pinned) (void)hipHostUnregister(host);
-    WT_HIP(e);
-    return 0;
+    return batch_plane_ptr(b, plane, ptr, frame_stride, "wt_batch_plane_ptr");
 }
 
 extern "C" int wt_batch_upload(wt_batch *b, int plane, int f0, int nf, const float *host, int64_t host_frame_stride)
@@ -700,72 +530,43 @@ extern "C" int wt_batch_download(wt_batch *b, int plane, int f0, int nf, float *
 
 extern "C" int wt_batch_decompose(wt_batch *b, int nf, int src, int level, int flags)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_decompose"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_decompose"));
     WtGuard guard_(b->ctx);
     if (!(flags & 1)) WT_FAIL("wt_batch_decompose: a batch runs the fused passes (flags bit0)");
     if (level == 0) {
-        float *s = nullptr, *d = nullptr;
+        float *s = nullptr;
         if (src == 0) WT_FAIL("wt_batch_decompose: src plane 0 is the output plane");
-        WT_TRY(bplane(b, src, &s));
-        WT_TRY(bplane(b, 0, &d));
-        WT_HIP(hipMemcpyAsync(d, s, (size_t)nf * (size_t)b->fstride * 4, hipMemcpyDeviceToDevice, b->ctx->stream));
-        return 0;
+        WT_TRY(batch_plane(b, src, &s));
+        return batch_copy_to_plane0(b, nf, s);
     }
-    return batch_schedule_run(b, nf, src, level, false, WT_PLANE_NONE, "wt_batch_decompose");
+    return batch_run(b, nf, src, level, false, WT_PLANE_NONE, "wt_batch_decompose");
 }
 
-// wt_decompose_bilateral (wt_transform.hip, watroo/wavelets.py:433-442) for the active frames: scale s reads `cur`,
-// writes c_{s+1} to a scratch plane (the two ping-pong; plane `level` on the last scale) and w_s to plane s, the
-// variance formed in the march with f1 = sigma_b[s]^2, f2 = s + 1 under bilateral_scaling.  One launch per scale for
-// all frames (wt_bilateral32_batch.hip); no two-kernel form, no side-stream overlap.
+// wt_decompose_bilateral (wt_transform.hip) for the active frames: batch_decompose_bilateral's loop on the batched
+// march of wt_bilateral32_batch.hip; no two-kernel form, no side-stream overlap.
 extern "C" int wt_batch_decompose_bilateral(wt_batch *b, int nf, int src, int level, const double *sigma_b, int bilateral_scaling, int flags)
 {
     (void)flags;
-    WT_TRY(check_frames(b, nf, "wt_batch_decompose_bilateral"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_decompose_bilateral"));
     WtGuard guard_(b->ctx);
-    if (!sigma_b) WT_FAIL("wt_batch_decompose_bilateral: null pointer");
-    if (level < 0 || level > b->max_level) WT_FAIL("wt_batch_decompose_bilateral: level %d exceeds the batch's max_level %d", level, b->max_level);
-    if (src >= 0 && src <= level) WT_FAIL("wt_batch_decompose_bilateral: src plane %d is one of the output planes", src);
-    if (src == WT_PLANE_SCRATCH(0) || src == WT_PLANE_SCRATCH(1)) WT_FAIL("wt_batch_decompose_bilateral: scratch planes 0/1 are used internally");
-    if (level > 25) WT_FAIL("wt_batch_decompose_bilateral: scale %d out of range", level - 1);
-    float *in = nullptr;
-    WT_TRY(bplane(b, src, &in));
-    if (level == 0) {
-        float *d = nullptr;
-        WT_TRY(bplane(b, 0, &d));
-        WT_HIP(hipMemcpyAsync(d, in, (size_t)nf * (size_t)b->fstride * 4, hipMemcpyDeviceToDevice, b->ctx->stream));
-        return 0;
-    }
-    WtFrames fr;
-    fr.n = nf;
-    fr.fstride = b->fstride;
-    for (int s = 0; s < level; ++s) {
-        const int nxt = (s == level - 1) ? level : WT_PLANE_SCRATCH(s & 1);
-        float *oc = nullptr, *ow = nullptr;
-        WT_TRY(bplane(b, nxt, &oc));
-        WT_TRY(bplane(b, s, &ow));
-        ChainArgs a{};
-        a.in = in; a.out_c = oc; a.out_w = ow;
-        // variance = sdev_loc(c_s)^2-form * sigma_b[s]**2 (* (s+1))   watroo/wavelets.py:434-436
-        a.f1 = (float)(sigma_b[s] * sigma_b[s]);
-        a.f2 = bilateral_scaling ? (float)(s + 1) : 1.f;
-        WT_TRY(wt32_bilateral_batch_launch(batch_stencil_ctx(b), a, s, g_opt_bilateral_paired != 0, fr));
-        in = oc;
-    }
-    return 0;
+    return batch_decompose_bilateral(
+        b, nf, src, level, sigma_b, bilateral_scaling, "wt_batch_decompose_bilateral", [] { return 0; },
+        [b](const ChainArgs &a, int s, const WtFrames &fr) {
+            return wt32_bilateral_batch_launch(batch_stencil_ctx(b), a, s, g_opt_bilateral_paired != 0, fr);
+        });
 }
 
 extern "C" int wt_batch_decompose_sum(wt_batch *b, int nf, int src, int level, int dst, int flags)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_decompose_sum"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_decompose_sum"));
     WtGuard guard_(b->ctx);
     if (!(flags & 1)) WT_FAIL("wt_batch_decompose_sum: a batch runs the fused passes (flags bit0)");
-    return batch_schedule_run(b, nf, src, level, true, dst, "wt_batch_decompose_sum");
+    return batch_run(b, nf, src, level, true, dst, "wt_batch_decompose_sum");
 }
 
 extern "C" int wt_batch_decompose_pass(wt_batch *b, int nf, int cur, int nxt, int s0, int ns, int flags)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_decompose_pass"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_decompose_pass"));
     WtGuard guard_(b->ctx);
     if (!(flags & 1)) WT_FAIL("wt_batch_decompose_pass: a batch runs the fused passes (flags bit0)");
     return batch_pass(b, nf, cur, nxt, s0, ns, 0, WT_PLANE_NONE, false);
@@ -774,7 +575,7 @@ extern "C" int wt_batch_decompose_pass(wt_batch *b, int nf, int cur, int nxt, in
 extern "C" int wt_batch_decompose_pass_sum(wt_batch *b, int nf, int cur, int nxt, int s0, int ns, int flags, int sum_plane, int first,
                                            int last)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_decompose_pass_sum"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_decompose_pass_sum"));
     WtGuard guard_(b->ctx);
     if (!(flags & 1)) WT_FAIL("wt_batch_decompose_pass_sum: a batch runs the fused passes (flags bit0)");
     return batch_pass(b, nf, cur, nxt, s0, ns, last ? 2 : 1, sum_plane, first != 0);
@@ -782,12 +583,12 @@ extern "C" int wt_batch_decompose_pass_sum(wt_batch *b, int nf, int cur, int nxt
 
 extern "C" int wt_batch_abs_median(wt_batch *b, int nf, int plane, float *medians)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_abs_median"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_abs_median"));
     if (!medians) WT_FAIL("wt_batch_abs_median: null pointer");
     WtGuard guard_(b->ctx);
     wt_ctx *c = b->ctx;
     float *q = nullptr;
-    WT_TRY(bplane(b, plane, &q));
+    WT_TRY(batch_plane(b, plane, &q));
     const Geo &g = b->geo.g;
     const int64_t N = (int64_t)g.H * g.W;
     const unsigned long long klo = (unsigned long long)((N - 1) / 2);
@@ -829,24 +630,20 @@ extern "C" int wt_batch_abs_median(wt_batch *b, int nf, int plane, float *median
 static int batch_denoise_sum(wt_batch *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft, int write_back,
                              int noise_plane, const char *who)
 {
-    WT_TRY(check_frames(b, nf, who));
+    WT_TRY(batch_check_frames(b, nf, who));
     WtGuard guard_(b->ctx);
-    if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > b->max_level)
-        WT_FAIL("%s: count %d out of range [1,%d]", who, count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
-    if (n_den < 0 || n_den > count) WT_FAIL("%s: n_den %d outside [0,%d]", who, n_den, count);
-    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("%s: null tau/wgt", who);
-    if (dst >= 0 && dst < count) WT_FAIL("%s: dst plane %d is one of the summed planes", who, dst);
+    WT_TRY(batch_check_sum(b, count, dst, n_den, 0, tau, wgt, who));
     if (noise_plane != WT_PLANE_NONE && (noise_plane == dst || (noise_plane >= 0 && noise_plane < count)))
         WT_FAIL("%s: the noise plane %d is a plane of the sum", who, noise_plane);
     BatchDenoiseArgs a{};
     a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
     for (int i = 0; i < count; ++i) {
-        WT_TRY(bplane(b, i, &a.p[i]));
+        WT_TRY(batch_plane(b, i, &a.p[i]));
         a.wgt[i] = i < n_den ? (float)wgt[i] : 1.f;
     }
     float *o = nullptr, *nz = nullptr;
-    WT_TRY(bplane(b, dst, &o));
-    if (noise_plane != WT_PLANE_NONE) WT_TRY(bplane(b, noise_plane, &nz));
+    WT_TRY(batch_plane(b, dst, &o));
+    if (noise_plane != WT_PLANE_NONE) WT_TRY(batch_plane(b, noise_plane, &nz));
     const int nt = std::max(n_den, 1);
     // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
     WT_HIP(hipStreamSynchronize(b->ctx->stream));
@@ -882,18 +679,14 @@ extern "C" int wt_batch_denoise_sum_map(wt_batch *b, int nf, int count, int dst,
 extern "C" int wt_batch_enhance_sum(wt_batch *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
                                     int write_back)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_enhance_sum"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_enhance_sum"));
     WtGuard guard_(b->ctx);
-    if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > b->max_level)
-        WT_FAIL("wt_batch_enhance_sum: count %d out of range [1,%d]", count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
-    if (n_den < 1 || n_den > count) WT_FAIL("wt_batch_enhance_sum: n_den %d outside [1,%d]", n_den, count);
-    if (!tau || !wgt) WT_FAIL("wt_batch_enhance_sum: null tau/wgt");
-    if (dst >= 0 && dst < count) WT_FAIL("wt_batch_enhance_sum: dst plane %d is one of the summed planes", dst);
+    WT_TRY(batch_check_sum(b, count, dst, n_den, 1, tau, wgt, "wt_batch_enhance_sum"));
     BatchEnhanceArgs a{};
     a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
-    for (int i = 0; i < count; ++i) WT_TRY(bplane(b, i, &a.p[i]));
+    for (int i = 0; i < count; ++i) WT_TRY(batch_plane(b, i, &a.p[i]));
     float *o = nullptr;
-    WT_TRY(bplane(b, dst, &o));
+    WT_TRY(batch_plane(b, dst, &o));
     // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
     WT_HIP(hipStreamSynchronize(b->ctx->stream));
     const int row = 2 * n_den;                              // nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables
@@ -913,22 +706,22 @@ extern "C" int wt_batch_enhance_sum(wt_batch *b, int nf, int count, int dst, int
 
 extern "C" int wt_batch_anscombe(wt_batch *b, int nf, int src, int dst, float alpha, float g, float sigma, int inverse)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_anscombe"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_anscombe"));
     WtGuard guard_(b->ctx);
     if (alpha == 0.f) WT_FAIL("wt_batch_anscombe: alpha must be non-zero");
     float *s = nullptr, *d = nullptr;
-    WT_TRY(bplane(b, src, &s));
-    WT_TRY(bplane(b, dst, &d));
+    WT_TRY(batch_plane(b, src, &s));
+    WT_TRY(batch_plane(b, dst, &d));
     return launch_anscombe(b->ctx, s, d, (int64_t)nf * b->fstride / 4, alpha, g, sigma, inverse);
 }
 
 // ------------------------------------------------------------------------------------------------ wow
 extern "C" int wt_batch_fill(wt_batch *b, int nf, int plane, float value)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_fill"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_fill"));
     WtGuard guard_(b->ctx);
     float *d = nullptr;
-    WT_TRY(bplane(b, plane, &d));
+    WT_TRY(batch_plane(b, plane, &d));
     const int64_t n4 = (int64_t)nf * b->fstride / 4;
     ProfScope ps(b->ctx, "wt_batch_fill_kernel");
     hipLaunchKernelGGL(wt_batch_fill_kernel, dim3(flat_grid(n4)), dim3(256), 0, b->ctx->stream, d, n4, value);
@@ -938,10 +731,10 @@ extern "C" int wt_batch_fill(wt_batch *b, int nf, int plane, float value)
 
 extern "C" int wt_batch_replicate(wt_batch *b, int nf, int plane)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_replicate"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_replicate"));
     WtGuard guard_(b->ctx);
     float *d = nullptr;
-    WT_TRY(bplane(b, plane, &d));
+    WT_TRY(batch_plane(b, plane, &d));
     if (nf == 1) return 0;
     const int64_t f4 = b->fstride / 4;
     ProfScope ps(b->ctx, "wt_batch_replicate_kernel");
@@ -953,38 +746,22 @@ extern "C" int wt_batch_replicate(wt_batch *b, int nf, int plane)
 // frame f of the plane <- the field wt_fill_normal(seed, first_trial + f) gives a wt_plan of the frame's shape
 extern "C" int wt_batch_fill_normal(wt_batch *b, int nf, int plane, uint64_t seed, uint32_t first_trial)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_fill_normal"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_fill_normal"));
     WtGuard guard_(b->ctx);
     float *d = nullptr;
-    WT_TRY(bplane(b, plane, &d));
+    WT_TRY(batch_plane(b, plane, &d));
     return wt_launch_fill_normal(b->ctx, d, b->geo.g, b->geo.g.H, nf, b->fstride, seed, first_trial);
-}
-
-static int wow_pairs(wt_batch *b, int nf, const double *tau, const float *factor, const double **dev, const char *who)
-{
-    if (!tau || !factor) WT_FAIL("%s: null tau / factor", who);
-    std::vector<double> pairs((size_t)nf * 2);
-    for (int f = 0; f < nf; ++f) {
-        pairs[2 * f] = tau[f];
-        pairs[2 * f + 1] = (double)factor[f];
-    }
-    return batch_table(b, nf, pairs.data(), dev);
 }
 
 // wt_batch_wow_update / wt_batch_wow_update_map: noise_plane == WT_PLANE_NONE runs the kernel without a map
 static int batch_wow_update(wt_batch *b, int nf, int plane, const double *tau, int soft, const float *factor, int gamma_plane, int noise_plane,
                             const char *who)
 {
-    WT_TRY(check_frames(b, nf, who));
+    WT_TRY(batch_check_frames(b, nf, who));
     WtGuard guard_(b->ctx);
-    if (gamma_plane == plane) WT_FAIL("%s: the gamma plane is the updated plane", who);
-    if (noise_plane != WT_PLANE_NONE && (noise_plane == plane || noise_plane == gamma_plane)) WT_FAIL("%s: the noise plane aliases a plane of the update", who);
     float *c = nullptr, *gm = nullptr, *nz = nullptr;
-    WT_TRY(bplane(b, plane, &c));
-    if (gamma_plane != WT_PLANE_NONE) WT_TRY(bplane(b, gamma_plane, &gm));
-    if (noise_plane != WT_PLANE_NONE) WT_TRY(bplane(b, noise_plane, &nz));
     const double *dt = nullptr;
-    WT_TRY(wow_pairs(b, nf, tau, factor, &dt, who));
+    WT_TRY(batch_wow_update_args(b, nf, plane, tau, factor, gamma_plane, noise_plane, who, &c, &gm, &nz, &dt));
     if (nz) {
         ProfScope ps(b->ctx, "wt_batch_wow_map_kernel");
         hipLaunchKernelGGL(wt_batch_wow_map_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, c, (const float *)nz, gm,
@@ -1013,31 +790,10 @@ extern "C" int wt_batch_wow_update_map(wt_batch *b, int nf, int plane, const dou
 static int batch_wow_scale(wt_batch *b, int nf, int plane, int s, const double *tau, int soft, const float *factor, int gamma_plane, int noise_plane,
                            const char *who)
 {
-    WT_TRY(check_frames(b, nf, who));
+    WT_TRY(batch_check_frames(b, nf, who));
     WtGuard guard_(b->ctx);
-    if (plane < 0 || plane > b->max_level) WT_FAIL("%s: plane %d is not a coefficient plane", who, plane);
-    if (s < 0 || s > 24) WT_FAIL("%s: scale %d out of range", who, s);
-    if (gamma_plane == plane || gamma_plane == WT_PLANE_SCRATCH(3)) WT_FAIL("%s: the gamma plane aliases a plane of the update", who);
-    if (noise_plane != WT_PLANE_NONE && (noise_plane == plane || noise_plane == WT_PLANE_SCRATCH(3) || noise_plane == gamma_plane))
-        WT_FAIL("%s: the noise plane aliases a plane of the update", who);
-    float *c = nullptr, *t = nullptr, *gm = nullptr, *nz = nullptr;
-    WT_TRY(bplane(b, plane, &c));
-    WT_TRY(bplane(b, WT_PLANE_SCRATCH(3), &t));
-    if (gamma_plane != WT_PLANE_NONE) WT_TRY(bplane(b, gamma_plane, &gm));
-    if (noise_plane != WT_PLANE_NONE) WT_TRY(bplane(b, noise_plane, &nz));
-    const double *dt = nullptr;
-    WT_TRY(wow_pairs(b, nf, tau, factor, &dt, who));
-    // (wt_wow_scale's arguments and its choice of instantiation; tau and factor come from the frame's row of the table)
-    ChainArgs a{};
-    a.in = c; a.out_c = t; a.out_w = nullptr; a.aux = nullptr;
-    a.noise = nz; a.gamma = gm; a.soft = soft; a.whiten = 1;
-    WtFrames fr;
-    fr.n = nf;
-    fr.fstride = b->fstride;
-    fr.ftab = dt;
-    WT_TRY(wt32_stencil_batch_launch(batch_stencil_ctx(b), nz ? MODE_WOW : (gm ? MODE_WOW_GAMMA : MODE_WOW_PLAIN), a, s, "wt_chain_batch_kernel<wow>", fr));
-    std::swap(b->coef[plane], b->spare);          // (wt_wow_scale: "in place" at pointer level)
-    return 0;
+    WT_TRY(batch_check_wow_scale(b, plane, s, who));
+    return batch_wow_scale_run(b, nf, plane, s, tau, soft, factor, gamma_plane, noise_plane, who);
 }
 
 extern "C" int wt_batch_wow_scale(wt_batch *b, int nf, int plane, int s, const double *tau, int soft, const float *factor, int gamma_plane)
@@ -1054,54 +810,36 @@ extern "C" int wt_batch_wow_scale_map(wt_batch *b, int nf, int plane, int s, con
 
 extern "C" int wt_batch_reduce(wt_batch *b, int nf, int plane, double *out)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_reduce"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_reduce"));
     if (!out) WT_FAIL("wt_batch_reduce: null pointer");
     WtGuard guard_(b->ctx);
     wt_ctx *c = b->ctx;
     float *q = nullptr;
-    WT_TRY(bplane(b, plane, &q));
+    WT_TRY(batch_plane(b, plane, &q));
     const Geo &g = b->geo.g;
     // (wt_reduce's work items: (row, chunk of 4096 pixels) pairs over at most partial_blocks blocks, per frame)
     const int blocks = (int)std::min<int64_t>((int64_t)g.H * ((g.W + 4095) / 4096), c->partial_blocks);
-    if (!b->d_red || b->red_blocks != blocks) {
-        (void)hipFree(b->d_red);
-        (void)hipHostFree(b->h_red);
-        b->d_red = nullptr;
-        b->h_red = nullptr;
-        WT_HIP(hipMalloc((void **)&b->d_red, (size_t)b->n * ((size_t)blocks + 1) * 4 * sizeof(double)));
-        WT_HIP(hipHostMalloc((void **)&b->h_red, (size_t)b->n * 4 * sizeof(double), 0));
-        b->red_blocks = blocks;
-    }
-    double *dout = b->d_red + (size_t)b->n * blocks * 4;
+    WT_TRY(batch_reduce_buffers(b, blocks, false));
     {
         ProfScope ps(c, "wt_batch_reduce_kernel");
         hipLaunchKernelGGL(wt_batch_reduce_kernel, dim3(blocks, nf), dim3(256), 0, c->stream, (const float *)q, g.H, g.P / 4, g.W, b->fstride, b->d_red);
-        hipLaunchKernelGGL(wt_batch_reduce_final_kernel, dim3(nf), dim3(256), 0, c->stream, (const double *)b->d_red, blocks, dout);
+        hipLaunchKernelGGL(wt_batch_reduce_final_kernel, dim3(nf), dim3(256), 0, c->stream, (const double *)b->d_red, blocks, batch_reduce_results(b));
     }
-    WT_HIP(hipGetLastError());
-    WT_HIP(hipMemcpyAsync(b->h_red, dout, (size_t)nf * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    WT_HIP(hipStreamSynchronize(c->stream));               // the one host round trip for all nf frames
-    memcpy(out, b->h_red, (size_t)nf * 4 * sizeof(double));
-    return 0;
+    return batch_reduce_fetch(b, nf, out);
 }
 
 extern "C" int wt_batch_gamma_blend(wt_batch *b, int nf, int recon, int gamma_plane, const float *gmin, const float *gmax, float inv_gamma,
                                     float h)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_gamma_blend"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_gamma_blend"));
     if (!gmin || !gmax) WT_FAIL("wt_batch_gamma_blend: null gmin / gmax");
     WtGuard guard_(b->ctx);
     if (recon == gamma_plane) WT_FAIL("wt_batch_gamma_blend: recon and gamma planes must differ");
     float *r = nullptr, *g = nullptr;
-    WT_TRY(bplane(b, recon, &r));
-    WT_TRY(bplane(b, gamma_plane, &g));
-    std::vector<double> pairs((size_t)nf * 2);
-    for (int f = 0; f < nf; ++f) {
-        pairs[2 * f] = gmin[f];
-        pairs[2 * f + 1] = gmax[f];
-    }
+    WT_TRY(batch_plane(b, recon, &r));
+    WT_TRY(batch_plane(b, gamma_plane, &g));
     const double *dt = nullptr;
-    WT_TRY(batch_table(b, nf, pairs.data(), &dt));
+    WT_TRY(batch_pairs(b, nf, gmin, gmax, &dt));
     ProfScope ps(b->ctx, "wt_batch_gamma_kernel");
     hipLaunchKernelGGL(wt_batch_gamma_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, r, g, b->fstride / 4, dt, inv_gamma, h);
     WT_HIP(hipGetLastError());
@@ -1110,19 +848,11 @@ extern "C" int wt_batch_gamma_blend(wt_batch *b, int nf, int recon, int gamma_pl
 
 extern "C" int wt_batch_plane_sum(wt_batch *b, int nf, int first, int count, int dst)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_plane_sum"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_plane_sum"));
     WtGuard guard_(b->ctx);
-    if (count < 1 || count > WT_MAX_SUM_PLANES) WT_FAIL("wt_batch_plane_sum: count %d out of range [1,%d]", count, WT_MAX_SUM_PLANES);
-    if (first < 0 || first + count - 1 > b->max_level) WT_FAIL("wt_batch_plane_sum: planes [%d,%d) outside [0,%d]", first, first + count, b->max_level);
-    if (dst >= first && dst < first + count) WT_FAIL("wt_batch_plane_sum: dst plane %d is one of the summed planes", dst);
     const float *planes[WT_MAX_SUM_PLANES];
-    for (int i = 0; i < count; ++i) {
-        float *q = nullptr;
-        WT_TRY(bplane(b, first + i, &q));
-        planes[i] = q;
-    }
     float *o = nullptr;
-    WT_TRY(bplane(b, dst, &o));
+    WT_TRY(batch_plane_sum_planes(b, first, count, dst, WT_MAX_SUM_PLANES, "wt_batch_plane_sum", planes, &o));
     // the frames back to back are one flat range: wt_plane_sum_kernel over all of them
     return launch_plane_sum(b->ctx, planes, count, o, (int64_t)nf * b->fstride / 4);
 }
@@ -1171,7 +901,7 @@ extern "C" int wt_batch_set_psf(wt_batch *b, int slot, const float *kernel, int 
 static int g_batch_f2d_plain = getenv("WT_BATCH_F2D_SKEW") ? 0 : 1;
 extern "C" int wt_batch_filter2d(wt_batch *b, int nf, int src, int dst, int slot, int ay, int ax, int border)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_filter2d"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_filter2d"));
     WtGuard guard_(b->ctx);
     if (slot < 0 || slot > 1 || !b->d_psf[slot] || !b->psf_kh[slot]) WT_FAIL("wt_batch_filter2d: PSF slot %d is not set (wt_batch_set_psf)", slot);
     const int kh = b->psf_kh[slot], kw = b->psf_kw[slot];
@@ -1184,8 +914,8 @@ extern "C" int wt_batch_filter2d(wt_batch *b, int nf, int src, int dst, int slot
     if (grid.y > 65535u) WT_FAIL("wt_batch_filter2d: frames of %d rows are too tall (%u row tiles, at most 65535)", g.H, grid.y);
     if (grid.z > 65535u) WT_FAIL("wt_batch_filter2d: %d frames in one launch (at most 65535)", nf);
     float *in = nullptr, *o = nullptr;
-    WT_TRY(bplane(b, src, &in));
-    WT_TRY(bplane(b, dst, &o));
+    WT_TRY(batch_plane(b, src, &in));
+    WT_TRY(batch_plane(b, dst, &o));
     const size_t lds = wt_f2d_lds_bytes(kh, kw);
     ProfScope ps(b->ctx, "wt_batch_filter2d_kernel");
     #define WT_BF2D_LAUNCH(WRAP, SKEW)                                                                                               \
@@ -1205,13 +935,13 @@ extern "C" int wt_batch_filter2d(wt_batch *b, int nf, int src, int dst, int slot
 // wt_binary over the active frames (watroo/utils.py:259,280-281,288)
 extern "C" int wt_batch_binary(wt_batch *b, int nf, int op, int a, int b2, int dst)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_binary"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_binary"));
     WtGuard guard_(b->ctx);
     if (op < 0 || op > WT_OP_ADD_DIV) WT_FAIL("wt_batch_binary: unknown op %d", op);
     float *pa = nullptr, *pb = nullptr, *pd = nullptr;
-    WT_TRY(bplane(b, a, &pa));
-    WT_TRY(bplane(b, b2, &pb));
-    WT_TRY(bplane(b, dst, &pd));
+    WT_TRY(batch_plane(b, a, &pa));
+    WT_TRY(batch_plane(b, b2, &pb));
+    WT_TRY(batch_plane(b, dst, &pd));
     const int64_t n4 = (int64_t)nf * b->fstride / 4;
     ProfScope ps(b->ctx, "wt_batch_binary_kernel");
     hipLaunchKernelGGL(wt_batch_binary_kernel, dim3(flat_grid(n4)), dim3(256), 0, b->ctx->stream, (const float *)pa, (const float *)pb, pd, n4, op);
@@ -1222,13 +952,13 @@ extern "C" int wt_batch_binary(wt_batch *b, int nf, int op, int a, int b2, int d
 // wt_mrs_update per frame (watroo/utils.py:263-276) with the frame's tau[f]; scalar noise only
 extern "C" int wt_batch_mrs_update(wt_batch *b, int nf, int plane, int mrs_plane, const double *tau, int soft, int persistent, float inv_pow)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_mrs_update"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_mrs_update"));
     WtGuard guard_(b->ctx);
     if (!tau) WT_FAIL("wt_batch_mrs_update: null tau");
     if (plane == mrs_plane) WT_FAIL("wt_batch_mrs_update: plane and mrs_plane must differ");
     float *c = nullptr, *m = nullptr;
-    WT_TRY(bplane(b, plane, &c));
-    WT_TRY(bplane(b, mrs_plane, &m));
+    WT_TRY(batch_plane(b, plane, &c));
+    WT_TRY(batch_plane(b, mrs_plane, &m));
     std::vector<double> pairs((size_t)nf * 2, 0.0);
     for (int f = 0; f < nf; ++f) pairs[2 * f] = tau[f];
     const double *dt = nullptr;
@@ -1259,7 +989,7 @@ extern "C" int wt_batch_fft_spectrum(wt_batch *b, int src)
     WT_TRY(wt_fft_supported(g.H, g.W, &ok));
     if (!ok) WT_FAIL("wt_batch_fft_spectrum: a side of the %d x %d frames has a prime factor above 5 (or lies outside 2 .. 8192)", g.H, g.W);
     float *s = nullptr;
-    WT_TRY(bplane(b, src, &s));
+    WT_TRY(batch_plane(b, src, &s));
     b->fft.have_spec = false;
     WT_TRY(wt_fft32_prepare(b->ctx, b->fft, g.H, g.W, b->fft_allocs, b->n));
     return wt_fft32_spectrum(b->ctx, b->fft, s, g.P);
@@ -1269,12 +999,12 @@ extern "C" int wt_batch_fft_spectrum(wt_batch *b, int src)
 // the batch's one kernel spectrum: six launches for all active frames, no stream drain, no host round trip
 extern "C" int wt_batch_fft_apply(wt_batch *b, int nf, int src, int dst, int conj)
 {
-    WT_TRY(check_frames(b, nf, "wt_batch_fft_apply"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch_fft_apply"));
     WtGuard guard_(b->ctx);
     if (src == dst) WT_FAIL("wt_batch_fft_apply: src and dst must differ");
     float *s = nullptr, *d = nullptr;
-    WT_TRY(bplane(b, src, &s));
-    WT_TRY(bplane(b, dst, &d));
+    WT_TRY(batch_plane(b, src, &s));
+    WT_TRY(batch_plane(b, dst, &d));
     if (!b->fft.have_spec) WT_FAIL("wt_batch_fft_apply: the batch has no kernel spectrum (wt_batch_fft_spectrum first)");
     return wt_fft32_apply(b->ctx, b->fft, s, d, b->geo.g.P, conj, nf, b->fstride);
 }

@@ -20,8 +20,7 @@
 #include <cstring>
 #include <vector>
 
-#include "wt_host.h"
-#include "wt_fused_decl.h"
+#include "wt_batch_core.h"
 #include "wt_math64.h"
 #include "wt_reduce.h"
 #include "wt_wow64.h"
@@ -35,34 +34,15 @@ struct WtBatch64Sel {               // select state of one rank of one frame
     uint32_t failed, pad;           // failed: the rank lies beyond the frame's keys (never, with every key counted)
 };
 
-struct wt_batch64 {
-    wt_ctx *ctx = nullptr;
+struct wt_batch64 : WtBatchCore<double> {
+    wt_batch64() : WtBatchCore<double>("wt_batch64") {}
     wt_plan64 geo;                  // ONE frame's geometry, context and taps: what the fused launches read (no planes)
-    int family = WT_B3SPLINE;
-    int n = 0, max_level = 0;
-    int64_t fstride = 0;            // doubles from one frame to the next (H * P)
-    std::vector<double *> coef;     // planes 0 .. max_level
-    double *input = nullptr, *out = nullptr, *scr[2] = {nullptr, nullptr};
-    double *noise = nullptr;        // WT_PLANE_SCRATCH(5): the per-pixel noise maps of the frames (Coefficients' noise plane id)
     void *istage = nullptr;         // frames of another element type on their way into a plane
     size_t istage_cap = 0;
     uint32_t *d_hist = nullptr;     // [n][2 ranks][WT_HIST_BINS] (allocated by the first median)
     WtBatch64Sel *d_sel = nullptr;  // [n][2 ranks]
     WtBatch64Sel *h_sel = nullptr;  // pinned copy
-    double *d_tau = nullptr;        // [n][3 * WT_MAX_SUM_PLANES]: the thresholds of wt_batch64_denoise_sum, then 1 / tau; wt_batch64_enhance_sum: then the weights
-    double *h_tau = nullptr;        // pinned staging of the table
-    // wow: WT_PLANE_SCRATCH(3) = the output plane of wt_batch64_wow_scale (swapped with the coefficient plane, as
-    // wt64_wow_scale does), WT_PLANE_SCRATCH(4) = the gamma accumulator (utils.wow's plane ids)
-    double *spare = nullptr, *gamma = nullptr;
-    // per-frame parameter pairs of one launch ({tau, factor}, {gmin, gmax}): a ring of table slots [n][2], pinned
-    // staging + device copy; a slot is refilled only after the copy that last read it has completed (its event)
-    static constexpr int kTabSlots = 16;
-    double *d_ptab = nullptr, *h_ptab = nullptr;
-    hipEvent_t ptab_ev[kTabSlots] = {};
-    int ptab_next = 0;
-    // wt_batch64_reduce: [n][red_blocks][4] partials + [n][4] results on the device, [n][4] pinned
-    double *d_red = nullptr, *h_red = nullptr;
-    int red_blocks = 0;
+    // (d_tau: [n][3 * WT_MAX_SUM_PLANES], the thresholds of wt_batch64_denoise_sum, then 1 / tau; wt_batch64_enhance_sum: then the weights)
 };
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -349,30 +329,6 @@ __global__ __launch_bounds__(256) void wt_batch64_plane_sum_kernel(Sum64Args a, 
 }
 
 // ------------------------------------------------------------------------------------------------ host
-static int b64plane(wt_batch64 *b, int id, double **out)
-{
-    double **slot = nullptr;
-    if (id >= 0 && id <= b->max_level) slot = &b->coef[id];
-    else if (id == WT_PLANE_INPUT) slot = &b->input;
-    else if (id == WT_PLANE_OUT) slot = &b->out;
-    else if (id == WT_PLANE_SCRATCH(0)) slot = &b->scr[0];
-    else if (id == WT_PLANE_SCRATCH(1)) slot = &b->scr[1];
-    else if (id == WT_PLANE_SCRATCH(3)) slot = &b->spare;
-    else if (id == WT_PLANE_SCRATCH(4)) slot = &b->gamma;
-    else if (id == WT_PLANE_SCRATCH(5)) slot = &b->noise;
-    if (!slot) WT_FAIL("wt_batch64: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1/3/4/5)", id, b->max_level);
-    if (!*slot) WT_HIP(hipMalloc((void **)slot, (size_t)b->n * (size_t)b->fstride * sizeof(double)));
-    *out = *slot;
-    return 0;
-}
-
-static int check_frames64(const wt_batch64 *b, int nf, const char *who)
-{
-    if (!b) WT_FAIL("%s: null batch", who);
-    if (nf < 1 || nf > b->n) WT_FAIL("%s: %d active frames (batch of %d)", who, nf, b->n);
-    return 0;
-}
-
 // fused64_ok (wt_f64.h) for one frame of this shape: an image (H >= 2) whose rows the fused passes take at 8 bytes
 // per pixel and whose float64 schedule of `level` scales is fused passes only
 static bool batch64_all_fused(int family, int64_t H, int64_t W, int level, int32_t *tr, int *np)
@@ -419,55 +375,19 @@ extern "C" int wt_batch64_wow_ok(int family, int64_t H, int64_t W, int level, in
     return 0;
 }
 
-// the frames of a batched stencil launch on the batch's stream: ONE frame's geometry (W, P, nrows, border 0 - what a
-// wt_plan64 of that shape hands wt_launch_stencil, so the kernel choice and the streaming-store flag are its own)
-static StencilCtx batch64_stencil_ctx(const wt_batch64 *b)
-{
-    return StencilCtx{b->ctx, b->ctx->stream, b->geo.g, b->family};
-}
-
-// one single-scale pass of the transform on the batched MODE_DECOMP stencil (fused64_run's smooth64 branch)
-static int batch64_stencil_pass(wt_batch64 *b, int nf, int cur, int nxt, int s0)
-{
-    if (s0 < 0 || s0 > 24 || s0 > b->max_level) WT_FAIL("wt_batch64_decompose: scale %d outside the batch (max_level %d)", s0, b->max_level);
-    if (cur == nxt || cur == s0 || nxt == s0) WT_FAIL("wt_batch64_decompose: input/output planes alias the detail plane of the pass");
-    double *in = nullptr, *oc = nullptr, *ow = nullptr;
-    WT_TRY(b64plane(b, cur, &in));
-    WT_TRY(b64plane(b, nxt, &oc));
-    WT_TRY(b64plane(b, s0, &ow));
-    ChainArgsT<double> a{};
-    a.in = in; a.out_c = oc; a.out_w = ow;
-    a.f1 = 1.0; a.f2 = 1.0;
-    WtFrames fr;
-    fr.n = nf;
-    fr.fstride = b->fstride;
-    return wt64_stencil_batch_launch(batch64_stencil_ctx(b), MODE_DECOMP, a, s0, "wt64_chain_batch_kernel<decomp>", fr);
-}
-
 static int batch64_pass(wt_batch64 *b, int nf, int cur, int nxt, int s0, int ns, int acc, int sum_plane, bool first)
 {
-    if (ns < 1 || ns > WT_FUSED_MAX_SCALES || s0 < 0 || s0 + ns - 1 > b->max_level)
-        WT_FAIL("wt_batch64_decompose_pass: scales [%d,%d) outside the batch (max_level %d)", s0, s0 + ns, b->max_level);
-    if (cur == nxt || (cur >= s0 && cur < s0 + ns) || (nxt >= s0 && nxt < s0 + ns))
-        WT_FAIL("wt_batch64_decompose_pass: input/output planes alias the detail planes of the pass");
-    if (!wt_fused_has_pass(s0, ns, b->family)) WT_FAIL("wt_batch64_decompose_pass: no fused kernel for first scale %d x %d scales", s0, ns);
-    if (acc && first != (s0 == 0))
-        WT_FAIL("wt_batch64_decompose_pass_sum: first must be set for the pass that starts at scale 0 and only for it (got first=%d, s0=%d)", (int)first, s0);
+    double *in = nullptr, *oc = nullptr, *ps = nullptr, *ow[WT_FUSED_MAX_SCALES] = {nullptr};
+    WT_TRY(batch_pass_planes(b, cur, nxt, s0, ns, acc, sum_plane, first, &in, &oc, ow, &ps));
     // (the arguments of fused64_pass, wt_f64.h)
     FusedArgsT<double> a{};
-    double *in = nullptr;
-    WT_TRY(b64plane(b, cur, &in));
     a.in = in;
-    WT_TRY(b64plane(b, nxt, &a.out_c));
-    for (int k = 0; k < ns && k < 3; ++k) WT_TRY(b64plane(b, s0 + k, &a.out_w[k]));
-    if (ns > 3) WT_TRY(b64plane(b, s0 + 3, &a.out_w3));
+    a.out_c = oc;
+    for (int k = 0; k < 3; ++k) a.out_w[k] = ow[k];
+    a.out_w3 = ow[3];
     a.g = b->geo.g;
-    if (acc) {
-        if (sum_plane == cur || sum_plane == nxt || (sum_plane >= s0 && sum_plane < s0 + ns))
-            WT_FAIL("wt_batch64_decompose_pass_sum: the sum plane aliases a plane of the pass");
-        WT_TRY(b64plane(b, sum_plane, &a.p_out));
-        a.p_in = first ? nullptr : a.p_out;
-    }
+    a.p_out = ps;
+    a.p_in = first ? nullptr : ps;
     FusedRows rows;
     rows.frames = nf;
     rows.fstride = b->fstride;
@@ -477,82 +397,51 @@ static int batch64_pass(wt_batch64 *b, int nf, int cur, int nxt, int s0, int ns,
     return b3 ? wt_fused_tu_f64_k5_batch_acc0(&b->geo, a, s0, ns, rows) : wt_fused_tu_f64_k3_batch_acc0(&b->geo, a, s0, ns, rows);
 }
 
-static int batch64_schedule_run(wt_batch64 *b, int nf, int src, int level, bool with_sum, int dst, const char *who)
+static int batch64_run(wt_batch64 *b, int nf, int src, int level, bool with_sum, int dst, const char *who)
 {
+    // (this engine refuses the level before it looks at the planes)
     if (level < 1 || level > b->max_level) WT_FAIL("%s: level %d outside [1, %d]", who, level, b->max_level);
-    if (src >= 0 && src <= level) WT_FAIL("%s: src plane %d is one of the output planes", who, src);
-    if (src == WT_PLANE_SCRATCH(0) || src == WT_PLANE_SCRATCH(1)) WT_FAIL("%s: scratch planes 0/1 are used internally", who);
-    if (with_sum && ((dst >= 0 && dst <= level) || dst == src || dst == WT_PLANE_SCRATCH(0) || dst == WT_PLANE_SCRATCH(1)))
-        WT_FAIL("%s: dst plane %d is an input / output / internal plane of the transform", who, dst);
-    int32_t tr[3 * 32];
-    int np = 0;
-    // (the passes with a sum run fused kernels only; a transform alone also takes single-scale stencil passes)
-    if (!batch64_all_fused(b->family, b->geo.g.H, b->geo.g.W, level, tr, &np) &&
-        (with_sum || !batch64_wow_shape_ok(b->family, b->geo.g.H, b->geo.g.W, level, tr, &np)))
-        WT_FAIL("%s: %d scales have no %s float64 schedule for %d x %d frames (%s): not a batch case", who, level,
-                with_sum ? "all-fused" : "batched", b->geo.g.H, b->geo.g.W, with_sum ? "wt64_plan_fused_ok" : "wt_batch64_wow_ok");
-    int cur = src;
-    for (int i = 0; i < np; ++i) {
-        const int s0 = tr[3 * i], ns = tr[3 * i + 1];
-        const bool last = s0 + ns == level;
-        const int nxt = last ? level : WT_PLANE_SCRATCH(i & 1);
-        if (!wt_fused_has_pass(s0, ns, b->family)) WT_TRY(batch64_stencil_pass(b, nf, cur, nxt, s0));
-        else WT_TRY(batch64_pass(b, nf, cur, nxt, s0, ns, with_sum ? (last ? 2 : 1) : 0, dst, i == 0));
-        cur = nxt;
-    }
-    return 0;
+    return batch_schedule_run(
+        b, nf, src, level, with_sum, dst, who,
+        // (the passes with a sum run fused kernels only; a transform alone also takes single-scale stencil passes)
+        [b](int lv, bool sum, int32_t *tr, int *np, const char *w) -> int {
+            if (!batch64_all_fused(b->family, b->geo.g.H, b->geo.g.W, lv, tr, np) &&
+                (sum || !batch64_wow_shape_ok(b->family, b->geo.g.H, b->geo.g.W, lv, tr, np)))
+                WT_FAIL("%s: %d scales have no %s float64 schedule for %d x %d frames (%s): not a batch case", w, lv, sum ? "all-fused" : "batched",
+                        b->geo.g.H, b->geo.g.W, sum ? "wt64_plan_fused_ok" : "wt_batch64_wow_ok");
+            return 0;
+        },
+        [b](int frames, int cur, int nxt, int s0, int ns, int acc, int sum_plane, bool first) {
+            return batch64_pass(b, frames, cur, nxt, s0, ns, acc, sum_plane, first);
+        });
 }
 
+// every buffer of the batch back to the runtime: the core's and the float64 engine's own
 static void batch64_free(wt_batch64 *b, int *bad)
 {
+    batch_release(b, bad);
     auto f = [&](void *q) { if (q && hipFree(q) != hipSuccess) *bad = 1; };
-    for (double *q : b->coef) f(q);
-    f(b->input);
-    f(b->out);
-    f(b->scr[0]);
-    f(b->scr[1]);
-    f(b->noise);
-    f(b->spare);
-    f(b->gamma);
-    f(b->d_ptab);
-    f(b->d_red);
     f(b->istage);
     f(b->d_hist);
     f(b->d_sel);
-    f(b->d_tau);
     if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) *bad = 1;
-    if (b->h_tau && hipHostFree(b->h_tau) != hipSuccess) *bad = 1;
-    if (b->h_ptab && hipHostFree(b->h_ptab) != hipSuccess) *bad = 1;
-    if (b->h_red && hipHostFree(b->h_red) != hipSuccess) *bad = 1;
-    for (hipEvent_t e : b->ptab_ev)
-        if (e && hipEventDestroy(e) != hipSuccess) *bad = 1;
 }
 
 extern "C" int wt_batch64_create(wt_ctx *ctx, int n, int H, int W, int family, int max_level, wt_batch64 **out)
 {
     WtGuard guard_(ctx);
-    if (!ctx || !out) WT_FAIL("wt_batch64_create: null pointer");
-    *out = nullptr;
-    if (n < 1 || n > 65535) WT_FAIL("wt_batch64_create: %d frames (1..65535 per batch)", n);
-    if (H < 1 || W < 1) WT_FAIL("wt_batch64_create: frame %d x %d", H, W);
-    if (family != WT_B3SPLINE && family != WT_TRIANGLE) WT_FAIL("wt_batch64_create: family %d (built-in families only)", family);
-    if (max_level < 0 || max_level > 30) WT_FAIL("wt_batch64_create: max_level %d", max_level);
+    WT_TRY(batch_check_create(ctx, out, n, H, W, family, max_level, "wt_batch64_create"));
     if (H < 2) WT_FAIL("wt_batch64_create: frames of one row are signals for the float64 engine (no fused passes)");
     if (!wt_fused_supported_bytes((int64_t)(W + 1) / 2 * 2 * 8)) WT_FAIL("wt_batch64_create: rows of %d pixels are too wide for the fused float64 passes", W);
     wt_batch64 *b = new wt_batch64;
-    b->ctx = ctx;
-    b->family = family;
-    b->n = n;
-    b->max_level = max_level;
+    batch_init(b, ctx, n, H, W, (W + 1) / 2 * 2, family, max_level);
     // the geometry and taps a wt_plan64 of this shape has (wt64_plan_create)
     static const double b3[5] = {1. / 16, 1. / 4, 3. / 8, 1. / 4, 1. / 16}, tri[3] = {1. / 4, 1. / 2, 1. / 4};
     b->geo.ctx = ctx;
-    b->geo.g = Geo{W, (W + 1) / 2 * 2, H, 0, H, 0, 0};
+    b->geo.g = b->g;
     b->geo.max_level = max_level;
     b->geo.ntaps = family == WT_B3SPLINE ? 5 : 3;
     for (int i = 0; i < b->geo.ntaps; ++i) b->geo.taps[i] = family == WT_B3SPLINE ? b3[i] : tri[i];
-    b->fstride = (int64_t)H * b->geo.g.P;
-    b->coef.assign(max_level + 1, nullptr);
     hipError_t e = hipMalloc((void **)&b->d_sel, (size_t)n * 2 * sizeof(WtBatch64Sel));
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_tau, (size_t)n * 3 * WT_MAX_SUM_PLANES * sizeof(double));
     if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_sel, (size_t)n * 2 * sizeof(WtBatch64Sel), 0);
@@ -582,70 +471,22 @@ extern "C" int wt_batch64_destroy(wt_batch64 *b)
 
 extern "C" int wt_batch64_info(wt_batch64 *b, int64_t *info)
 {
-    if (!b || !info) WT_FAIL("wt_batch64_info: null pointer");
-    const Geo &g = b->geo.g;
-    const int64_t v[7] = {b->n, g.H, g.W, g.P, b->fstride, b->max_level, b->family};
-    memcpy(info, v, sizeof v);
-    return 0;
+    return batch_info(b, info, "wt_batch64_info");
 }
 
 extern "C" int wt_batch64_plane_ptr(wt_batch64 *b, int plane, void **ptr, int64_t *frame_stride)
 {
-    if (!b || !ptr || !frame_stride) WT_FAIL("wt_batch64_plane_ptr: null pointer");
-    WtGuard guard_(b->ctx);
-    double *q = nullptr;
-    WT_TRY(b64plane(b, plane, &q));
-    *ptr = q;
-    *frame_stride = b->fstride;
-    return 0;
-}
-
-static int check_range64(const wt_batch64 *b, int f0, int nf, const char *who)
-{
-    if (f0 < 0 || nf < 1 || f0 + nf > b->n) WT_FAIL("%s: frames [%d, %d) outside the batch of %d", who, f0, f0 + nf, b->n);
-    return 0;
-}
-
-// frames [f0, f0 + nf) of a plane <-> host frames `hstride` doubles apart (rows of W doubles back to back within a frame)
-static int batch64_copy(wt_batch64 *b, int plane, int f0, int nf, double *host, int64_t hstride, bool up, const char *who)
-{
-    if (!b || !host) WT_FAIL("%s: null pointer", who);
-    WT_TRY(check_range64(b, f0, nf, who));
-    const Geo &g = b->geo.g;
-    const int64_t fpx = (int64_t)g.H * g.W;
-    if (hstride == 0) hstride = fpx;
-    if (hstride < fpx) WT_FAIL("%s: host frame stride %lld below the %lld pixels of a frame", who, (long long)hstride, (long long)fpx);
-    WtGuard guard_(b->ctx);
-    WT_TRY(wt_side_join(b->ctx));
-    double *q = nullptr;
-    WT_TRY(b64plane(b, plane, &q));
-    double *dev = q + (int64_t)f0 * b->fstride;
-    const size_t span = ((size_t)(nf - 1) * (size_t)hstride + (size_t)fpx) * 8;
-    const bool pinned = try_pin(host, span);     // (no-op for page-locked blocks: _lib.host_empty)
-    hipError_t e = hipSuccess;
-    // contiguous frames are one tall image of nf * H rows; else one 2-D copy per frame
-    const int pieces = hstride == fpx ? 1 : nf;
-    const size_t rows = (size_t)g.H * (size_t)(hstride == fpx ? nf : 1);
-    for (int i = 0; i < pieces && e == hipSuccess; ++i) {
-        double *d = dev + (int64_t)i * b->fstride, *h = host + (int64_t)i * hstride;
-        e = up ? hipMemcpy2DAsync(d, (size_t)g.P * 8, h, (size_t)g.W * 8, (size_t)g.W * 8, rows, hipMemcpyHostToDevice, b->ctx->stream)
-               : hipMemcpy2DAsync(h, (size_t)g.W * 8, d, (size_t)g.P * 8, (size_t)g.W * 8, rows, hipMemcpyDeviceToHost, b->ctx->stream);
-    }
-    hipError_t e2 = hipStreamSynchronize(b->ctx->stream);
-    if (e == hipSuccess) e = e2;
-    if (pinned) (void)hipHostUnregister(host);
-    WT_HIP(e);
-    return 0;
+    return batch_plane_ptr(b, plane, ptr, frame_stride, "wt_batch64_plane_ptr");
 }
 
 extern "C" int wt_batch64_upload(wt_batch64 *b, int plane, int f0, int nf, const double *host, int64_t host_frame_stride)
 {
-    return batch64_copy(b, plane, f0, nf, const_cast<double *>(host), host_frame_stride, true, "wt_batch64_upload");
+    return batch_copy(b, plane, f0, nf, const_cast<double *>(host), host_frame_stride, true, "wt_batch64_upload");
 }
 
 extern "C" int wt_batch64_download(wt_batch64 *b, int plane, int f0, int nf, double *host, int64_t host_frame_stride)
 {
-    return batch64_copy(b, plane, f0, nf, host, host_frame_stride, false, "wt_batch64_download");
+    return batch_copy(b, plane, f0, nf, host, host_frame_stride, false, "wt_batch64_download");
 }
 
 template <typename I>
@@ -662,7 +503,7 @@ static void batch64_widen_launch(wt_batch64 *b, double *dst, int nrows, bool swa
 extern "C" int wt_batch64_upload_elems(wt_batch64 *b, int plane, int f0, int nf, const void *host, int dtype)
 {
     if (!b || !host) WT_FAIL("wt_batch64_upload_elems: null pointer");
-    WT_TRY(check_range64(b, f0, nf, "wt_batch64_upload_elems"));
+    WT_TRY(batch_check_range(b, f0, nf, "wt_batch64_upload_elems"));
     WtGuard guard_(b->ctx);
     static const int isz[11] = {0, 1, 1, 2, 2, 4, 4, 8, 8, 4, 8};
     const bool swap = (dtype & WT_BYTESWAPPED) != 0;
@@ -675,7 +516,7 @@ extern "C" int wt_batch64_upload_elems(wt_batch64 *b, int plane, int f0, int nf,
     const size_t need = (size_t)nrows * (size_t)g.W * isz[base];
     WT_TRY(wt_side_join(b->ctx));
     double *q = nullptr;
-    WT_TRY(b64plane(b, plane, &q));
+    WT_TRY(batch_plane(b, plane, &q));
     if (b->istage_cap < need) {
         WT_HIP(hipStreamSynchronize(b->ctx->stream));
         if (b->istage) (void)hipFree(b->istage);
@@ -709,18 +550,16 @@ extern "C" int wt_batch64_upload_elems(wt_batch64 *b, int plane, int f0, int nf,
 
 extern "C" int wt_batch64_decompose(wt_batch64 *b, int nf, int src, int level, int flags)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_decompose"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_decompose"));
     WtGuard guard_(b->ctx);
     if (!(flags & 1)) WT_FAIL("wt_batch64_decompose: a batch runs the fused passes (flags bit0)");
     if (level == 0) {
-        double *s = nullptr, *d = nullptr;
+        double *s = nullptr;
         if (src == 0) WT_FAIL("wt_batch64_decompose: src plane 0 is the output plane");
-        WT_TRY(b64plane(b, src, &s));
-        WT_TRY(b64plane(b, 0, &d));
-        WT_HIP(hipMemcpyAsync(d, s, (size_t)nf * (size_t)b->fstride * 8, hipMemcpyDeviceToDevice, b->ctx->stream));
-        return 0;
+        WT_TRY(batch_plane(b, src, &s));
+        return batch_copy_to_plane0(b, nf, s);
     }
-    return batch64_schedule_run(b, nf, src, level, false, WT_PLANE_NONE, "wt_batch64_decompose");
+    return batch64_run(b, nf, src, level, false, WT_PLANE_NONE, "wt_batch64_decompose");
 }
 
 // When a frame of this shape takes the float64 bilateral march per frame (wt64_decompose_bilateral's `tiled`:
@@ -742,62 +581,35 @@ extern "C" int wt_batch64_bilateral_ok(int family, int64_t H, int64_t W, int lev
     return 0;
 }
 
-// wt64_decompose_bilateral (wt_f64.h, watroo/wavelets.py:433-442) for the active frames: scale s reads the current
-// smooth, writes c_{s+1} to a scratch plane (the two ping-pong; plane `level` on the last scale) and w_s to plane s,
-// the variance formed in the march with f1 = sigma_b[s]^2, f2 = s + 1 under bilateral_scaling.  One launch per scale
-// for all frames (wt_bilateral64_batch.hip); no three-kernel form, no side stream, no scale events.
+// wt64_decompose_bilateral (wt_f64.h) for the active frames: batch_decompose_bilateral's loop on the batched march of
+// wt_bilateral64_batch.hip; no three-kernel form, no side stream, no scale events.
 extern "C" int wt_batch64_decompose_bilateral(wt_batch64 *b, int nf, int src, int level, const double *sigma_b, int bilateral_scaling, int flags)
 {
     (void)flags;
-    WT_TRY(check_frames64(b, nf, "wt_batch64_decompose_bilateral"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_decompose_bilateral"));
     WtGuard guard_(b->ctx);
-    if (!sigma_b) WT_FAIL("wt_batch64_decompose_bilateral: null pointer");
-    if (level < 0 || level > b->max_level) WT_FAIL("wt_batch64_decompose_bilateral: level %d exceeds the batch's max_level %d", level, b->max_level);
-    if (src >= 0 && src <= level) WT_FAIL("wt_batch64_decompose_bilateral: src plane %d is one of the output planes", src);
-    if (src == WT_PLANE_SCRATCH(0) || src == WT_PLANE_SCRATCH(1)) WT_FAIL("wt_batch64_decompose_bilateral: scratch planes 0/1 are used internally");
-    if (level > 25) WT_FAIL("wt_batch64_decompose_bilateral: scale %d out of range", level - 1);
-    double *in = nullptr;
-    WT_TRY(b64plane(b, src, &in));
-    if (level == 0) {
-        double *d = nullptr;
-        WT_TRY(b64plane(b, 0, &d));
-        WT_HIP(hipMemcpyAsync(d, in, (size_t)nf * (size_t)b->fstride * 8, hipMemcpyDeviceToDevice, b->ctx->stream));
-        return 0;
-    }
-    if (!batch64_bilateral_shape_ok(b->family, b->geo.g.H, b->geo.g.W, level))
-        WT_FAIL("wt_batch64_decompose_bilateral: %d x %d frames do not take the float64 march per frame (wt_batch64_bilateral_ok): not a batch case",
-                b->geo.g.H, b->geo.g.W);
-    WtFrames fr;
-    fr.n = nf;
-    fr.fstride = b->fstride;
-    const StencilCtx sc{b->ctx, b->ctx->stream, b->geo.g, b->family};
-    for (int s = 0; s < level; ++s) {
-        const int nxt = (s == level - 1) ? level : WT_PLANE_SCRATCH(s & 1);
-        double *oc = nullptr, *ow = nullptr;
-        WT_TRY(b64plane(b, nxt, &oc));
-        WT_TRY(b64plane(b, s, &ow));
-        ChainArgsT<double> a{};
-        a.in = in; a.out_c = oc; a.out_w = ow;
-        // variance = sdev_loc(c_s)^2-form * sigma_b[s]**2 (* (s+1))   watroo/wavelets.py:434-436
-        a.f1 = sigma_b[s] * sigma_b[s];
-        a.f2 = bilateral_scaling ? (double)(s + 1) : 1.0;
-        WT_TRY(wt64_bilateral_batch_launch(sc, a, s, fr));
-        in = oc;
-    }
-    return 0;
+    return batch_decompose_bilateral(
+        b, nf, src, level, sigma_b, bilateral_scaling, "wt_batch64_decompose_bilateral",
+        [b, level]() -> int {
+            if (!batch64_bilateral_shape_ok(b->family, b->geo.g.H, b->geo.g.W, level))
+                WT_FAIL("wt_batch64_decompose_bilateral: %d x %d frames do not take the float64 march per frame (wt_batch64_bilateral_ok): not a batch case",
+                        b->geo.g.H, b->geo.g.W);
+            return 0;
+        },
+        [b](const ChainArgsT<double> &a, int s, const WtFrames &fr) { return wt64_bilateral_batch_launch(batch_stencil_ctx(b), a, s, fr); });
 }
 
 extern "C" int wt_batch64_decompose_sum(wt_batch64 *b, int nf, int src, int level, int dst, int flags)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_decompose_sum"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_decompose_sum"));
     WtGuard guard_(b->ctx);
     if (!(flags & 1)) WT_FAIL("wt_batch64_decompose_sum: a batch runs the fused passes (flags bit0)");
-    return batch64_schedule_run(b, nf, src, level, true, dst, "wt_batch64_decompose_sum");
+    return batch64_run(b, nf, src, level, true, dst, "wt_batch64_decompose_sum");
 }
 
 extern "C" int wt_batch64_decompose_pass(wt_batch64 *b, int nf, int cur, int nxt, int s0, int ns, int flags)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_decompose_pass"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_decompose_pass"));
     WtGuard guard_(b->ctx);
     if (!(flags & 1)) WT_FAIL("wt_batch64_decompose_pass: a batch runs the fused passes (flags bit0)");
     return batch64_pass(b, nf, cur, nxt, s0, ns, 0, WT_PLANE_NONE, false);
@@ -806,7 +618,7 @@ extern "C" int wt_batch64_decompose_pass(wt_batch64 *b, int nf, int cur, int nxt
 extern "C" int wt_batch64_decompose_pass_sum(wt_batch64 *b, int nf, int cur, int nxt, int s0, int ns, int flags, int sum_plane, int first,
                                              int last)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_decompose_pass_sum"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_decompose_pass_sum"));
     WtGuard guard_(b->ctx);
     if (!(flags & 1)) WT_FAIL("wt_batch64_decompose_pass_sum: a batch runs the fused passes (flags bit0)");
     return batch64_pass(b, nf, cur, nxt, s0, ns, last ? 2 : 1, sum_plane, first != 0);
@@ -814,12 +626,12 @@ extern "C" int wt_batch64_decompose_pass_sum(wt_batch64 *b, int nf, int cur, int
 
 extern "C" int wt_batch64_abs_median(wt_batch64 *b, int nf, int plane, double *medians)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_abs_median"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_abs_median"));
     if (!medians) WT_FAIL("wt_batch64_abs_median: null pointer");
     WtGuard guard_(b->ctx);
     wt_ctx *c = b->ctx;
     double *q = nullptr;
-    WT_TRY(b64plane(b, plane, &q));
+    WT_TRY(batch_plane(b, plane, &q));
     if (!b->d_hist) {
         WT_HIP(hipMalloc((void **)&b->d_hist, (size_t)b->n * 2 * WT_HIST_BINS * sizeof(uint32_t)));
         WT_HIP(hipMemsetAsync(b->d_hist, 0, (size_t)b->n * 2 * WT_HIST_BINS * sizeof(uint32_t), c->stream));
@@ -864,105 +676,98 @@ extern "C" int wt_batch64_abs_median(wt_batch64 *b, int nf, int plane, double *m
     return 0;
 }
 
-extern "C" int wt_batch64_denoise_sum(wt_batch64 *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
-                                      int write_back)
+// What the threshold sums share once their arguments hold: the drain before d_tau is rewritten (the table goes up
+// stream-ordered from pinned staging, and the previous call's kernel may still read it), then tau and 1 / tau (the
+// host's IEEE division: wt64_denoise_sum's inv_tau) of every active frame at the head of its `row` of the staging table.
+static int batch64_tau_rows(wt_batch64 *b, int nf, int n_den, int row, const double *tau)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_denoise_sum"));
-    WtGuard guard_(b->ctx);
-    if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > b->max_level)
-        WT_FAIL("wt_batch64_denoise_sum: count %d out of range [1,%d]", count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
-    if (n_den < 0 || n_den > count) WT_FAIL("wt_batch64_denoise_sum: n_den %d outside [0,%d]", n_den, count);
-    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("wt_batch64_denoise_sum: null tau/wgt");
-    if (dst >= 0 && dst < count) WT_FAIL("wt_batch64_denoise_sum: dst plane %d is one of the summed planes", dst);
-    Batch64DenoiseArgs a{};
-    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
-    for (int i = 0; i < count; ++i) {
-        WT_TRY(b64plane(b, i, &a.p[i]));
-        a.wgt[i] = i < n_den ? wgt[i] : 1.0;
-    }
-    double *o = nullptr;
-    WT_TRY(b64plane(b, dst, &o));
-    // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
     WT_HIP(hipStreamSynchronize(b->ctx->stream));
-    const int row = 2 * std::max(n_den, 1);
     for (int f = 0; f < nf; ++f)
         for (int k = 0; k < n_den; ++k) {
             const double t = tau[f * n_den + k];
             b->h_tau[f * row + k] = t;
-            b->h_tau[f * row + n_den + k] = t > 0.0 ? 1.0 / t : 0.0;       // (wt64_denoise_sum's inv_tau)
+            b->h_tau[f * row + n_den + k] = t > 0.0 ? 1.0 / t : 0.0;
         }
-    if (n_den == 0)
+    return 0;
+}
+
+// x blocks of the flat kernels over n2 16-byte groups
+static dim3 batch64_flat_grid(int64_t n2)
+{
+    return dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8));
+}
+
+// wt_batch64_denoise_sum / wt_batch64_denoise_sum_map (map: with the noise plane and the frames' has_map flags)
+static int batch64_denoise_sum(wt_batch64 *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft, int write_back,
+                               bool map, int noise_plane, const int *has_map, const char *who)
+{
+    WT_TRY(batch_check_frames(b, nf, who));
+    WtGuard guard_(b->ctx);
+    WT_TRY(batch_check_sum(b, count, dst, n_den, 0, tau, wgt, who));
+    if (map && noise_plane == WT_PLANE_NONE) WT_FAIL("%s: no noise plane (wt_batch64_denoise_sum is the call without a map)", who);
+    if (map && (noise_plane == dst || (noise_plane >= 0 && noise_plane < count))) WT_FAIL("%s: the noise plane %d is a plane of the sum", who, noise_plane);
+    Batch64DenoiseArgs a{};
+    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
+    for (int i = 0; i < count; ++i) {
+        WT_TRY(batch_plane(b, i, &a.p[i]));
+        a.wgt[i] = i < n_den ? wgt[i] : 1.0;
+    }
+    double *o = nullptr, *nz = nullptr;
+    WT_TRY(batch_plane(b, dst, &o));
+    if (map) WT_TRY(batch_plane(b, noise_plane, &nz));
+    // rows of {tau, 1 / tau}; with a map: then 1.0 for a frame that has one (nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables)
+    const int row = map ? 2 * n_den + 1 : 2 * std::max(n_den, 1);
+    WT_TRY(batch64_tau_rows(b, nf, n_den, row, tau));
+    if (map)
+        for (int f = 0; f < nf; ++f) b->h_tau[f * row + 2 * n_den] = (!has_map || has_map[f]) ? 1.0 : 0.0;
+    else if (n_den == 0)
         for (int i = 0; i < nf * row; ++i) b->h_tau[i] = 0.0;
     WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * row * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
     const int64_t n2 = (int64_t)nf * b->fstride / 2;
-    ProfScope ps(b->ctx, "wt_batch64_denoise_sum_kernel");
-    hipLaunchKernelGGL(wt_batch64_denoise_sum_kernel, dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8)), dim3(256), 0,
-                       b->ctx->stream, a, (const double *)b->d_tau, o, n2, b->fstride / 2);
+    if (map) {
+        ProfScope ps(b->ctx, "wt_batch64_denoise_sum_map_kernel");
+        hipLaunchKernelGGL(wt_batch64_denoise_sum_map_kernel, batch64_flat_grid(n2), dim3(256), 0, b->ctx->stream, a, (const double *)b->d_tau,
+                           (const double *)nz, o, n2, b->fstride / 2);
+    } else {
+        ProfScope ps(b->ctx, "wt_batch64_denoise_sum_kernel");
+        hipLaunchKernelGGL(wt_batch64_denoise_sum_kernel, batch64_flat_grid(n2), dim3(256), 0, b->ctx->stream, a, (const double *)b->d_tau, o, n2,
+                           b->fstride / 2);
+    }
     WT_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int wt_batch64_denoise_sum(wt_batch64 *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
+                                      int write_back)
+{
+    return batch64_denoise_sum(b, nf, count, dst, n_den, tau, wgt, soft, write_back, false, WT_PLANE_NONE, nullptr, "wt_batch64_denoise_sum");
 }
 
 extern "C" int wt_batch64_denoise_sum_map(wt_batch64 *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
                                           int write_back, int noise_plane, const int *has_map)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_denoise_sum_map"));
-    WtGuard guard_(b->ctx);
-    if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > b->max_level)
-        WT_FAIL("wt_batch64_denoise_sum_map: count %d out of range [1,%d]", count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
-    if (n_den < 0 || n_den > count) WT_FAIL("wt_batch64_denoise_sum_map: n_den %d outside [0,%d]", n_den, count);
-    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("wt_batch64_denoise_sum_map: null tau/wgt");
-    if (dst >= 0 && dst < count) WT_FAIL("wt_batch64_denoise_sum_map: dst plane %d is one of the summed planes", dst);
-    if (noise_plane == WT_PLANE_NONE) WT_FAIL("wt_batch64_denoise_sum_map: no noise plane (wt_batch64_denoise_sum is the call without a map)");
-    if (noise_plane == dst || (noise_plane >= 0 && noise_plane < count)) WT_FAIL("wt_batch64_denoise_sum_map: the noise plane %d is a plane of the sum", noise_plane);
-    Batch64DenoiseArgs a{};
-    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
-    for (int i = 0; i < count; ++i) {
-        WT_TRY(b64plane(b, i, &a.p[i]));
-        a.wgt[i] = i < n_den ? wgt[i] : 1.0;
-    }
-    double *o = nullptr, *nz = nullptr;
-    WT_TRY(b64plane(b, dst, &o));
-    WT_TRY(b64plane(b, noise_plane, &nz));
-    // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
-    WT_HIP(hipStreamSynchronize(b->ctx->stream));
-    const int row = 2 * n_den + 1;                          // nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables
-    for (int f = 0; f < nf; ++f) {
-        for (int k = 0; k < n_den; ++k) {
-            const double t = tau[f * n_den + k];
-            b->h_tau[f * row + k] = t;
-            b->h_tau[f * row + n_den + k] = t > 0.0 ? 1.0 / t : 0.0;       // (wt64_denoise_sum's inv_tau)
-        }
-        b->h_tau[f * row + 2 * n_den] = (!has_map || has_map[f]) ? 1.0 : 0.0;
-    }
-    WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * row * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
-    const int64_t n2 = (int64_t)nf * b->fstride / 2;
-    ProfScope ps(b->ctx, "wt_batch64_denoise_sum_map_kernel");
-    hipLaunchKernelGGL(wt_batch64_denoise_sum_map_kernel, dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8)), dim3(256), 0,
-                       b->ctx->stream, a, (const double *)b->d_tau, (const double *)nz, o, n2, b->fstride / 2);
-    WT_HIP(hipGetLastError());
-    return 0;
+    return batch64_denoise_sum(b, nf, count, dst, n_den, tau, wgt, soft, write_back, true, noise_plane, has_map, "wt_batch64_denoise_sum_map");
 }
 
 extern "C" int wt_batch64_fill(wt_batch64 *b, int nf, int plane, double value)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_fill"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_fill"));
     WtGuard guard_(b->ctx);
     double *d = nullptr;
-    WT_TRY(b64plane(b, plane, &d));
+    WT_TRY(batch_plane(b, plane, &d));
     const int64_t n2 = (int64_t)nf * b->fstride / 2;
     ProfScope ps(b->ctx, "wt_batch64_fill_kernel");
-    hipLaunchKernelGGL(wt_batch64_fill_kernel, dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8)), dim3(256), 0, b->ctx->stream, d, n2,
-                       value);
+    hipLaunchKernelGGL(wt_batch64_fill_kernel, batch64_flat_grid(n2), dim3(256), 0, b->ctx->stream, d, n2, value);
     WT_HIP(hipGetLastError());
     return 0;
 }
 
 extern "C" int wt_batch64_replicate(wt_batch64 *b, int nf, int plane)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_replicate"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_replicate"));
     WtGuard guard_(b->ctx);
     double *d = nullptr;
-    WT_TRY(b64plane(b, plane, &d));
+    WT_TRY(batch_plane(b, plane, &d));
     if (nf == 1) return 0;
     const int64_t f2 = b->fstride / 2;
     const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((f2 + 255) / 256, (2048 + nf - 1) / nf));
@@ -975,45 +780,35 @@ extern "C" int wt_batch64_replicate(wt_batch64 *b, int nf, int plane)
 extern "C" int wt_batch64_enhance_sum(wt_batch64 *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
                                       int write_back)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_enhance_sum"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_enhance_sum"));
     WtGuard guard_(b->ctx);
-    if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > b->max_level)
-        WT_FAIL("wt_batch64_enhance_sum: count %d out of range [1,%d]", count, std::min(WT_MAX_SUM_PLANES, b->max_level + 1));
-    if (n_den < 1 || n_den > count) WT_FAIL("wt_batch64_enhance_sum: n_den %d outside [1,%d]", n_den, count);
-    if (!tau || !wgt) WT_FAIL("wt_batch64_enhance_sum: null tau/wgt");
-    if (dst >= 0 && dst < count) WT_FAIL("wt_batch64_enhance_sum: dst plane %d is one of the summed planes", dst);
+    WT_TRY(batch_check_sum(b, count, dst, n_den, 1, tau, wgt, "wt_batch64_enhance_sum"));
     Batch64EnhanceArgs a{};
     a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
-    for (int i = 0; i < count; ++i) WT_TRY(b64plane(b, i, &a.p[i]));
+    for (int i = 0; i < count; ++i) WT_TRY(batch_plane(b, i, &a.p[i]));
     double *o = nullptr;
-    WT_TRY(b64plane(b, dst, &o));
-    // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
-    WT_HIP(hipStreamSynchronize(b->ctx->stream));
+    WT_TRY(batch_plane(b, dst, &o));
     const int row = 3 * n_den;                              // nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables
+    WT_TRY(batch64_tau_rows(b, nf, n_den, row, tau));
     for (int f = 0; f < nf; ++f)
-        for (int k = 0; k < n_den; ++k) {
-            const double t = tau[f * n_den + k];
-            b->h_tau[f * row + k] = t;
-            b->h_tau[f * row + n_den + k] = t > 0.0 ? 1.0 / t : 0.0;       // (wt64_denoise_sum's inv_tau)
-            b->h_tau[f * row + 2 * n_den + k] = wgt[f * n_den + k];
-        }
+        for (int k = 0; k < n_den; ++k) b->h_tau[f * row + 2 * n_den + k] = wgt[f * n_den + k];
     WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * row * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
     const int64_t n2 = (int64_t)nf * b->fstride / 2;
     ProfScope ps(b->ctx, "wt_batch64_enhance_sum_kernel");
-    hipLaunchKernelGGL(wt_batch64_enhance_sum_kernel, dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8)), dim3(256), 0,
-                       b->ctx->stream, a, (const double *)b->d_tau, o, n2, b->fstride / 2);
+    hipLaunchKernelGGL(wt_batch64_enhance_sum_kernel, batch64_flat_grid(n2), dim3(256), 0, b->ctx->stream, a, (const double *)b->d_tau, o, n2,
+                       b->fstride / 2);
     WT_HIP(hipGetLastError());
     return 0;
 }
 
 extern "C" int wt_batch64_anscombe(wt_batch64 *b, int nf, int src, int dst, double alpha, double g, double sigma, int inverse)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_anscombe"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_anscombe"));
     WtGuard guard_(b->ctx);
     if (alpha == 0.0) WT_FAIL("wt_batch64_anscombe: alpha must be non-zero");
     double *s = nullptr, *d = nullptr;
-    WT_TRY(b64plane(b, src, &s));
-    WT_TRY(b64plane(b, dst, &d));
+    WT_TRY(batch_plane(b, src, &s));
+    WT_TRY(batch_plane(b, dst, &d));
     const Geo &geo = b->geo.g;
     const int64_t nrows64 = (int64_t)nf * geo.H;
     if (nrows64 > INT32_MAX) WT_FAIL("wt_batch64_anscombe: %lld rows", (long long)nrows64);
@@ -1026,38 +821,6 @@ extern "C" int wt_batch64_anscombe(wt_batch64 *b, int nf, int src, int dst, doub
 }
 
 // ------------------------------------------------------------------------------------------------ wow
-// per-frame parameter pairs (pairs[2 * f], pairs[2 * f + 1]) -> a device table slot, stream-ordered (*dev)
-static int batch64_table(wt_batch64 *b, int nf, const double *pairs, const double **dev)
-{
-    wt_ctx *c = b->ctx;
-    if (!b->d_ptab) {
-        WT_HIP(hipMalloc((void **)&b->d_ptab, (size_t)wt_batch64::kTabSlots * b->n * 2 * sizeof(double)));
-        WT_HIP(hipHostMalloc((void **)&b->h_ptab, (size_t)wt_batch64::kTabSlots * b->n * 2 * sizeof(double), 0));
-    }
-    const int slot = b->ptab_next;
-    b->ptab_next = (slot + 1) % wt_batch64::kTabSlots;
-    if (b->ptab_ev[slot]) WT_HIP(hipEventSynchronize(b->ptab_ev[slot]));    // (the copy of kTabSlots calls ago)
-    else WT_HIP(hipEventCreateWithFlags(&b->ptab_ev[slot], hipEventDisableTiming));
-    double *h = b->h_ptab + (size_t)slot * b->n * 2, *d = b->d_ptab + (size_t)slot * b->n * 2;
-    memcpy(h, pairs, (size_t)nf * 2 * sizeof(double));
-    WT_HIP(hipMemcpyAsync(d, h, (size_t)nf * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    WT_HIP(hipEventRecord(b->ptab_ev[slot], c->stream));
-    *dev = d;
-    return 0;
-}
-
-// {tau[f], factor[f]} of a wow launch: the factors travel as the doubles the host computed (utils._wow_factor)
-static int wow64_pairs(wt_batch64 *b, int nf, const double *tau, const double *factor, const double **dev, const char *who)
-{
-    if (!tau || !factor) WT_FAIL("%s: null tau / factor", who);
-    std::vector<double> pairs((size_t)nf * 2);
-    for (int f = 0; f < nf; ++f) {
-        pairs[2 * f] = tau[f];
-        pairs[2 * f + 1] = factor[f];
-    }
-    return batch64_table(b, nf, pairs.data(), dev);
-}
-
 // grid of the batched pointwise kernels: wt64's (x blocks, rows) per frame, the frame as grid z
 static dim3 batch64_point_grid(const wt_batch64 *b, int nf)
 {
@@ -1069,16 +832,11 @@ static dim3 batch64_point_grid(const wt_batch64 *b, int nf)
 static int batch64_wow_update(wt_batch64 *b, int nf, int plane, const double *tau, int soft, const double *factor, int gamma_plane, int noise_plane,
                               const char *who)
 {
-    WT_TRY(check_frames64(b, nf, who));
+    WT_TRY(batch_check_frames(b, nf, who));
     WtGuard guard_(b->ctx);
-    if (gamma_plane == plane) WT_FAIL("%s: the gamma plane is the updated plane", who);
-    if (noise_plane != WT_PLANE_NONE && (noise_plane == plane || noise_plane == gamma_plane)) WT_FAIL("%s: the noise plane aliases a plane of the update", who);
     double *c = nullptr, *gm = nullptr, *nz = nullptr;
-    WT_TRY(b64plane(b, plane, &c));
-    if (gamma_plane != WT_PLANE_NONE) WT_TRY(b64plane(b, gamma_plane, &gm));
-    if (noise_plane != WT_PLANE_NONE) WT_TRY(b64plane(b, noise_plane, &nz));
     const double *dt = nullptr;
-    WT_TRY(wow64_pairs(b, nf, tau, factor, &dt, who));
+    WT_TRY(batch_wow_update_args(b, nf, plane, tau, factor, gamma_plane, noise_plane, who, &c, &gm, &nz, &dt));
     const Geo &g = b->geo.g;
     ProfScope ps(b->ctx, nz ? "wt_batch64_wow_map_kernel" : "wt_batch64_wow_kernel");
     hipLaunchKernelGGL(wt_batch64_wow_kernel, batch64_point_grid(b, nf), dim3(256), 0, b->ctx->stream, c, (const double *)nz, gm, g.W, g.P, g.H,
@@ -1103,33 +861,11 @@ extern "C" int wt_batch64_wow_update_map(wt_batch64 *b, int nf, int plane, const
 static int batch64_wow_scale(wt_batch64 *b, int nf, int plane, int s, const double *tau, int soft, const double *factor, int gamma_plane,
                              int noise_plane, const char *who)
 {
-    WT_TRY(check_frames64(b, nf, who));
+    WT_TRY(batch_check_frames(b, nf, who));
     WtGuard guard_(b->ctx);
-    if (plane < 0 || plane > b->max_level) WT_FAIL("%s: plane %d is not a coefficient plane", who, plane);
-    if (s < 0 || s > 24) WT_FAIL("%s: scale %d out of range", who, s);
+    WT_TRY(batch_check_wow_scale(b, plane, s, who));
     if (!wt_get_stencil64()) WT_FAIL("%s: option stencil64 is off (the per-frame call runs the generic kernels): not a batch case", who);
-    if (gamma_plane == plane || gamma_plane == WT_PLANE_SCRATCH(3)) WT_FAIL("%s: the gamma plane aliases a plane of the update", who);
-    if (noise_plane != WT_PLANE_NONE && (noise_plane == plane || noise_plane == WT_PLANE_SCRATCH(3) || noise_plane == gamma_plane))
-        WT_FAIL("%s: the noise plane aliases a plane of the update", who);
-    double *c = nullptr, *t = nullptr, *gm = nullptr, *nz = nullptr;
-    WT_TRY(b64plane(b, plane, &c));
-    WT_TRY(b64plane(b, WT_PLANE_SCRATCH(3), &t));
-    if (gamma_plane != WT_PLANE_NONE) WT_TRY(b64plane(b, gamma_plane, &gm));
-    if (noise_plane != WT_PLANE_NONE) WT_TRY(b64plane(b, noise_plane, &nz));
-    const double *dt = nullptr;
-    WT_TRY(wow64_pairs(b, nf, tau, factor, &dt, who));
-    // (wt64_wow_scale's arguments and its choice of instantiation; tau and factor come from the frame's row of the table)
-    ChainArgsT<double> a{};
-    a.in = c; a.out_c = t;
-    a.noise = nz; a.gamma = gm; a.soft = soft; a.whiten = 1;
-    WtFrames fr;
-    fr.n = nf;
-    fr.fstride = b->fstride;
-    fr.ftab = dt;
-    WT_TRY(wt64_stencil_batch_launch(batch64_stencil_ctx(b), !nz && !gm ? MODE_WOW_PLAIN : (!nz ? MODE_WOW_GAMMA : MODE_WOW), a, s,
-                                     "wt64_chain_batch_kernel<wow>", fr));
-    std::swap(b->coef[plane], b->spare);          // (wt64_wow_scale: "in place" at pointer level)
-    return 0;
+    return batch_wow_scale_run(b, nf, plane, s, tau, soft, factor, gamma_plane, noise_plane, who);
 }
 
 extern "C" int wt_batch64_wow_scale(wt_batch64 *b, int nf, int plane, int s, const double *tau, int soft, const double *factor, int gamma_plane)
@@ -1146,55 +882,36 @@ extern "C" int wt_batch64_wow_scale_map(wt_batch64 *b, int nf, int plane, int s,
 
 extern "C" int wt_batch64_reduce(wt_batch64 *b, int nf, int plane, double *out)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_reduce"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_reduce"));
     if (!out) WT_FAIL("wt_batch64_reduce: null pointer");
     WtGuard guard_(b->ctx);
     wt_ctx *c = b->ctx;
     double *q = nullptr;
-    WT_TRY(b64plane(b, plane, &q));
+    WT_TRY(batch_plane(b, plane, &q));
     const Geo &g = b->geo.g;
     // (wt64_reduce's split: row-strided blocks, at most partial_blocks of them, per frame)
     const int blocks = std::min(g.H, c->partial_blocks);
-    if (!b->d_red || b->red_blocks != blocks) {
-        WT_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(b->d_red);
-        (void)hipHostFree(b->h_red);
-        b->d_red = nullptr;
-        b->h_red = nullptr;
-        WT_HIP(hipMalloc((void **)&b->d_red, (size_t)b->n * ((size_t)blocks + 1) * 4 * sizeof(double)));
-        WT_HIP(hipHostMalloc((void **)&b->h_red, (size_t)b->n * 4 * sizeof(double), 0));
-        b->red_blocks = blocks;
-    }
-    double *dout = b->d_red + (size_t)b->n * blocks * 4;
+    WT_TRY(batch_reduce_buffers(b, blocks, true));
     {
         ProfScope ps(c, "wt_batch64_reduce_kernel");
         hipLaunchKernelGGL(wt_batch64_reduce_kernel, dim3(blocks, nf), dim3(256), 0, c->stream, (const double *)q, g.H, g.P, g.W, b->fstride, b->d_red);
-        hipLaunchKernelGGL(wt_batch64_reduce_final_kernel, dim3(nf), dim3(256), 0, c->stream, (const double *)b->d_red, blocks, dout);
+        hipLaunchKernelGGL(wt_batch64_reduce_final_kernel, dim3(nf), dim3(256), 0, c->stream, (const double *)b->d_red, blocks, batch_reduce_results(b));
     }
-    WT_HIP(hipGetLastError());
-    WT_HIP(hipMemcpyAsync(b->h_red, dout, (size_t)nf * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    WT_HIP(hipStreamSynchronize(c->stream));               // the one host round trip for all nf frames
-    memcpy(out, b->h_red, (size_t)nf * 4 * sizeof(double));
-    return 0;
+    return batch_reduce_fetch(b, nf, out);
 }
 
 extern "C" int wt_batch64_gamma_blend(wt_batch64 *b, int nf, int recon, int gamma_plane, const double *gmin, const double *gmax, double inv_gamma,
                                       double h)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_gamma_blend"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_gamma_blend"));
     if (!gmin || !gmax) WT_FAIL("wt_batch64_gamma_blend: null gmin / gmax");
     WtGuard guard_(b->ctx);
     if (recon == gamma_plane) WT_FAIL("wt_batch64_gamma_blend: recon and gamma planes must differ");
     double *r = nullptr, *g = nullptr;
-    WT_TRY(b64plane(b, recon, &r));
-    WT_TRY(b64plane(b, gamma_plane, &g));
-    std::vector<double> pairs((size_t)nf * 2);
-    for (int f = 0; f < nf; ++f) {
-        pairs[2 * f] = gmin[f];
-        pairs[2 * f + 1] = gmax[f];
-    }
+    WT_TRY(batch_plane(b, recon, &r));
+    WT_TRY(batch_plane(b, gamma_plane, &g));
     const double *dt = nullptr;
-    WT_TRY(batch64_table(b, nf, pairs.data(), &dt));
+    WT_TRY(batch_pairs(b, nf, gmin, gmax, &dt));
     const Geo &geo = b->geo.g;
     ProfScope ps(b->ctx, "wt_batch64_gamma_kernel");
     hipLaunchKernelGGL(wt_batch64_gamma_kernel, batch64_point_grid(b, nf), dim3(256), 0, b->ctx->stream, r, (const double *)g, geo.W, geo.P, geo.H,
@@ -1205,20 +922,12 @@ extern "C" int wt_batch64_gamma_blend(wt_batch64 *b, int nf, int recon, int gamm
 
 extern "C" int wt_batch64_plane_sum(wt_batch64 *b, int nf, int first, int count, int dst)
 {
-    WT_TRY(check_frames64(b, nf, "wt_batch64_plane_sum"));
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_plane_sum"));
     WtGuard guard_(b->ctx);
-    if (count < 1 || count > 32) WT_FAIL("wt_batch64_plane_sum: count %d out of range [1,32]", count);
-    if (first < 0 || first + count - 1 > b->max_level) WT_FAIL("wt_batch64_plane_sum: planes [%d,%d) outside [0,%d]", first, first + count, b->max_level);
-    if (dst >= first && dst < first + count) WT_FAIL("wt_batch64_plane_sum: dst plane %d is one of the summed planes", dst);
     Sum64Args a{};
     a.n = count;
-    for (int i = 0; i < count; ++i) {
-        double *q = nullptr;
-        WT_TRY(b64plane(b, first + i, &q));
-        a.p[i] = q;
-    }
     double *o = nullptr;
-    WT_TRY(b64plane(b, dst, &o));
+    WT_TRY(batch_plane_sum_planes(b, first, count, dst, 32, "wt_batch64_plane_sum", a.p, &o));
     // the frames back to back are one flat range: wt64_plane_sum_kernel's groups over all of them
     const int64_t n2 = (int64_t)nf * b->fstride / 2;
     ProfScope ps(b->ctx, "wt_batch64_plane_sum_kernel");
