@@ -823,6 +823,30 @@ int wt_batch64_gamma_blend(wt_batch64 *batch, int nf, int recon, int gamma_plane
 /* wt64_plane_sum per frame: dst = planes [first, first + count) summed in plane order (np.sum(coefficients, axis=0),
  * watroo/utils.py:205); count <= 32 */
 int wt_batch64_plane_sum(wt_batch64 *batch, int nf, int first, int count, int dst);
+/* ---- richardson_lucy over a float64 batch (watroo/utils.py:222-290, utils.richardson_lucy per frame on a wt_plan64):
+ * the float64 twins of the wt_batch_set_psf / _filter2d / _binary / _mrs_update entries.  Extra planes, the per-frame
+ * call's ids, allocated on first use: WT_PLANE_SCRATCH(6 .. 10) - data, psi, phi, residual, correlation - and
+ * WT_PLANE_SCRATCH(16 + s), s < max_level, the support plane of scale s; they are planes of a batch from its first
+ * wt_batch64_set_psf on.  Every frame gets the bits of the per-frame call. */
+/* host logic: *ok = 1 when wt_batch64_set_psf takes a kh x kw PSF (cv2.filter2D of watroo/utils.py:257,286 in one launch
+ * of the tiled kernel): kh * kw <= 4096, kw <= 512 and (64 + kw - 1) * (16 + kh - 1) * 8 <= 96 KB; no GPU needed */
+int wt_batch64_psf_ok(int kh, int kw, int *ok);
+/* One PSF operand of the call -> device memory of the batch: slot 0 the forward operand (the flipped PSF of
+ * watroo/utils.py:257), slot 1 the backward one (utils.py:286).  `kernel`: kh * kw host doubles, copied before the
+ * call returns.  PSFs of wt_batch64_psf_ok only. */
+int wt_batch64_set_psf(wt_batch64 *batch, int slot, const double *kernel, int kh, int kw);
+/* wt64_filter2d per frame with the PSF of `slot` (cv2.filter2D of watroo/utils.py:257,286 with WT_BORDER_SYMMETRIC;
+ * the circular products of utils.py:245-254,284 with WT_BORDER_PERIODIC), anchor (ay, ax) inside the kernel,
+ * src != dst: one launch for all active frames (64 x 16 output tiles, the input window staged in LDS as doubles), no
+ * stream drain, no PSF copy */
+int wt_batch64_filter2d(wt_batch64 *batch, int nf, int src, int dst, int slot, int ay, int ax, int border);
+/* wt64_binary over the active frames: dst = a OP b (watroo/utils.py:259,280-281,288); op as in wt_batch_binary
+ * (0 sub, 1 add, 2 mul, 3 div, 4 (a + b) / b) */
+int wt_batch64_binary(wt_batch64 *batch, int nf, int op, int a, int b, int dst);
+/* wt64_mrs_update per frame (watroo/utils.py:263-276) with the frame's tau[f] (<= 0: significance one); scalar noise
+ * only - the noise of richardson_lucy is the data's MAD estimate (utils.py:262) */
+int wt_batch64_mrs_update(wt_batch64 *batch, int nf, int plane, int mrs_plane, const double *tau, int soft,
+                          int persistent, double inv_pow);
 
 #ifdef __cplusplus
 }

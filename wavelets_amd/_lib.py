@@ -283,6 +283,12 @@ SIGNATURES = {
     "wt_batch64_gamma_blend": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
                                           _c.POINTER(_c.c_double), _c.c_double, _c.c_double]),
     "wt_batch64_plane_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch64_psf_ok": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
+    "wt_batch64_set_psf": (_c.c_int, [_vp, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _c.c_int]),
+    "wt_batch64_filter2d": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch64_binary": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_batch64_mrs_update": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _c.c_int,
+                                         _c.c_double]),
 }
 
 _lib = None
@@ -1027,6 +1033,14 @@ def batch_psf_ok(kh, kw):
     return bool(ok.value)
 
 
+def batch64_psf_ok(kh, kw):
+    """True when a float64 batch takes a kh x kw PSF (host logic, wt_batch64_psf_ok): RLBatchPlan64.filter2d applies it
+    in a single launch - at most 4096 taps in rows of at most 512, an LDS tile of doubles of at most 96 KB"""
+    ok = _c.c_int(0)
+    check(load().wt_batch64_psf_ok(int(kh), int(kw), _c.byref(ok)))
+    return bool(ok.value)
+
+
 def batch_fft_ok(H, W):
     """True when a batch of H x W frames takes the circular products through the FFT (host logic, wt_batch_fft_ok):
     fft_supported's rule on the frame shape - sides 2 .. 8192 without a prime factor above 5"""
@@ -1212,10 +1226,10 @@ class BatchPlan(_BatchBase):
     # -- richardson_lucy (wt_batch_set_psf / _filter2d / _binary / _mrs_update)
     def set_psf(self, slot, kernel):
         """PSF operand `slot` (0: forward, 1: backward) of the batch <- `kernel`, once per call of the stack function"""
-        k = np.ascontiguousarray(kernel, dtype=np.float32)
+        k = np.ascontiguousarray(kernel, dtype=self.dtype)
         if k.ndim != 2:
             raise ValueError("set_psf kernel must be 2-D")
-        self._call("set_psf", slot, k.ctypes.data_as(_fp), k.shape[0], k.shape[1])
+        self._call("set_psf", slot, k.ctypes.data_as(_c.POINTER(self._real)), k.shape[0], k.shape[1])
         self._psf_shape = getattr(self, "_psf_shape", {})
         self._psf_shape[slot] = k.shape
 
@@ -1272,8 +1286,8 @@ def batch64_wow_ok(family, H, W, level):
 class BatchPlan64(_BatchBase):
     """Double-precision planes of up to `n` frames of one H x W shape (wt_batch64): _BatchBase's operations for the
     stacks the reference computes in float64.  Integer and big-endian frames cross as they are and are widened on
-    the device (device_widens).  It has none of the operations that only the float32 batch has: no wt_batch64 entry
-    stands behind them."""
+    the device (device_widens).  It has none of the operations that only the float32 batch has (richardson_lucy's
+    four are RLBatchPlan64's; no wt_batch64 entry stands behind the others)."""
 
     _prefix, dtype, _real = "wt_batch64_", np.float64, _c.c_double
 
@@ -1297,6 +1311,17 @@ class BatchPlan64(_BatchBase):
         return (None if has_map is None else self._has_map(has_map, nf),)
 
 
+class RLBatchPlan64(BatchPlan64):
+    """A BatchPlan64 with richardson_lucy's operations (wt_batch64_set_psf / _filter2d / _binary / _mrs_update): the
+    calls of BatchPlan under the same names and signatures, in float64.  Its first set_psf makes richardson_lucy's planes
+    - PLANE_SCRATCH(6 .. 10) and PLANE_SCRATCH(16 + s) - planes of the batch."""
+
+    set_psf = BatchPlan.set_psf
+    filter2d = BatchPlan.filter2d
+    binary = BatchPlan.binary
+    mrs_update = BatchPlan.mrs_update
+
+
 _batch_cache = {}        # id(ctx) -> [BatchPlan / BatchPlan64], most recently used last (its own small cache: not the plan pool)
 _BATCH_CACHE_MAX = 2
 
@@ -1310,6 +1335,12 @@ def acquire_batch64(ctx, n, H, W, family, max_level):
     """A BatchPlan64 of at least `n` frames of (H, W, family, max_level) on `ctx`: cached if available, else new
     (the cache of acquire_batch; release with release_batch64)."""
     return _acquire(BatchPlan64, ctx, n, H, W, family, max_level)
+
+
+def acquire_rl_batch64(ctx, n, H, W, family, max_level):
+    """An RLBatchPlan64 of at least `n` frames of (H, W, family, max_level) on `ctx`: cached if available, else new (the
+    cache of acquire_batch, which keeps the classes apart; release with release_rl_batch64)."""
+    return _acquire(RLBatchPlan64, ctx, n, H, W, family, max_level)
 
 
 def _acquire(cls, ctx, n, H, W, family, max_level):
@@ -1341,7 +1372,7 @@ def release_batch(b):
             lst.pop(0).close()
 
 
-release_batch64 = release_batch          # (one cache for both kinds of batch)
+release_batch64 = release_rl_batch64 = release_batch          # (one cache for every kind of batch)
 
 
 # ------------------------------------------------------------------------------------------

@@ -18,7 +18,8 @@ run on the float64 batch (wt_batch64).  transform_stack and denoise_stack take i
 bilateral= behind the batched float64 march under bilateral64_eligible.  wow_stack takes the same batch under
 wow64_eligible: the transform's scales beyond the fused passes and the fused update of every scale run on the batched
 float64 per-scale stencil, one launch per scale for all frames; the moments, the medians and the gamma range of all
-frames come back in one host round trip each.
+frames come back in one host round trip each.  richardson_lucy_stack takes it under rl64_eligible: the float32 chunk
+loop in doubles, the PSF correlation of all frames one launch of the tiled float64 kernel (wt_batch64_filter2d).
 
 `noise` may hold per-pixel noise maps (ref wavelets.py:133-141): one (H, W) ndarray shared by the frames, or one entry
 per frame, maps mixed with levels and None.  The maps lie in one more plane of the batch, the noise plane
@@ -41,7 +42,7 @@ from .utils import (richardson_lucy, _rl_check_fft_width, _rl_direct_operands, _
 from .utils import (denoise, wow, enhance, _enhance_lists, _GAMMA_PLANE, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments,
                     _wow_factor, _gamma_range, _wow_sigma_bilateral)
 
-__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'enhance_stack', 'richardson_lucy_stack', 'rl_eligible', 'rl_fft_eligible', 'batch_eligible', 'batch64_eligible',
+__all__ = ['transform_stack', 'denoise_stack', 'wow_stack', 'enhance_stack', 'richardson_lucy_stack', 'rl_eligible', 'rl_fft_eligible', 'rl64_eligible', 'batch_eligible', 'batch64_eligible',
            'wow_eligible', 'wow64_eligible', 'bilateral_eligible', 'bilateral64_eligible', 'enhance_eligible',
            'noise_map_eligible']
 
@@ -874,6 +875,56 @@ def rl_fft_eligible(frames, psf, level, uniform_init=False):
     return _rl_uses_fft(True, H, W, psf.shape[0], psf.shape[1], sides_ok=_lib.batch_fft_ok)
 
 
+# richardson_lucy_stack takes float64 stacks from this many pixels per frame on: WOW64_MIN_PIXELS' number and its
+# reasoning - the per-frame loop is pinned for a 3 x 12 x 16 float64 stack (tests/test_rl_stack_cpu.py), and a frame of
+# a few hundred pixels has nothing for a batch to save.  A condition, not a measured crossover
+# (tools/bench_rl_stack.py --dtype float64 has the measured shapes).
+RL64_MIN_PIXELS = WOW_MAP_MIN_PIXELS
+
+
+def rl64_eligible(frames, psf, level, uniform_init=False, fft=False):
+    """True when the float64 batch (wt_batch64) computes richardson_lucy over this stack (host logic): an (N, H, W)
+    ndarray the reference computes in float64 (_float64_frames: native float64, or int16 / uint16 / int32 / uint32 /
+    int64 / '>f4' / '>f8', widened on the device), level = len(denoise_coefficients) in 2..8 with an all-fused float64
+    schedule for these frames (_lib.batch64_fused_ok), no uniform_init (the reference then keeps the estimate in
+    float32, and the per-frame call leaves the float64 engine), a 2-D numeric PSF whose two operands
+    (utils._rl_direct_operands) the tiled float64 correlation applies in one launch (_lib.batch64_psf_ok: at most
+    4096 taps in rows of at most 512, an LDS tile of doubles of at most 96 KB), and frames of at least RL64_MIN_PIXELS
+    pixels.  With fft=True also rl_eligible's direct-periodic clauses: kh * kw < utils._FFT_MIN_TAPS, kh <= H,
+    kw <= W.  Everything else - the float64 FFT products among it - runs the per-frame loop."""
+    if not _float64_frames(frames):
+        return False
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level not in BATCH_LEVELS:
+        return False
+    if uniform_init:
+        return False
+    N, H, W = frames.shape
+    if N < 1 or H * W < RL64_MIN_PIXELS or not _lib.batch64_fused_ok(_family_of(B3spline(2)), H, W, int(level)):
+        return False
+    psf = np.asarray(psf)
+    if psf.ndim != 2 or psf.dtype.kind not in "biuf" or psf.size == 0:
+        return False
+    kh, kw = psf.shape
+    if fft and (kh * kw >= _utils._FFT_MIN_TAPS or kh > H or kw > W):
+        return False
+    (fwd_k, _), (bwd_k, _) = _rl_direct_operands(psf, H, fft)
+    return _lib.batch64_psf_ok(*fwd_k.shape) and _lib.batch64_psf_ok(*bwd_k.shape)
+
+
+@contextmanager
+def _rl_batch(f64, n, H, W, family, level):
+    """_batch for richardson_lucy_stack: the float64 batch is the one with richardson_lucy's operations (RLBatchPlan64)"""
+    if not f64:
+        with _batch(False, n, H, W, family, level) as bp:
+            yield bp
+        return
+    bp = _lib.acquire_rl_batch64(_lib.default_context(), n, H, W, family, level)
+    try:
+        yield bp
+    finally:
+        _lib.release_rl_batch64(bp)
+
+
 def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2, 1), threshold_type='soft',
                           uniform_init=False, persistent_mrs=True, fft=False, out=None):
     """(N, H, W): utils.richardson_lucy of every frame with the one PSF `psf` (ref utils.py:222-290), batched -
@@ -887,7 +938,10 @@ def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2
     - nothing returns to the host until the chunk's estimates.  fft=True with a PSF of utils._FFT_MIN_TAPS taps or
     more (rl_fft_eligible stacks): the same chunk loop with the two products through the batched FFT - the spectrum
     of the periodically placed PSF once per call, then six launches per product for all frames of a chunk.
-    Everything else runs the per-frame loop."""
+    Stacks the reference computes in float64 - float64, integer and big-endian frames - take the same chunk loop on
+    the float64 batch (rl64_eligible stacks): double planes, the PSF as doubles, the tiled float64 correlation, a
+    float64 result.  The float64 FFT products (fft=True with a PSF of utils._FFT_MIN_TAPS taps or more) are not
+    batched: they stay on the per-frame loop, as does everything else."""
     fr = _as_frames(frames)
     if np.ndim(psf) != 2:
         raise ValueError("psf must be 2-D")
@@ -895,29 +949,32 @@ def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2
     level = len(denoise_coefficients)
     direct = rl_eligible(fr, psf, level, uniform_init, fft)
     by_fft = not direct and bool(fft) and rl_fft_eligible(fr, psf, level, uniform_init)
+    f64 = not direct and not by_fft and rl64_eligible(fr, psf, level, uniform_init, fft)
+    if f64:
+        direct = True
     if not direct and not by_fft:
         return _hand_over(np.stack([richardson_lucy(f, psf, iterations=iterations, denoise_coefficients=denoise_coefficients,
                                                     threshold_type=threshold_type, uniform_init=uniform_init,
                                                     persistent_mrs=persistent_mrs, fft=fft) for f in fr]), out)
     N, H, W = fr.shape
-    out, _ = _target(False, out, (N, H, W))
+    out, caller_out = _target(f64, out, (N, H, W))
     soft = threshold_type == 'soft'
     sf = B3spline(2)                                                             # ref:229 default transform
     sigma_e = sf.sigma_e()
     DATA, PSI, PHI, RES, CONV = (PLANE_SCRATCH(i) for i in (6, 7, 8, 9, 10))     # (the per-frame call's plane ids)
     MRS = [PLANE_SCRATCH(16 + s) for s in range(level)]
-    psf32 = np.ascontiguousarray(psf, dtype=np.float32)
+    kernel = np.ascontiguousarray(psf, dtype=np.float64 if f64 else np.float32)     # (the per-frame call's cast)
     if direct:
-        (fwd_k, fwd), (bwd_k, bwd) = _rl_direct_operands(psf32, H, fft)
+        (fwd_k, fwd), (bwd_k, bwd) = _rl_direct_operands(kernel, H, fft)
     # Coefficients._denoise_sum(list(denoise_coefficients)): the (scale, sigma, weight) entries of the initial estimate
     entries = list(zip(range(level + 1), denoise_coefficients, (1,) * level))
-    chunks = _plan_chunks(N, H, W, level, False, (_rl_extra_planes if direct else _rl_fft_extra_planes)(level))
-    with _batch(False, max(nf for _, nf in chunks), H, W, _family_of(sf), level) as bp:
+    chunks = _plan_chunks(N, H, W, level, f64, (_rl_extra_planes if direct else _rl_fft_extra_planes)(level))
+    with _rl_batch(f64, max(nf for _, nf in chunks), H, W, _family_of(sf), level) as bp:
         if direct:
             bp.set_psf(0, fwd_k)
             bp.set_psf(1, bwd_k)
         else:                                                                    # ref:246-251, once for every chunk
-            bp.upload(CONV, _rl_fft_kernel_image(psf32, H, W)[None])
+            bp.upload(CONV, _rl_fft_kernel_image(kernel, H, W)[None])
             bp.fft_spectrum(CONV)
         for f0, nf in chunks:
             bp.upload(DATA, fr[f0:f0 + nf])
@@ -949,4 +1006,4 @@ def richardson_lucy_stack(frames, psf, iterations=10, denoise_coefficients=(5, 2
                     bp.fft_apply(nf, RES, CONV, True)                            # ref:284
                 bp.binary(nf, "mul", PSI, CONV, PSI)                             # ref:288
             bp.download(PSI, nf, out=out[f0:f0 + nf])
-    return out
+    return out if caller_out is None else _hand_over(out, caller_out)

@@ -16,6 +16,10 @@
 // batched per-scale stencil for their single-scale passes, the fused update of a scale is ONE launch of that stencil
 // for all frames (wt_stencil64_batch.hip), and the pointwise update, the gamma blend, the moments and the plane sum
 // are the per-frame kernels' texts (wt_wow64.h) with the frame as a grid dimension.
+// richardson_lucy (watroo/utils.py:222-290) runs on the same planes plus its own (data, psi, phi, residual,
+// correlation, one support plane per scale): the PSF correlation of all frames is ONE launch of the tiled kernel
+// (wt_batch64_filter2d_kernel: wt_rl_point.h's 64 x 16 tile staged in LDS as doubles, the two operands resident in
+// the batch), the binary ops run once over the frames as a flat range, the support update has the frame as grid y.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -23,6 +27,7 @@
 #include "wt_batch_core.h"
 #include "wt_math64.h"
 #include "wt_reduce.h"
+#include "wt_rl_point.h"
 #include "wt_wow64.h"
 #include "wt_unit_probe.h"
 
@@ -42,6 +47,15 @@ struct wt_batch64 : WtBatchCore<double> {
     uint32_t *d_hist = nullptr;     // [n][2 ranks][WT_HIST_BINS] (allocated by the first median)
     WtBatch64Sel *d_sel = nullptr;  // [n][2 ranks]
     WtBatch64Sel *h_sel = nullptr;  // pinned copy
+    // richardson_lucy: WT_PLANE_SCRATCH(6 .. 10) = data, psi, phi, residual, correlation; WT_PLANE_SCRATCH(16 + s) = the
+    // support plane of scale s (utils.richardson_lucy's plane ids); the forward / backward PSF of wt_batch64_set_psf.
+    // The planes belong to a batch from its first wt_batch64_set_psf on (extra_plane): a batch without a PSF keeps
+    // the plane list every other stack function sees.
+    double *rl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    std::vector<double *> mrs;      // max_level entries
+    double *d_psf[2] = {nullptr, nullptr};
+    size_t psf_cap[2] = {0, 0};
+    int psf_kh[2] = {0, 0}, psf_kw[2] = {0, 0};
     // (d_tau: [n][3 * WT_MAX_SUM_PLANES], the thresholds of wt_batch64_denoise_sum, then 1 / tau; wt_batch64_enhance_sum: then the weights)
 };
 
@@ -328,7 +342,73 @@ __global__ __launch_bounds__(256) void wt_batch64_plane_sum_kernel(Sum64Args a, 
     wt64_plane_sum_groups(a, dst, n2);
 }
 
+// wt64_filter2d_kernel (wt_kernels_f64.h) for the frames of a batch, tiled: grid z = the frame, each its own image
+// (the border rules act at the frame's borders).  Staging, tile geometry and tap loop are wt_rl_point.h's with
+// T = double - the (64 + kw - 1) x (16 + kh - 1) window of a 64 x 16 output tile in dynamic LDS, four output rows per
+// thread, taps as wave-uniform loads from the batch's device copy.  Every output is the chain
+// acc = fma(psf[i * kw + j], v, acc) from 0.0, i outer, j inner, over the same samples (wt_refl / a true modulo
+// pick the sample the per-frame kernel reads): the bits of wt64_filter2d on that frame.
+template <bool WRAP>
+__global__ __launch_bounds__(256) void wt_batch64_filter2d_kernel(const double *in, double *out, Geo g, int64_t fstride,
+                                                                  const double *__restrict__ psf, int kh, int kw, int ay, int ax)
+{
+    extern __shared__ double tile64[];
+    in += (int64_t)blockIdx.z * fstride;
+    out += (int64_t)blockIdx.z * fstride;
+    const int tw = WT_F2D_TW + kw - 1, th = WT_F2D_TH + kh - 1;
+    const int x0 = blockIdx.x * WT_F2D_TW, ly0 = blockIdx.y * WT_F2D_TH;
+    wt_f2d_stage<WRAP>(tile64, in, g, x0, ly0, tw, th, ay, ax);
+    __syncthreads();
+    const int x = x0 + threadIdx.x;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    wt_f2d_taps(tile64, tw, psf, kw, kh, kw, acc);
+    if (x < g.W) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ly = ly0 + threadIdx.y * 4 + r;
+            if (ly < g.H) out[(int64_t)ly * g.P + x] = acc[r];
+        }
+    }
+}
+
+// wt64_binary_kernel (wt_kernels_f64.h) over the active frames, one flat range of 16-byte groups (wt64_binary_point;
+// op in wt64_binary's numbering)
+__global__ __launch_bounds__(256) void wt_batch64_binary_kernel(const double *a, const double *b, double *dst, int64_t n2, int op)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (int64_t)gridDim.x * 256) {
+        const double2 u = reinterpret_cast<const double2 *>(a)[i], v = reinterpret_cast<const double2 *>(b)[i];
+        reinterpret_cast<double2 *>(dst)[i] = make_double2(wt64_binary_point(u.x, v.x, op), wt64_binary_point(u.y, v.y, op));
+    }
+}
+
+// wt64_mrs_kernel (wt_kernels_f64.h) with the frame as grid y and its own tau (ptab[2 * f]; <= 0: significance one);
+// no noise map - richardson_lucy's noise is the data's MAD estimate.  Same wt64_mrs_point: the bits of the per-frame call.
+__global__ __launch_bounds__(256) void wt_batch64_mrs_kernel(double *c, double *mrs, int64_t f2, const double *ptab, int soft, int persistent,
+                                                             double inv_pow)
+{
+    const int f = blockIdx.y;
+    const double tau = ptab[2 * f];
+    double2 *cf = reinterpret_cast<double2 *>(c) + (int64_t)f * f2;
+    double2 *mf = reinterpret_cast<double2 *>(mrs) + (int64_t)f * f2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < f2; i += (int64_t)gridDim.x * 256) {
+        double2 v = cf[i], m = mf[i];
+        wt64_mrs_point(v.x, m.x, tau, tau, soft, persistent, inv_pow);
+        wt64_mrs_point(v.y, m.y, tau, tau, soft, persistent, inv_pow);
+        cf[i] = v;
+        mf[i] = m;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host
+// richardson_lucy's planes (WtBatchCore::extra_plane, set by the first wt_batch64_set_psf)
+static double **batch64_rl_plane(WtBatchCore<double> *core, int id)
+{
+    wt_batch64 *b = static_cast<wt_batch64 *>(core);
+    if (id <= WT_PLANE_SCRATCH(6) && id >= WT_PLANE_SCRATCH(10)) return &b->rl[WT_PLANE_SCRATCH(6) - id];
+    if (id <= WT_PLANE_SCRATCH(16) && id > WT_PLANE_SCRATCH(16) - (int)b->mrs.size()) return &b->mrs[WT_PLANE_SCRATCH(16) - id];
+    return nullptr;
+}
+
 // fused64_ok (wt_f64.h) for one frame of this shape: an image (H >= 2) whose rows the fused passes take at 8 bytes
 // per pixel and whose float64 schedule of `level` scales is fused passes only
 static bool batch64_all_fused(int family, int64_t H, int64_t W, int level, int32_t *tr, int *np)
@@ -424,6 +504,10 @@ static void batch64_free(wt_batch64 *b, int *bad)
     f(b->istage);
     f(b->d_hist);
     f(b->d_sel);
+    for (double *q : b->rl) f(q);
+    for (double *q : b->mrs) f(q);
+    f(b->d_psf[0]);
+    f(b->d_psf[1]);
     if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) *bad = 1;
 }
 
@@ -435,6 +519,7 @@ extern "C" int wt_batch64_create(wt_ctx *ctx, int n, int H, int W, int family, i
     if (!wt_fused_supported_bytes((int64_t)(W + 1) / 2 * 2 * 8)) WT_FAIL("wt_batch64_create: rows of %d pixels are too wide for the fused float64 passes", W);
     wt_batch64 *b = new wt_batch64;
     batch_init(b, ctx, n, H, W, (W + 1) / 2 * 2, family, max_level);
+    b->mrs.assign(std::min(max_level, WT_NUM_SCRATCH - 16), nullptr);
     // the geometry and taps a wt_plan64 of this shape has (wt64_plan_create)
     static const double b3[5] = {1. / 16, 1. / 4, 3. / 8, 1. / 4, 1. / 16}, tri[3] = {1. / 4, 1. / 2, 1. / 4};
     b->geo.ctx = ctx;
@@ -932,6 +1017,123 @@ extern "C" int wt_batch64_plane_sum(wt_batch64 *b, int nf, int first, int count,
     const int64_t n2 = (int64_t)nf * b->fstride / 2;
     ProfScope ps(b->ctx, "wt_batch64_plane_sum_kernel");
     hipLaunchKernelGGL(wt_batch64_plane_sum_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, b->ctx->stream, a, o, n2);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ richardson_lucy
+// host logic: *ok = 1 when wt_batch64_set_psf takes a kh x kw PSF - wt_batch64_filter2d applies it in ONE launch
+extern "C" int wt_batch64_psf_ok(int kh, int kw, int *ok)
+{
+    if (!ok) WT_FAIL("wt_batch64_psf_ok: null pointer");
+    *ok = wt64_f2d_single_launch(kh, kw) ? 1 : 0;
+    return 0;
+}
+
+// One of the two PSF operands of a richardson_lucy call (slot 0: forward, watroo/utils.py:257; slot 1: backward,
+// utils.py:286) -> device memory of the batch, once per call: the iterations then correlate without a stream drain
+// and without a PSF copy (wt64_filter2d does both on every call - its kernel comes from caller-owned memory).
+// The first PSF makes richardson_lucy's planes planes of this batch.
+extern "C" int wt_batch64_set_psf(wt_batch64 *b, int slot, const double *kernel, int kh, int kw)
+{
+    if (!b || !kernel) WT_FAIL("wt_batch64_set_psf: null pointer");
+    WtGuard guard_(b->ctx);
+    if (slot < 0 || slot > 1) WT_FAIL("wt_batch64_set_psf: slot %d (0: forward, 1: backward)", slot);
+    if (!wt64_f2d_single_launch(kh, kw))
+        WT_FAIL("wt_batch64_set_psf: a %d x %d PSF is not applied in one launch (at most %d taps, rows of at most %d, an LDS tile of at most %d KB)",
+                kh, kw, WT_F2D_MAX_TAPS, WT_F2D_MAX_KW, WT_F2D_MAX_LDS / 1024);
+    const size_t ntaps = (size_t)kh * kw;
+    // a launch on the stream may still read the slot, and `kernel` is the caller's: drain, then copy synchronously
+    WT_HIP(hipStreamSynchronize(b->ctx->stream));
+    if (ntaps > b->psf_cap[slot]) {
+        (void)hipFree(b->d_psf[slot]);
+        b->d_psf[slot] = nullptr;
+        b->psf_cap[slot] = 0;
+        b->psf_kh[slot] = b->psf_kw[slot] = 0;
+        WT_HIP(hipMalloc((void **)&b->d_psf[slot], ntaps * sizeof(double)));
+        b->psf_cap[slot] = ntaps;
+    }
+    WT_HIP(hipMemcpy(b->d_psf[slot], kernel, ntaps * sizeof(double), hipMemcpyHostToDevice));
+    b->psf_kh[slot] = kh;
+    b->psf_kw[slot] = kw;
+    if (!b->extra_plane) {
+        b->extra_plane = batch64_rl_plane;
+        b->extra_planes = ", 6..10, 16.." + std::to_string(15 + (int)b->mrs.size());
+    }
+    return 0;
+}
+
+// wt64_filter2d per frame (watroo/utils.py:257,286; periodic: the circular products of utils.py:245-254,284) with
+// the PSF of `slot`: one launch of the tiled kernel for all active frames
+extern "C" int wt_batch64_filter2d(wt_batch64 *b, int nf, int src, int dst, int slot, int ay, int ax, int border)
+{
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_filter2d"));
+    WtGuard guard_(b->ctx);
+    if (slot < 0 || slot > 1 || !b->d_psf[slot] || !b->psf_kh[slot]) WT_FAIL("wt_batch64_filter2d: PSF slot %d is not set (wt_batch64_set_psf)", slot);
+    const int kh = b->psf_kh[slot], kw = b->psf_kw[slot];
+    if (!wt64_f2d_single_launch(kh, kw)) WT_FAIL("wt_batch64_filter2d: a %d x %d PSF is not applied in one launch", kh, kw);
+    if (ay < 0 || ay >= kh || ax < 0 || ax >= kw) WT_FAIL("wt_batch64_filter2d: anchor (%d, %d) outside the %d x %d kernel", ay, ax, kh, kw);
+    if (src == dst) WT_FAIL("wt_batch64_filter2d: src and dst must differ");
+    if (border != WT_BORDER_SYMMETRIC && border != WT_BORDER_PERIODIC) WT_FAIL("wt_batch64_filter2d: border %d unsupported (symmetric or periodic)", border);
+    const Geo &g = b->geo.g;
+    dim3 grid((g.W + WT_F2D_TW - 1) / WT_F2D_TW, (g.H + WT_F2D_TH - 1) / WT_F2D_TH, nf), block(64, 4);
+    if (grid.y > 65535u) WT_FAIL("wt_batch64_filter2d: frames of %d rows are too tall (%u row tiles, at most 65535)", g.H, grid.y);
+    if (grid.z > 65535u) WT_FAIL("wt_batch64_filter2d: %d frames in one launch (at most 65535)", nf);
+    double *in = nullptr, *o = nullptr;
+    WT_TRY(batch_plane(b, src, &in));
+    WT_TRY(batch_plane(b, dst, &o));
+    const size_t lds = wt_f2d_lds_bytes(kh, kw, sizeof(double));
+    ProfScope ps(b->ctx, "wt_batch64_filter2d_kernel");
+    #define WT_B64F2D_LAUNCH(WRAP)                                                                                                   \
+        do {                                                                                                                         \
+            if (lds > 64 * 1024)                                                                                                     \
+                WT_HIP(hipFuncSetAttribute((const void *)wt_batch64_filter2d_kernel<WRAP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            hipLaunchKernelGGL((wt_batch64_filter2d_kernel<WRAP>), grid, block, lds, b->ctx->stream, (const double *)in, o, g, b->fstride, \
+                               (const double *)b->d_psf[slot], kh, kw, ay, ax);                                                      \
+        } while (0)
+    if (border == WT_BORDER_PERIODIC) WT_B64F2D_LAUNCH(true);
+    else WT_B64F2D_LAUNCH(false);
+    #undef WT_B64F2D_LAUNCH
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+// wt64_binary over the active frames (watroo/utils.py:259,280-281,288); op: wt_batch_binary's numbering (WT_OP_*)
+extern "C" int wt_batch64_binary(wt_batch64 *b, int nf, int op, int a, int b2, int dst)
+{
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_binary"));
+    WtGuard guard_(b->ctx);
+    if (op < 0 || op > WT_OP_ADD_DIV) WT_FAIL("wt_batch64_binary: unknown op %d", op);
+    double *pa = nullptr, *pb = nullptr, *pd = nullptr;
+    WT_TRY(batch_plane(b, a, &pa));
+    WT_TRY(batch_plane(b, b2, &pb));
+    WT_TRY(batch_plane(b, dst, &pd));
+    const int op64 = op == WT_OP_SUB ? 1 : op == WT_OP_ADD ? 0 : op;      // (wt64_binary counts add, sub, ...)
+    const int64_t n2 = (int64_t)nf * b->fstride / 2;
+    ProfScope ps(b->ctx, "wt_batch64_binary_kernel");
+    hipLaunchKernelGGL(wt_batch64_binary_kernel, batch64_flat_grid(n2), dim3(256), 0, b->ctx->stream, (const double *)pa, (const double *)pb, pd, n2, op64);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+// wt64_mrs_update per frame (watroo/utils.py:263-276) with the frame's tau[f]; scalar noise only
+extern "C" int wt_batch64_mrs_update(wt_batch64 *b, int nf, int plane, int mrs_plane, const double *tau, int soft, int persistent, double inv_pow)
+{
+    WT_TRY(batch_check_frames(b, nf, "wt_batch64_mrs_update"));
+    WtGuard guard_(b->ctx);
+    if (!tau) WT_FAIL("wt_batch64_mrs_update: null tau");
+    if (plane == mrs_plane) WT_FAIL("wt_batch64_mrs_update: plane and mrs_plane must differ");
+    double *c = nullptr, *m = nullptr;
+    WT_TRY(batch_plane(b, plane, &c));
+    WT_TRY(batch_plane(b, mrs_plane, &m));
+    std::vector<double> pairs((size_t)nf * 2, 0.0);
+    for (int f = 0; f < nf; ++f) pairs[2 * f] = tau[f];
+    const double *dt = nullptr;
+    WT_TRY(batch_table(b, nf, pairs.data(), &dt));
+    const int64_t f2 = b->fstride / 2;
+    const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((f2 + 255) / 256, (2048 + nf - 1) / nf));
+    ProfScope ps(b->ctx, "wt_batch64_mrs_kernel");
+    hipLaunchKernelGGL(wt_batch64_mrs_kernel, dim3(bx, nf), dim3(256), 0, b->ctx->stream, c, m, f2, dt, soft, persistent, inv_pow);
     WT_HIP(hipGetLastError());
     return 0;
 }

@@ -11,6 +11,7 @@
 #include "wt_device.h"
 #include "wt_math64.h"
 #include "wt_kernels_common.h"
+#include "wt_rl_point.h"   // the pointwise arithmetic of richardson_lucy shared with the batched forms (wt_batch64.hip)
 #include "wt_wow64.h"      // wt_ntd2; the pieces of wow shared with the batched forms (wt_batch64.hip)
 
 struct Taps64 {
@@ -229,8 +230,7 @@ __global__ __launch_bounds__(256) void wt64_binary_kernel(const double *a, const
     if (x >= W) return;
     for (int y = blockIdx.y; y < nrows; y += gridDim.y) {
         const int64_t o = (int64_t)y * P + x;
-        const double u = a[o], v = b[o];
-        dst[o] = op == 0 ? u + v : op == 1 ? u - v : op == 2 ? u * v : op == 3 ? u / v : (u + v) / v;
+        dst[o] = wt64_binary_point(a[o], b[o], op);
     }
 }
 
@@ -382,21 +382,10 @@ __global__ __launch_bounds__(256) void wt64_mrs_kernel(double *c, double *mrs, c
     if (x >= W) return;
     for (int y = blockIdx.y; y < nrows; y += gridDim.y) {
         const int64_t o = (int64_t)y * P + x;
-        const double v = c[o];
-        double sg = 1.0;
-        if (tau > 0.0) {
-            const double tt = noise ? tau * noise[o] : tau;
-            sg = wt_sig64(v, tt, soft);
-        }
-        double m = mrs[o];
-        if (soft) {
-            m = persistent ? m * sg : sg;
-            c[o] = v * pow(m, inv_pow);
-        } else {
-            m = persistent ? fmax(m, sg) : sg;
-            c[o] = v * m;
-        }
-        mrs[o] = m;
+        double cc = c[o], mm = mrs[o];
+        wt64_mrs_point(cc, mm, tau, noise && tau > 0.0 ? tau * noise[o] : tau, soft, persistent, inv_pow);
+        c[o] = cc;
+        mrs[o] = mm;
     }
 }
 

@@ -19,13 +19,19 @@
 #define WT_F2D_MAX_TAPS 4096
 #define WT_F2D_MAX_KW 512
 #define WT_F2D_MAX_LDS (96 * 1024)
-static inline size_t wt_f2d_lds_bytes(int kh, int kw)
+// (elem: bytes of a staged sample - floats, or the doubles of wt_batch64_filter2d_kernel)
+static inline size_t wt_f2d_lds_bytes(int kh, int kw, size_t elem = sizeof(float))
 {
-    return (size_t)(WT_F2D_TW + kw - 1) * (WT_F2D_TH + kh - 1) * sizeof(float);
+    return (size_t)(WT_F2D_TW + kw - 1) * (WT_F2D_TH + kh - 1) * elem;
 }
-static inline bool wt_f2d_single_launch(int kh, int kw)
+static inline bool wt_f2d_single_launch(int kh, int kw, size_t elem = sizeof(float))
 {
-    return kh >= 1 && kw >= 1 && kw <= WT_F2D_MAX_KW && (int64_t)kh * kw <= WT_F2D_MAX_TAPS && wt_f2d_lds_bytes(kh, kw) <= WT_F2D_MAX_LDS;
+    return kh >= 1 && kw >= 1 && kw <= WT_F2D_MAX_KW && (int64_t)kh * kw <= WT_F2D_MAX_TAPS && wt_f2d_lds_bytes(kh, kw, elem) <= WT_F2D_MAX_LDS;
+}
+// the same rule with the tile staged as doubles: the same tile geometry at twice the bytes (wt_batch64_psf_ok)
+static inline bool wt64_f2d_single_launch(int kh, int kw)
+{
+    return wt_f2d_single_launch(kh, kw, sizeof(double));
 }
 
 // WRAP: periodic border (the circular convolution of the reference's rFFT path,
@@ -37,32 +43,36 @@ __device__ __forceinline__ int wt_wrap(int i, int n)
 }
 
 // the (WT_F2D_TW + kw - 1) x (WT_F2D_TH + kh - 1) input window of the output tile at (x0, local row ly0) -> LDS,
-// by the 256 threads of the block
-template <bool WRAP>
-__device__ __forceinline__ void wt_f2d_stage(float *tile, const float *in, const Geo &g, int x0, int ly0, int tw, int th, int ay, int ax)
+// by the 256 threads of the block (T: float, or double for the float64 batch)
+template <bool WRAP, typename T>
+__device__ __forceinline__ void wt_f2d_stage(T *tile, const T *in, const Geo &g, int x0, int ly0, int tw, int th, int ay, int ax)
 {
     const int tid = threadIdx.y * 64 + threadIdx.x;
     for (int i = tid; i < tw * th; i += 256) {
         const int ty = i / tw, tx = i - ty * tw;
         if (WRAP) {
-            const float *row = in + (int64_t)wt_wrap(ly0 + ty - ay, g.H) * g.P;
+            const T *row = in + (int64_t)wt_wrap(ly0 + ty - ay, g.H) * g.P;
             tile[i] = row[wt_wrap(x0 + tx - ax, g.W)];
         } else {
-            const float *row = wt_row(in, g, g.row0 + ly0 + ty - ay);
+            const T *row = wt_row(in, g, g.row0 + ly0 + ty - ay);
             tile[i] = row[wt_refl(x0 + tx - ax, g.W)];
         }
     }
 }
 
 // the four output rows threadIdx.y * 4 + r of column threadIdx.x: acc[r] = fmaf(k[i][j], v, acc[r]), i outer, j inner
-__device__ __forceinline__ void wt_f2d_taps(const float *tile, int tw, const float *psf, int psf_pitch, int kh, int kw, float acc[4])
+// (T = double: fma, the chain of wt64_filter2d_kernel)
+__device__ __forceinline__ float wt_f2d_fma(float k, float v, float acc) { return fmaf(k, v, acc); }
+__device__ __forceinline__ double wt_f2d_fma(double k, double v, double acc) { return fma(k, v, acc); }
+template <typename T>
+__device__ __forceinline__ void wt_f2d_taps(const T *tile, int tw, const T *psf, int psf_pitch, int kh, int kw, T acc[4])
 {
     for (int i = 0; i < kh; ++i)
         for (int j = 0; j < kw; ++j) {
-            const float k = psf[i * psf_pitch + j];
+            const T k = psf[i * psf_pitch + j];
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                acc[r] = fmaf(k, tile[(threadIdx.y * 4 + r + i) * tw + threadIdx.x + j], acc[r]);
+                acc[r] = wt_f2d_fma(k, tile[(threadIdx.y * 4 + r + i) * tw + threadIdx.x + j], acc[r]);
         }
 }
 
@@ -117,6 +127,13 @@ __device__ __forceinline__ float4 wt_binary_point4(float4 u, float4 v, int op)
     return make_float4(o[0], o[1], o[2], o[3]);
 }
 
+// ... and of the float64 engine (wt64_binary_kernel, wt_batch64_binary_kernel); op in wt64_binary's numbering:
+// 0 add, 1 sub, 2 mul, 3 div, 4 (u + v) / v
+__device__ __forceinline__ double wt64_binary_point(double u, double v, int op)
+{
+    return op == 0 ? u + v : op == 1 ? u - v : op == 2 ? u * v : op == 3 ? u / v : (u + v) / v;
+}
+
 // multiresolution-support update of one residual value (watroo/utils.py:263-276):
 //   sig = significance(c);  hard: mrs = persistent ? max(mrs, sig) : sig ;  c *= mrs
 //                           soft: mrs = persistent ? mrs * sig   : sig ;  c *= mrs ** inv_pow
@@ -130,4 +147,22 @@ __device__ __forceinline__ void wt_mrs_point(float &cc, float &mm, float nn, dou
         mm = persistent ? fmaxf(mm, sg) : sg;
         cc = cc * mm;
     }
+}
+
+// ... in float64 (wt64_mrs_kernel, wt_batch64_mrs_kernel): tt = the threshold of this sample (tau, or tau * its noise);
+// the significance is the quotient form wt_sig64 (wt_sig64_inv differs by a rounding)
+__device__ __forceinline__ void wt64_mrs_point(double &cc, double &mm, double tau, double tt, int soft, int persistent, double inv_pow)
+{
+    const double v = cc;
+    double sg = 1.0;
+    if (tau > 0.0) sg = wt_sig64(v, tt, soft);
+    double m = mm;
+    if (soft) {
+        m = persistent ? m * sg : sg;
+        cc = v * pow(m, inv_pow);
+    } else {
+        m = persistent ? fmax(m, sg) : sg;
+        cc = v * m;
+    }
+    mm = m;
 }
