@@ -848,6 +848,44 @@ int wt_batch64_binary(wt_batch64 *batch, int nf, int op, int a, int b, int dst);
 int wt_batch64_mrs_update(wt_batch64 *batch, int nf, int plane, int mrs_plane, const double *tau, int soft,
                           int persistent, double inv_pow);
 
+/* ---- stacks of 1-D signals of one length (wt_signals) ------------------------------------------------------------
+ * M signals of N samples, float or double: one workgroup per signal, the scales of a signal in LDS, every plane
+ * written once.  The reference transforms a signal in the 1-D branch of convolution() (watroo/wavelets.py:65-69,
+ * scipy's 'mirror' border) under atrous_standard (:408-444); every signal gets the bits of the per-signal call
+ * (wt_decompose / wt64_decompose on a 1 x N plan under wt_plan_set_border(2)).  Operations take the number of active
+ * signals `count` (signals 0 .. count-1); transfers address signals [first, first + count). */
+typedef struct wt_signals wt_signals;
+/* host logic, no GPU needed: 1 when signals of n_samples samples of `itemsize` bytes (4: float, 8: double) of
+ * `family` over `level` scales (watroo/wavelets.py:426-444) run on a wt_signals, else 0: a built-in family, 1 .. 24
+ * scales, and the two LDS buffers of a signal within 64 KiB - n_samples <= 8192 floats, <= 4096 doubles */
+int wt_signals_ok(int family, int64_t n_samples, int level, int itemsize);
+/* device memory for n_signals signals of n_samples samples (wt_signals_ok) and transforms of up to max_level scales:
+ * the signals, max_level + 1 planes and one sum per signal (watroo/wavelets.py:426-427) */
+int wt_signals_create(wt_ctx *ctx, int n_signals, int n_samples, int family, int max_level, int itemsize,
+                      wt_signals **out);
+int wt_signals_destroy(wt_signals *signals);
+/* info[6] = {n_signals, n_samples, pitch in elements, family, max_level, itemsize} */
+int wt_signals_info(wt_signals *signals, int64_t *info);
+/* signals [first, first + count) <- `count` rows of n_samples contiguous elements (the arr of watroo/wavelets.py:307);
+ * the block is free when the call returns */
+int wt_signals_upload(wt_signals *signals, int first, int count, const void *host);
+/* AtrousTransform.atrous_standard of signals 0 .. count-1 over `level` scales (watroo/wavelets.py:408-444 over
+ * :65-69): one launch; HBM traffic sizeof(element) * (level + 2) bytes per sample */
+int wt_signals_decompose(wt_signals *signals, int count, int level);
+/* np.median(np.abs(w_0)) of signals 0 .. count-1 (Coefficients.get_noise, watroo/wavelets.py:126-127), exact and
+ * with the even / odd rule of wt_abs_median: medians[count] of the stack's element type, one host round trip */
+int wt_signals_abs_median(wt_signals *signals, int count, void *medians);
+/* Coefficients.denoise + np.sum(coefficients, axis=0) of signals 0 .. count-1 (watroo/wavelets.py:145-149,
+ * utils.py:97-98; wt_denoise_sum / wt64_denoise_sum per signal, planes left as they are): tau[count * n_den] and
+ * wgt[count * n_den], one row per signal; tau <= 0: significance one.  At most 16 planes (level <= 15) */
+int wt_signals_denoise_sum(wt_signals *signals, int count, int n_den, const double *tau, const double *wgt,
+                           int soft);
+/* the planes of signals [first, first + count) of the last wt_signals_decompose -> host (count, level + 1, n_samples)
+ * (Coefficients.data per signal, watroo/wavelets.py:426-444) */
+int wt_signals_download_planes(wt_signals *signals, int first, int count, void *host);
+/* the sums of wt_signals_denoise_sum of signals [first, first + count) -> host (count, n_samples) (utils.py:98) */
+int wt_signals_download_sum(wt_signals *signals, int first, int count, void *host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ from .utils import *  # noqa: F401,F403
 from .sequence import map_frames, denoise_many, wow_many, transform_many  # noqa: F401  (sequences of frames: double-buffered over PCIe)
 
 from .batch import transform_stack, denoise_stack, wow_stack, enhance_stack, richardson_lucy_stack  # noqa: F401  (stacks of same-shape frames: one launch per pass)
+from .signals import transform_signals, denoise_signals, signals_eligible  # noqa: F401  (stacks of 1-D signals of one length: a workgroup per signal, the scales in LDS)
 from .rng import normal_frames  # noqa: F401  (seeded standard-normal frames, filled on the GPU)
 
 __version__ = '0.1.0'

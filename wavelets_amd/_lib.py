@@ -289,6 +289,18 @@ SIGNATURES = {
     "wt_batch64_binary": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "wt_batch64_mrs_update": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int, _c.c_int,
                                          _c.c_double]),
+    # stacks of 1-D signals of one length (wt_signals)
+    "wt_signals_ok": (_c.c_int, [_c.c_int, _i64, _c.c_int, _c.c_int]),
+    "wt_signals_create": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_vp)]),
+    "wt_signals_destroy": (_c.c_int, [_vp]),
+    "wt_signals_info": (_c.c_int, [_vp, _c.POINTER(_i64)]),
+    "wt_signals_upload": (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp]),
+    "wt_signals_decompose": (_c.c_int, [_vp, _c.c_int, _c.c_int]),
+    "wt_signals_abs_median": (_c.c_int, [_vp, _c.c_int, _vp]),
+    "wt_signals_denoise_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
+                                          _c.c_int]),
+    "wt_signals_download_planes": (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp]),
+    "wt_signals_download_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp]),
 }
 
 _lib = None
@@ -469,7 +481,7 @@ def _shutdown():
     otherwise destroys planes after the runtime's own static destructors ran)."""
     _host_pool.close()
     objs = list(_live)
-    for kind in ((Plan, Plan64, BatchPlan, BatchPlan64), (Context,)):
+    for kind in ((Plan, Plan64, BatchPlan, BatchPlan64, SignalBatch), (Context,)):
         for o in objs:
             if isinstance(o, kind):
                 try:
@@ -480,6 +492,7 @@ def _shutdown():
     _lane_ctx.clear()
     del _pool[:]
     _batch_cache.clear()
+    _signal_cache.clear()
 
 
 _tls = threading.local()          # .ctx: the context the API calls of THIS thread run on (use_context)
@@ -1373,6 +1386,140 @@ def release_batch(b):
 
 
 release_batch64 = release_rl_batch64 = release_batch          # (one cache for every kind of batch)
+
+
+# ------------------------------------------------------------------------------------------
+# stacks of 1-D signals of one length (wt_signals): one workgroup per signal, the scales in LDS
+# ------------------------------------------------------------------------------------------
+SIGNAL_MAX_LEVEL = 24                     # wt_signals_ok: the per-scale kernels' limit
+
+
+def signals_ok(family, n_samples, level, itemsize):
+    """True when signals of `n_samples` samples of `itemsize` bytes of `family` over `level` scales run on a
+    SignalBatch (host logic, wt_signals_ok): a built-in family, 1..24 scales, the two LDS buffers of a signal within
+    64 KiB - at most 8192 float32 or 4096 float64 samples"""
+    if not isinstance(family, int):
+        return False
+    return bool(load().wt_signals_ok(int(family), int(n_samples), int(level), int(itemsize)))
+
+
+def signal_bytes(n_samples, level, itemsize=4):
+    """device bytes one signal of a SignalBatch takes: the signal, planes 0..level and the sum, at the 16-byte pitch
+    (host logic, wt_signals_create)"""
+    return (level + 3) * _batch_pitch(n_samples, itemsize) * itemsize
+
+
+def signal_chunks(n, n_samples, level, budget=None, itemsize=4):
+    """[(first signal, signals)] of a stack of `n` signals, in the manner of batch_chunks: as many signals per chunk
+    as `budget` bytes of device memory allow (default BATCH_BYTES; at least one), the last chunk the remainder"""
+    if n < 0:
+        raise ValueError("negative signal count")
+    budget = BATCH_BYTES if budget is None else budget
+    per = max(1, min(int(budget // signal_bytes(n_samples, level, itemsize)), (1 << 31) - 1))
+    return [(f0, min(per, n - f0)) for f0 in range(0, n, per)]
+
+
+class SignalBatch:
+    """Device memory of up to `n` signals of `n_samples` samples, float32 or float64 (wt_signals).  Operations take the
+    number of active signals `nf` (signals 0 .. nf-1); upload / download move C-contiguous blocks of signals."""
+
+    def __init__(self, ctx, n, n_samples, family, max_level, dtype=np.float32):
+        self._h = _vp()
+        self.ctx = ctx
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"SignalBatch: float32 or float64 signals (got {self.dtype})")
+        check(load().wt_signals_create(ctx._h, n, n_samples, family, max_level, self.dtype.itemsize, _c.byref(self._h)))
+        info = (_i64 * 6)()
+        check(load().wt_signals_info(self._h, info))
+        self.n, self.n_samples, self.pitch, self.family, self.max_level, _ = [int(v) for v in info]
+        self.level = 0
+        _live.add(self)
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, _vp()
+            check(load().wt_signals_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def upload(self, signals, f0=0):
+        a = np.ascontiguousarray(signals, dtype=self.dtype)
+        if a.ndim != 2 or a.shape[1] != self.n_samples:
+            raise ValueError(f"signals of shape {a.shape} != (., {self.n_samples})")
+        check(load().wt_signals_upload(self._h, f0, a.shape[0], _vp(a.ctypes.data)))
+
+    def decompose(self, nf, level):
+        check(load().wt_signals_decompose(self._h, nf, level))
+        self.level = level
+
+    def abs_median(self, nf):
+        """np.median(np.abs(w_0)) of signals 0 .. nf-1 as an array of the stack's type: one host round trip"""
+        out = np.empty(nf, self.dtype)
+        check(load().wt_signals_abs_median(self._h, nf, _vp(out.ctypes.data)))
+        return out
+
+    def denoise_sum(self, nf, taus, wgts, soft=True):
+        """Coefficients.denoise + the plane sum of signals 0 .. nf-1: one row of thresholds and one of weights per signal"""
+        n, ta, wa = _enhance_rows(nf, taus, wgts)
+        check(load().wt_signals_denoise_sum(self._h, nf, n, ta, wa, int(soft)))
+
+    def _target(self, out, shape):
+        if out is None:
+            return host_empty(shape, self.ctx, self.dtype)
+        assert out.dtype == self.dtype and out.shape == shape and out.flags.c_contiguous and out.flags.writeable
+        return out
+
+    def download_planes(self, nf, out=None, f0=0):
+        """(nf, level + 1, n_samples) of the last decompose"""
+        out = self._target(out, (nf, self.level + 1, self.n_samples))
+        check(load().wt_signals_download_planes(self._h, f0, nf, _vp(out.ctypes.data)))
+        return out
+
+    def download_sum(self, nf, out=None, f0=0):
+        """(nf, n_samples) of the last denoise_sum"""
+        out = self._target(out, (nf, self.n_samples))
+        check(load().wt_signals_download_sum(self._h, f0, nf, _vp(out.ctypes.data)))
+        return out
+
+
+_signal_cache = {}       # id(ctx) -> [SignalBatch], most recently used last (its own cache: not the batch cache, not the plan pool)
+_SIGNAL_CACHE_MAX = 2
+
+
+def acquire_signals(ctx, n, n_samples, family, max_level, dtype=np.float32):
+    """A SignalBatch of at least `n` signals of (n_samples, family, max_level, dtype) on `ctx`: cached if available, else new."""
+    dtype = np.dtype(dtype)
+    with _pool_lock:
+        lst = _signal_cache.setdefault(id(ctx), [])
+        for i, b in enumerate(lst):
+            if b._h and b.ctx is ctx and (b.n_samples, b.family, b.max_level, b.dtype) == (n_samples, family, max_level, dtype) \
+                    and b.n >= n:
+                return lst.pop(i)
+    return SignalBatch(ctx, n, n_samples, family, max_level, dtype)
+
+
+def release_signals(b):
+    if b is None or not b._h:
+        return
+    with _pool_lock:
+        lst = _signal_cache.setdefault(id(b.ctx), [])
+        lst.append(b)
+        while len(lst) > _SIGNAL_CACHE_MAX:
+            lst.pop(0).close()
+
+
+def trim_signals():
+    """Release the device memory of every cached SignalBatch (the cache keeps at most two per context)."""
+    with _pool_lock:
+        lst = [b for v in _signal_cache.values() for b in v]
+        _signal_cache.clear()
+    for b in lst:
+        b.close()
 
 
 # ------------------------------------------------------------------------------------------
