@@ -886,6 +886,47 @@ int wt_signals_download_planes(wt_signals *signals, int first, int count, void *
 /* the sums of wt_signals_denoise_sum of signals [first, first + count) -> host (count, n_samples) (utils.py:98) */
 int wt_signals_download_sum(wt_signals *signals, int first, int count, void *host);
 
+/* ---- the 1-D transform along an axis that is not the last one (wt_along) -------------------------------------------
+ * An array viewed as (O, N, I), float or double: N samples of a signal lie I elements apart (every pixel's light curve
+ * of a (T, H, W) movie: O = 1, N = T, I = H * W).  A workgroup takes a tile of TI neighbouring signals with their
+ * scales in LDS and writes every plane once in the layout of the input; no transpose.  Every signal gets the bits of
+ * wt_signals on the transposed stack, hence of the reference's 1-D branch (watroo/wavelets.py:65-69 under :408-444).
+ * The stack holds one chunk (n_outer, N, n_inner) at a time (wt_along_upload); a plane of a chunk is laid out as the
+ * chunk.  Host blocks are addressed as rows of n_inner elements, `pitch` elements apart (pitch = I). */
+typedef struct wt_along wt_along;
+/* host logic, no GPU needed: 1 when signals of n_samples samples n_inner elements apart of `itemsize` bytes (4: float,
+ * 8: double) of `family` over `level` scales (watroo/wavelets.py:426-444) run on a wt_along, else 0: a built-in family,
+ * 1 .. 24 scales, n_inner >= 2, and a tile of at least 64 bytes per run whose two LDS buffers fit 64 KiB -
+ * n_samples <= 512 in either type (a chosen budget, not a measured optimum) */
+int wt_along_ok(int family, int64_t n_samples, int64_t n_inner, int level, int itemsize);
+/* device memory for chunks of up to n_signals signals (n_outer * n_inner) of n_samples samples: with_planes != 0 for
+ * transforms of up to max_level scales (the block and max_level + 1 planes, watroo/wavelets.py:426-427), 0 for the
+ * fused thresholded sum (the block, the sum and the threshold table, utils.py:97-98) */
+int wt_along_create(wt_ctx *ctx, int64_t n_signals, int n_samples, int family, int max_level, int itemsize,
+                    int with_planes, wt_along **out);
+int wt_along_destroy(wt_along *along);
+/* info[8] = {n_signals, n_samples, tile TI, family, max_level, itemsize, with_planes, scales of the last transform} */
+int wt_along_info(wt_along *along, int64_t *info);
+/* the chunk (n_outer, n_samples, n_inner) <- n_outer * n_samples host rows of n_inner elements, `pitch` elements apart
+ * (the arr of watroo/wavelets.py:307, in place); the block is free when the call returns */
+int wt_along_upload(wt_along *along, int n_outer, int n_inner, const void *host, int64_t pitch);
+/* AtrousTransform.atrous_standard of every signal of the chunk over `level` scales (watroo/wavelets.py:408-444 over
+ * :65-69): one launch; HBM traffic sizeof(element) * (level + 2) bytes per sample */
+int wt_along_decompose(wt_along *along, int level);
+/* np.median(np.abs(w_0)) of every signal of the chunk (Coefficients.get_noise, watroo/wavelets.py:126-127), exact,
+ * the even / odd rule of wt_signals_abs_median: scale 0 in LDS only, no plane written; medians[n_outer * n_inner] of
+ * the stack's element type, one host round trip */
+int wt_along_abs_median(wt_along *along, void *medians);
+/* Coefficients.denoise + np.sum(coefficients, axis=0) of every signal of the chunk (watroo/wavelets.py:145-149,
+ * utils.py:97-98) fused with the transform over `level` scales: only the sum is written.  tau[n_outer * n_inner *
+ * n_den], one row per signal (tau <= 0: significance one), wgt[n_den] shared; n_den <= level <= 15 */
+int wt_along_denoise(wt_along *along, int level, int n_den, const double *tau, const double *wgt, int soft);
+/* the planes of the last wt_along_decompose -> host: plane s at host + s * plane_stride elements, each as the rows of
+ * wt_along_upload (Coefficients.data per signal, watroo/wavelets.py:426-444) */
+int wt_along_download_planes(wt_along *along, void *host, int64_t pitch, int64_t plane_stride);
+/* the sum of wt_along_denoise -> host rows as wt_along_upload (utils.py:98) */
+int wt_along_download_sum(wt_along *along, void *host, int64_t pitch);
+
 #ifdef __cplusplus
 }
 #endif

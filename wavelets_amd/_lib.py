@@ -301,6 +301,17 @@ SIGNATURES = {
                                           _c.c_int]),
     "wt_signals_download_planes": (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp]),
     "wt_signals_download_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp]),
+    # the 1-D transform along an axis that is not the last one (wt_along)
+    "wt_along_ok": (_c.c_int, [_c.c_int, _i64, _i64, _c.c_int, _c.c_int]),
+    "wt_along_create": (_c.c_int, [_vp, _i64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_vp)]),
+    "wt_along_destroy": (_c.c_int, [_vp]),
+    "wt_along_info": (_c.c_int, [_vp, _c.POINTER(_i64)]),
+    "wt_along_upload": (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp, _i64]),
+    "wt_along_decompose": (_c.c_int, [_vp, _c.c_int]),
+    "wt_along_abs_median": (_c.c_int, [_vp, _vp]),
+    "wt_along_denoise": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.c_int]),
+    "wt_along_download_planes": (_c.c_int, [_vp, _vp, _i64, _i64]),
+    "wt_along_download_sum": (_c.c_int, [_vp, _vp, _i64]),
 }
 
 _lib = None
@@ -481,7 +492,7 @@ def _shutdown():
     otherwise destroys planes after the runtime's own static destructors ran)."""
     _host_pool.close()
     objs = list(_live)
-    for kind in ((Plan, Plan64, BatchPlan, BatchPlan64, SignalBatch), (Context,)):
+    for kind in ((Plan, Plan64, BatchPlan, BatchPlan64, SignalBatch, AlongBatch), (Context,)):
         for o in objs:
             if isinstance(o, kind):
                 try:
@@ -493,6 +504,7 @@ def _shutdown():
     del _pool[:]
     _batch_cache.clear()
     _signal_cache.clear()
+    _along_cache.clear()
 
 
 _tls = threading.local()          # .ctx: the context the API calls of THIS thread run on (use_context)
@@ -1518,6 +1530,189 @@ def trim_signals():
     with _pool_lock:
         lst = [b for v in _signal_cache.values() for b in v]
         _signal_cache.clear()
+    for b in lst:
+        b.close()
+
+
+# ------------------------------------------------------------------------------------------
+# the 1-D transform along an axis that is not the last one (wt_along): an array viewed as (O, N, I), a tile of
+# neighbouring signals per workgroup, the scales in LDS
+# ------------------------------------------------------------------------------------------
+ALONG_MAX_TILE = 256                      # WT_ALONG_MAX_TILE
+ALONG_LDS_BYTES = 65536                   # WT_SIGNALS_LDS_BYTES: the two N x TI buffers of a tile (chosen, not measured)
+ALONG_MAX_SIGNALS = 1 << 30               # signals of one chunk (wt_along_create)
+
+
+def along_ok(family, n_samples, n_inner, level, itemsize):
+    """True when signals of `n_samples` samples `n_inner` elements apart of `itemsize` bytes of `family` over `level`
+    scales run on an AlongBatch (host logic, wt_along_ok): a built-in family, 1..24 scales, n_inner >= 2, and a tile
+    with runs of at least 64 bytes within the 64 KiB of LDS - at most 512 samples in float32 and in float64"""
+    if not isinstance(family, int):
+        return False
+    return bool(load().wt_along_ok(int(family), int(n_samples), int(n_inner), int(level), int(itemsize)))
+
+
+def along_tile(n_samples, itemsize):
+    """signals one workgroup takes (host logic, the rule of wt_along.hip): the largest power of two TI with
+    2 * n_samples * TI * itemsize <= 64 KiB, at most 256 (0: not even one signal fits).  Never adapted to a narrow
+    inner extent: a tile wider than it has idle lanes."""
+    if n_samples < 1:
+        return 0
+    ti = ALONG_MAX_TILE
+    while ti and 2 * n_samples * ti * itemsize > ALONG_LDS_BYTES:
+        ti >>= 1
+    return ti
+
+
+def along_bytes(n_samples, level, itemsize=4, planes=True):
+    """device bytes one signal of an AlongBatch takes (host logic, wt_along_create): the signal, its median and -
+    planes - planes 0..level, or - the fused sum - the sum and its rows of the threshold table"""
+    if planes:
+        return (level + 2) * n_samples * itemsize + itemsize
+    return 2 * n_samples * itemsize + itemsize + 2 * level * 8
+
+
+def along_chunks(O, N, I, level, itemsize=4, budget=None, planes=True):
+    """[(first outer index, outer indices, first inner position, inner positions)] of an (O, N, I) array over `budget`
+    bytes of device memory (default BATCH_BYTES).  The outer index is split first: as many whole outer slices per chunk
+    as fit.  When not even one fits, every outer slice is split along the inner axis in multiples of the tile (at
+    least one tile): those chunks move as rows of their inner positions at pitch I."""
+    if O < 0 or N < 0 or I < 0:
+        raise ValueError("negative size")
+    if O == 0 or N == 0 or I == 0:
+        return []
+    budget = BATCH_BYTES if budget is None else budget
+    fit = min(int(budget // along_bytes(N, level, itemsize, planes)), ALONG_MAX_SIGNALS)       # signals of one chunk
+    if fit >= I:
+        per = fit // I
+        return [(o0, min(per, O - o0), 0, I) for o0 in range(0, O, per)]
+    tile = max(1, along_tile(N, itemsize))
+    ni = max(tile, fit // tile * tile)
+    return [(o, 1, i0, min(ni, I - i0)) for o in range(O) for i0 in range(0, I, ni)]
+
+
+class AlongBatch:
+    """Device memory of chunks of up to `n_signals` signals of `n_samples` samples a stride apart, float32 or float64
+    (wt_along).  `planes`: a batch for transforms (decompose / download_planes), else one for the fused thresholded
+    sum (denoise / download_sum).  upload takes a (no, n_samples, ni) view of the caller's C-contiguous (O, N, I)
+    array - rows of ni elements at pitch I - and the downloads fill views of the same kind."""
+
+    def __init__(self, ctx, n_signals, n_samples, family, max_level, dtype=np.float32, planes=True):
+        self._h = _vp()
+        self.ctx = ctx
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"AlongBatch: float32 or float64 samples (got {self.dtype})")
+        check(load().wt_along_create(ctx._h, n_signals, n_samples, family, max_level, self.dtype.itemsize, int(bool(planes)),
+                                     _c.byref(self._h)))
+        info = (_i64 * 8)()
+        check(load().wt_along_info(self._h, info))
+        self.n, self.n_samples, self.tile, self.family, self.max_level, _, planes, _ = [int(v) for v in info]
+        self.planes = bool(planes)
+        self.level = 0
+        self.chunk = (0, 0)                  # (outer indices, inner positions) of the last upload
+        _live.add(self)
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, _vp()
+            check(load().wt_along_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _rows(self, a, lead=()):
+        """pitch in elements of a `lead` + (no, n_samples, ni) block whose rows of ni elements are contiguous and lie
+        one pitch apart through the outer index too"""
+        no, ni = a.shape[-3], a.shape[-1]
+        isz = self.dtype.itemsize
+        if a.dtype != self.dtype or a.ndim != len(lead) + 3 or a.shape[-2] != self.n_samples or a.shape[:-3] != tuple(lead):
+            raise ValueError(f"a {self.dtype} block of shape {tuple(lead)} + (., {self.n_samples}, .) expected (got {a.dtype} {a.shape})")
+        pitch = a.strides[-2] // isz
+        if (ni > 1 and a.strides[-1] != isz) or a.strides[-2] % isz or pitch < ni \
+                or (no > 1 and a.strides[-3] != self.n_samples * a.strides[-2]):
+            raise ValueError("rows of contiguous elements at one pitch expected")
+        return pitch
+
+    def upload(self, block):
+        pitch = self._rows(block)
+        no, _, ni = block.shape
+        check(load().wt_along_upload(self._h, no, ni, _vp(block.ctypes.data), pitch))
+        self.chunk, self.level = (no, ni), 0
+
+    def decompose(self, level):
+        check(load().wt_along_decompose(self._h, level))
+        self.level = level
+
+    def abs_median(self):
+        """np.median(np.abs(w_0)) of every signal of the chunk, (no, ni) of the stack's type: one host round trip"""
+        out = np.empty(self.chunk, self.dtype)
+        check(load().wt_along_abs_median(self._h, _vp(out.ctypes.data)))
+        return out
+
+    def denoise(self, level, taus, wgts, soft=True):
+        """the fused transform + Coefficients.denoise + plane sum of the chunk: `taus` one row of thresholds per signal
+        ((no * ni, n_den) doubles, 0 = significance one), `wgts` the one row of weights"""
+        ta = np.ascontiguousarray(taus, dtype=np.float64)
+        wa = np.ascontiguousarray(wgts, dtype=np.float64)
+        n_den = wa.shape[0]
+        if ta.shape != (self.chunk[0] * self.chunk[1], n_den):
+            raise ValueError(f"thresholds of shape {ta.shape} != ({self.chunk[0] * self.chunk[1]}, {n_den})")
+        dp = _c.POINTER(_c.c_double)
+        check(load().wt_along_denoise(self._h, level, n_den, ta.ctypes.data_as(dp), wa.ctypes.data_as(dp), int(soft)))
+
+    def download_planes(self, out):
+        """the planes of the last decompose into `out`: a (level + 1, no, n_samples, ni) view"""
+        pitch = self._rows(out, (self.level + 1,))
+        if out.shape[1::2] != self.chunk or not out.flags.writeable:
+            raise ValueError(f"a writable block of the chunk {self.chunk} expected (got {out.shape})")
+        check(load().wt_along_download_planes(self._h, _vp(out.ctypes.data), pitch, out.strides[0] // self.dtype.itemsize))
+        return out
+
+    def download_sum(self, out):
+        """the sum of the last denoise into `out`: a (no, n_samples, ni) view"""
+        pitch = self._rows(out)
+        if out.shape[0::2] != self.chunk or not out.flags.writeable:
+            raise ValueError(f"a writable block of the chunk {self.chunk} expected (got {out.shape})")
+        check(load().wt_along_download_sum(self._h, _vp(out.ctypes.data), pitch))
+        return out
+
+
+_along_cache = {}        # id(ctx) -> [AlongBatch], most recently used last (a cache of its own, as the signal unit's)
+_ALONG_CACHE_MAX = 2
+
+
+def acquire_along(ctx, n_signals, n_samples, family, max_level, dtype=np.float32, planes=True):
+    """An AlongBatch of at least `n_signals` signals of (n_samples, family, max_level, dtype, planes) on `ctx`: cached if
+    available, else new."""
+    dtype = np.dtype(dtype)
+    with _pool_lock:
+        lst = _along_cache.setdefault(id(ctx), [])
+        for i, b in enumerate(lst):
+            if b._h and b.ctx is ctx and b.n >= n_signals and \
+                    (b.n_samples, b.family, b.max_level, b.dtype, b.planes) == (n_samples, family, max_level, dtype, bool(planes)):
+                return lst.pop(i)
+    return AlongBatch(ctx, n_signals, n_samples, family, max_level, dtype, planes)
+
+
+def release_along(b):
+    if b is None or not b._h:
+        return
+    with _pool_lock:
+        lst = _along_cache.setdefault(id(b.ctx), [])
+        lst.append(b)
+        while len(lst) > _ALONG_CACHE_MAX:
+            lst.pop(0).close()
+
+
+def trim_along():
+    """Release the device memory of every cached AlongBatch (the cache keeps at most two per context)."""
+    with _pool_lock:
+        lst = [b for v in _along_cache.values() for b in v]
+        _along_cache.clear()
     for b in lst:
         b.close()
 

@@ -135,6 +135,9 @@ __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_abs_median_kern
     }
 }
 
+// (the thresholded sum is two explicit specialisations - definitions, not templates: a unit that includes this header
+//  for the filter text alone, as wt_along_kernels.h does, leaves them out with WT_SIGNALS_FILTER_ONLY)
+#ifndef WT_SIGNALS_FILTER_ONLY
 // Coefficients.denoise over the first n_den planes of every signal + np.sum(planes, axis=0) (watroo/wavelets.py:
 // 145-149, utils.py:98), from the planes in HBM: the per-signal wt_denoise_sum / wt64_denoise_sum with one row of
 // thresholds and one of weights per signal.  A lane owns one 16-byte group; g = groups per signal (Np / PX).
@@ -205,3 +208,4 @@ __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_denoise_sum_ker
         reinterpret_cast<double2 *>(a.dst)[i] = acc;
     }
 }
+#endif      // WT_SIGNALS_FILTER_ONLY
