@@ -276,7 +276,7 @@ class _Fake:
 
 def test_the_cache_keeps_the_two_float64_classes_apart(monkeypatch):
     W, B, U, L = _mods()
-    monkeypatch.setattr(L, "_batch_cache", {})
+    monkeypatch.setattr(L, "_batch_cache", L._StackCache())
     made = []
     for cls in (L.BatchPlan64, L.RLBatchPlan64):
         monkeypatch.setattr(cls, "__init__", lambda self, *a, _c=cls: made.append(_c))

@@ -502,9 +502,8 @@ def _shutdown():
     _default_ctx.clear()
     _lane_ctx.clear()
     del _pool[:]
-    _batch_cache.clear()
-    _signal_cache.clear()
-    _along_cache.clear()
+    for cache in (_batch_cache, _signal_cache, _along_cache):
+        cache.lists.clear()
 
 
 _tls = threading.local()          # .ctx: the context the API calls of THIS thread run on (use_context)
@@ -1106,6 +1105,10 @@ class _BatchBase:
         except Exception:
             pass
 
+    def _key(self):
+        """what a cached batch must match besides its class and capacity (_StackCache)"""
+        return self.H, self.W, self.family, self.max_level
+
     def _check_frames(self, a):
         if a.ndim != 3 or a.shape[1:] != (self.H, self.W):
             raise ValueError(f"frames of shape {a.shape[1:]} != batch frame shape {(self.H, self.W)}")
@@ -1347,54 +1350,71 @@ class RLBatchPlan64(BatchPlan64):
     mrs_update = BatchPlan.mrs_update
 
 
-_batch_cache = {}        # id(ctx) -> [BatchPlan / BatchPlan64], most recently used last (its own small cache: not the plan pool)
-_BATCH_CACHE_MAX = 2
+class _StackCache:
+    """A small cache of device stacks that are costly to allocate - objects with `_h` (the live handle), `ctx`, `n` (the
+    capacity), `_key()` (what else must match) and `close()`: per context, most recently used last, at most MAX per
+    context.  Its own cache, not the plan pool; the batches, the signal stacks and the axis stacks have one each."""
+
+    MAX = 2
+
+    def __init__(self):
+        self.lists = {}          # id(ctx) -> [stack], most recently used last
+
+    def acquire(self, cls, ctx, n, *key):
+        """a cached `cls` on `ctx` of at least `n` with `_key()` == key, taken out of the cache, else cls(ctx, n, *key)"""
+        with _pool_lock:
+            lst = self.lists.setdefault(id(ctx), [])
+            for i, b in enumerate(lst):
+                if type(b) is cls and b._h and b.ctx is ctx and b._key() == key and b.n >= n:
+                    return lst.pop(i)
+        return cls(ctx, n, *key)
+
+    def release(self, b):
+        """a stack that is still open goes (back) into the cache; the oldest of more than MAX is closed"""
+        if b is None or not b._h:
+            return
+        with _pool_lock:
+            lst = self.lists.setdefault(id(b.ctx), [])
+            lst.append(b)
+            while len(lst) > self.MAX:
+                lst.pop(0).close()
+
+    def trim(self):
+        """Release the device memory of every cached stack."""
+        with _pool_lock:
+            lst = [b for v in self.lists.values() for b in v]
+            self.lists.clear()
+        for b in lst:
+            b.close()
+
+
+_batch_cache, _signal_cache, _along_cache = _StackCache(), _StackCache(), _StackCache()
 
 
 def acquire_batch(ctx, n, H, W, family, max_level):
     """A BatchPlan of at least `n` frames of (H, W, family, max_level) on `ctx`: cached if available, else new."""
-    return _acquire(BatchPlan, ctx, n, H, W, family, max_level)
+    return _batch_cache.acquire(BatchPlan, ctx, n, H, W, family, max_level)
 
 
 def acquire_batch64(ctx, n, H, W, family, max_level):
     """A BatchPlan64 of at least `n` frames of (H, W, family, max_level) on `ctx`: cached if available, else new
     (the cache of acquire_batch; release with release_batch64)."""
-    return _acquire(BatchPlan64, ctx, n, H, W, family, max_level)
+    return _batch_cache.acquire(BatchPlan64, ctx, n, H, W, family, max_level)
 
 
 def acquire_rl_batch64(ctx, n, H, W, family, max_level):
     """An RLBatchPlan64 of at least `n` frames of (H, W, family, max_level) on `ctx`: cached if available, else new (the
     cache of acquire_batch, which keeps the classes apart; release with release_rl_batch64)."""
-    return _acquire(RLBatchPlan64, ctx, n, H, W, family, max_level)
-
-
-def _acquire(cls, ctx, n, H, W, family, max_level):
-    with _pool_lock:
-        lst = _batch_cache.setdefault(id(ctx), [])
-        for i, b in enumerate(lst):
-            if type(b) is cls and b._h and b.ctx is ctx and (b.H, b.W, b.family, b.max_level) == (H, W, family, max_level) \
-                    and b.n >= n:
-                return lst.pop(i)
-    return cls(ctx, n, H, W, family, max_level)
+    return _batch_cache.acquire(RLBatchPlan64, ctx, n, H, W, family, max_level)
 
 
 def trim_batches():
     """Release the device memory of every cached BatchPlan (the cache keeps at most two per context)."""
-    with _pool_lock:
-        lst = [b for v in _batch_cache.values() for b in v]
-        _batch_cache.clear()
-    for b in lst:
-        b.close()
+    _batch_cache.trim()
 
 
 def release_batch(b):
-    if b is None or not b._h:
-        return
-    with _pool_lock:
-        lst = _batch_cache.setdefault(id(b.ctx), [])
-        lst.append(b)
-        while len(lst) > _BATCH_CACHE_MAX:
-            lst.pop(0).close()
+    _batch_cache.release(b)
 
 
 release_batch64 = release_rl_batch64 = release_batch          # (one cache for every kind of batch)
@@ -1431,27 +1451,35 @@ def signal_chunks(n, n_samples, level, budget=None, itemsize=4):
     return [(f0, min(per, n - f0)) for f0 in range(0, n, per)]
 
 
-class SignalBatch:
-    """Device memory of up to `n` signals of `n_samples` samples, float32 or float64 (wt_signals).  Operations take the
-    number of active signals `nf` (signals 0 .. nf-1); upload / download move C-contiguous blocks of signals."""
+class _LinesBase:
+    """What SignalBatch and AlongBatch share, written once, in the manner of _BatchBase: the handle of a stack of 1-D
+    signals of float32 or float64.  A subclass names the library's entries (`_prefix`) and itself with what it holds
+    (`_holds`: the head of the element type error)."""
 
-    def __init__(self, ctx, n, n_samples, family, max_level, dtype=np.float32):
+    _prefix = _holds = None
+
+    def _call(self, name, *args):
+        check(getattr(load(), self._prefix + name)(self._h, *args))
+
+    def _create(self, n_info, ctx, n, n_samples, family, max_level, dtype, *more):
+        """wt_..._create(ctx, n, n_samples, family, max_level, itemsize, *more, &handle); its wt_..._info as ints"""
         self._h = _vp()
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise ValueError(f"SignalBatch: float32 or float64 signals (got {self.dtype})")
-        check(load().wt_signals_create(ctx._h, n, n_samples, family, max_level, self.dtype.itemsize, _c.byref(self._h)))
-        info = (_i64 * 6)()
-        check(load().wt_signals_info(self._h, info))
-        self.n, self.n_samples, self.pitch, self.family, self.max_level, _ = [int(v) for v in info]
+            raise ValueError(f"{self._holds} (got {self.dtype})")
+        check(getattr(load(), self._prefix + "create")(ctx._h, n, n_samples, family, max_level, self.dtype.itemsize, *more,
+                                                        _c.byref(self._h)))
+        info = (_i64 * n_info)()
+        self._call("info", info)
         self.level = 0
         _live.add(self)
+        return [int(v) for v in info]
 
     def close(self):
         if self._h:
             h, self._h = self._h, _vp()
-            check(load().wt_signals_destroy(h))
+            check(getattr(load(), self._prefix + "destroy")(h))
 
     def __del__(self):
         try:
@@ -1459,26 +1487,39 @@ class SignalBatch:
         except Exception:
             pass
 
+
+class SignalBatch(_LinesBase):
+    """Device memory of up to `n` signals of `n_samples` samples, float32 or float64 (wt_signals).  Operations take the
+    number of active signals `nf` (signals 0 .. nf-1); upload / download move C-contiguous blocks of signals."""
+
+    _prefix, _holds = "wt_signals_", "SignalBatch: float32 or float64 signals"
+
+    def __init__(self, ctx, n, n_samples, family, max_level, dtype=np.float32):
+        self.n, self.n_samples, self.pitch, self.family, self.max_level, _ = self._create(6, ctx, n, n_samples, family, max_level, dtype)
+
+    def _key(self):
+        return self.n_samples, self.family, self.max_level, self.dtype
+
     def upload(self, signals, f0=0):
         a = np.ascontiguousarray(signals, dtype=self.dtype)
         if a.ndim != 2 or a.shape[1] != self.n_samples:
             raise ValueError(f"signals of shape {a.shape} != (., {self.n_samples})")
-        check(load().wt_signals_upload(self._h, f0, a.shape[0], _vp(a.ctypes.data)))
+        self._call("upload", f0, a.shape[0], _vp(a.ctypes.data))
 
     def decompose(self, nf, level):
-        check(load().wt_signals_decompose(self._h, nf, level))
+        self._call("decompose", nf, level)
         self.level = level
 
     def abs_median(self, nf):
         """np.median(np.abs(w_0)) of signals 0 .. nf-1 as an array of the stack's type: one host round trip"""
         out = np.empty(nf, self.dtype)
-        check(load().wt_signals_abs_median(self._h, nf, _vp(out.ctypes.data)))
+        self._call("abs_median", nf, _vp(out.ctypes.data))
         return out
 
     def denoise_sum(self, nf, taus, wgts, soft=True):
         """Coefficients.denoise + the plane sum of signals 0 .. nf-1: one row of thresholds and one of weights per signal"""
         n, ta, wa = _enhance_rows(nf, taus, wgts)
-        check(load().wt_signals_denoise_sum(self._h, nf, n, ta, wa, int(soft)))
+        self._call("denoise_sum", nf, n, ta, wa, int(soft))
 
     def _target(self, out, shape):
         if out is None:
@@ -1489,49 +1530,28 @@ class SignalBatch:
     def download_planes(self, nf, out=None, f0=0):
         """(nf, level + 1, n_samples) of the last decompose"""
         out = self._target(out, (nf, self.level + 1, self.n_samples))
-        check(load().wt_signals_download_planes(self._h, f0, nf, _vp(out.ctypes.data)))
+        self._call("download_planes", f0, nf, _vp(out.ctypes.data))
         return out
 
     def download_sum(self, nf, out=None, f0=0):
         """(nf, n_samples) of the last denoise_sum"""
         out = self._target(out, (nf, self.n_samples))
-        check(load().wt_signals_download_sum(self._h, f0, nf, _vp(out.ctypes.data)))
+        self._call("download_sum", f0, nf, _vp(out.ctypes.data))
         return out
-
-
-_signal_cache = {}       # id(ctx) -> [SignalBatch], most recently used last (its own cache: not the batch cache, not the plan pool)
-_SIGNAL_CACHE_MAX = 2
 
 
 def acquire_signals(ctx, n, n_samples, family, max_level, dtype=np.float32):
     """A SignalBatch of at least `n` signals of (n_samples, family, max_level, dtype) on `ctx`: cached if available, else new."""
-    dtype = np.dtype(dtype)
-    with _pool_lock:
-        lst = _signal_cache.setdefault(id(ctx), [])
-        for i, b in enumerate(lst):
-            if b._h and b.ctx is ctx and (b.n_samples, b.family, b.max_level, b.dtype) == (n_samples, family, max_level, dtype) \
-                    and b.n >= n:
-                return lst.pop(i)
-    return SignalBatch(ctx, n, n_samples, family, max_level, dtype)
+    return _signal_cache.acquire(SignalBatch, ctx, n, n_samples, family, max_level, np.dtype(dtype))
 
 
 def release_signals(b):
-    if b is None or not b._h:
-        return
-    with _pool_lock:
-        lst = _signal_cache.setdefault(id(b.ctx), [])
-        lst.append(b)
-        while len(lst) > _SIGNAL_CACHE_MAX:
-            lst.pop(0).close()
+    _signal_cache.release(b)
 
 
 def trim_signals():
     """Release the device memory of every cached SignalBatch (the cache keeps at most two per context)."""
-    with _pool_lock:
-        lst = [b for v in _signal_cache.values() for b in v]
-        _signal_cache.clear()
-    for b in lst:
-        b.close()
+    _signal_cache.trim()
 
 
 # ------------------------------------------------------------------------------------------
@@ -1591,38 +1611,22 @@ def along_chunks(O, N, I, level, itemsize=4, budget=None, planes=True):
     return [(o, 1, i0, min(ni, I - i0)) for o in range(O) for i0 in range(0, I, ni)]
 
 
-class AlongBatch:
+class AlongBatch(_LinesBase):
     """Device memory of chunks of up to `n_signals` signals of `n_samples` samples a stride apart, float32 or float64
     (wt_along).  `planes`: a batch for transforms (decompose / download_planes), else one for the fused thresholded
     sum (denoise / download_sum).  upload takes a (no, n_samples, ni) view of the caller's C-contiguous (O, N, I)
     array - rows of ni elements at pitch I - and the downloads fill views of the same kind."""
 
+    _prefix, _holds = "wt_along_", "AlongBatch: float32 or float64 samples"
+
     def __init__(self, ctx, n_signals, n_samples, family, max_level, dtype=np.float32, planes=True):
-        self._h = _vp()
-        self.ctx = ctx
-        self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise ValueError(f"AlongBatch: float32 or float64 samples (got {self.dtype})")
-        check(load().wt_along_create(ctx._h, n_signals, n_samples, family, max_level, self.dtype.itemsize, int(bool(planes)),
-                                     _c.byref(self._h)))
-        info = (_i64 * 8)()
-        check(load().wt_along_info(self._h, info))
-        self.n, self.n_samples, self.tile, self.family, self.max_level, _, planes, _ = [int(v) for v in info]
+        info = self._create(8, ctx, n_signals, n_samples, family, max_level, dtype, int(bool(planes)))
+        self.n, self.n_samples, self.tile, self.family, self.max_level, _, planes, _ = info
         self.planes = bool(planes)
-        self.level = 0
         self.chunk = (0, 0)                  # (outer indices, inner positions) of the last upload
-        _live.add(self)
 
-    def close(self):
-        if self._h:
-            h, self._h = self._h, _vp()
-            check(load().wt_along_destroy(h))
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _key(self):
+        return self.n_samples, self.family, self.max_level, self.dtype, self.planes
 
     def _rows(self, a, lead=()):
         """pitch in elements of a `lead` + (no, n_samples, ni) block whose rows of ni elements are contiguous and lie
@@ -1640,17 +1644,17 @@ class AlongBatch:
     def upload(self, block):
         pitch = self._rows(block)
         no, _, ni = block.shape
-        check(load().wt_along_upload(self._h, no, ni, _vp(block.ctypes.data), pitch))
+        self._call("upload", no, ni, _vp(block.ctypes.data), pitch)
         self.chunk, self.level = (no, ni), 0
 
     def decompose(self, level):
-        check(load().wt_along_decompose(self._h, level))
+        self._call("decompose", level)
         self.level = level
 
     def abs_median(self):
         """np.median(np.abs(w_0)) of every signal of the chunk, (no, ni) of the stack's type: one host round trip"""
         out = np.empty(self.chunk, self.dtype)
-        check(load().wt_along_abs_median(self._h, _vp(out.ctypes.data)))
+        self._call("abs_median", _vp(out.ctypes.data))
         return out
 
     def denoise(self, level, taus, wgts, soft=True):
@@ -1661,15 +1665,14 @@ class AlongBatch:
         n_den = wa.shape[0]
         if ta.shape != (self.chunk[0] * self.chunk[1], n_den):
             raise ValueError(f"thresholds of shape {ta.shape} != ({self.chunk[0] * self.chunk[1]}, {n_den})")
-        dp = _c.POINTER(_c.c_double)
-        check(load().wt_along_denoise(self._h, level, n_den, ta.ctypes.data_as(dp), wa.ctypes.data_as(dp), int(soft)))
+        self._call("denoise", level, n_den, ta.ctypes.data_as(_dp), wa.ctypes.data_as(_dp), int(soft))
 
     def download_planes(self, out):
         """the planes of the last decompose into `out`: a (level + 1, no, n_samples, ni) view"""
         pitch = self._rows(out, (self.level + 1,))
         if out.shape[1::2] != self.chunk or not out.flags.writeable:
             raise ValueError(f"a writable block of the chunk {self.chunk} expected (got {out.shape})")
-        check(load().wt_along_download_planes(self._h, _vp(out.ctypes.data), pitch, out.strides[0] // self.dtype.itemsize))
+        self._call("download_planes", _vp(out.ctypes.data), pitch, out.strides[0] // self.dtype.itemsize)
         return out
 
     def download_sum(self, out):
@@ -1677,44 +1680,23 @@ class AlongBatch:
         pitch = self._rows(out)
         if out.shape[0::2] != self.chunk or not out.flags.writeable:
             raise ValueError(f"a writable block of the chunk {self.chunk} expected (got {out.shape})")
-        check(load().wt_along_download_sum(self._h, _vp(out.ctypes.data), pitch))
+        self._call("download_sum", _vp(out.ctypes.data), pitch)
         return out
-
-
-_along_cache = {}        # id(ctx) -> [AlongBatch], most recently used last (a cache of its own, as the signal unit's)
-_ALONG_CACHE_MAX = 2
 
 
 def acquire_along(ctx, n_signals, n_samples, family, max_level, dtype=np.float32, planes=True):
     """An AlongBatch of at least `n_signals` signals of (n_samples, family, max_level, dtype, planes) on `ctx`: cached if
     available, else new."""
-    dtype = np.dtype(dtype)
-    with _pool_lock:
-        lst = _along_cache.setdefault(id(ctx), [])
-        for i, b in enumerate(lst):
-            if b._h and b.ctx is ctx and b.n >= n_signals and \
-                    (b.n_samples, b.family, b.max_level, b.dtype, b.planes) == (n_samples, family, max_level, dtype, bool(planes)):
-                return lst.pop(i)
-    return AlongBatch(ctx, n_signals, n_samples, family, max_level, dtype, planes)
+    return _along_cache.acquire(AlongBatch, ctx, n_signals, n_samples, family, max_level, np.dtype(dtype), bool(planes))
 
 
 def release_along(b):
-    if b is None or not b._h:
-        return
-    with _pool_lock:
-        lst = _along_cache.setdefault(id(b.ctx), [])
-        lst.append(b)
-        while len(lst) > _ALONG_CACHE_MAX:
-            lst.pop(0).close()
+    _along_cache.release(b)
 
 
 def trim_along():
     """Release the device memory of every cached AlongBatch (the cache keeps at most two per context)."""
-    with _pool_lock:
-        lst = [b for v in _along_cache.values() for b in v]
-        _along_cache.clear()
-    for b in lst:
-        b.close()
+    _along_cache.trim()
 
 
 # ------------------------------------------------------------------------------------------

@@ -18,8 +18,8 @@ go through transform_signals / denoise_signals and return what those return."""
 import numpy as np
 
 from . import _lib
-from .wavelets import B3spline, _family_of, _needs_generic, _interleave_split, _result_dtype
-from .signals import transform_signals, denoise_signals, _target, _hand_over
+from .wavelets import B3spline, _result_dtype
+from .signals import transform_signals, denoise_signals, _engine_family, _target, _hand_over, _result, _thresholds
 from .batch import _real_scalar
 
 __all__ = ['transform_along', 'denoise_along', 'along_eligible']
@@ -41,38 +41,34 @@ def _real_array(noise):
     return isinstance(noise, np.ndarray) and noise.dtype.kind in "biuf"
 
 
+def _along_family(a, level, scaling_function, axis, noise=None):
+    """the family the axis engine computes this array with, or None (along_eligible)"""
+    if not isinstance(a, np.ndarray) or a.ndim < 2:
+        return None
+    axis = _axis_of(a, axis)
+    if axis is None:
+        return None
+    O, N, I = _view(a.shape, axis)
+    if O < 1 or N < 1 or I < 2:
+        return None
+    fam = _engine_family(a.dtype, level, scaling_function)
+    if fam is None:
+        return None
+    if isinstance(noise, np.ndarray):
+        if not _real_array(noise) or noise.shape != a.shape[:axis] + a.shape[axis + 1:]:
+            return None
+    elif noise is not None and not _real_scalar(noise):
+        return None
+    return fam if _lib.along_ok(fam, N, I, int(level), a.dtype.itemsize) else None
+
+
 def along_eligible(a, level, scaling_function=B3spline, axis=0, noise=None):
     """True when the axis engine computes this array (host logic): an ndarray of at least two dimensions of native
     float32 or native float64 with at least one signal; an axis that is not in effect the last one (I >= 2: the last
     axis is the signal engine's); a built-in scaling function with its own taps; an int level, 1 <= level <= 24;
     `noise` None, a real scalar or a real ndarray of the shape of `a` without `axis`; and an axis within the LDS budget
     of the kernel (_lib.along_ok: at most 512 samples).  Everything else runs the transposed route."""
-    if not isinstance(a, np.ndarray) or a.ndim < 2:
-        return False
-    if a.dtype not in (np.dtype(np.float32), np.dtype(np.float64)) or not a.dtype.isnative:
-        return False
-    axis = _axis_of(a, axis)
-    if axis is None:
-        return False
-    O, N, I = _view(a.shape, axis)
-    if O < 1 or N < 1 or I < 2:
-        return False
-    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 1 <= level <= _lib.SIGNAL_MAX_LEVEL:
-        return False
-    if _needs_generic(scaling_function):
-        return False
-    try:
-        fam = _family_of(scaling_function(1), 1)
-    except (ValueError, NotImplementedError):
-        return False
-    if not isinstance(fam, int):
-        return False
-    if isinstance(noise, np.ndarray):
-        if not _real_array(noise) or noise.shape != a.shape[:axis] + a.shape[axis + 1:]:
-            return False
-    elif noise is not None and not _real_scalar(noise):
-        return False
-    return _lib.along_ok(fam, N, I, int(level), a.dtype.itemsize)
+    return _along_family(a, level, scaling_function, axis, noise) is not None
 
 
 # ---------------------------------------------------------------- thresholds of all signals at once
@@ -151,7 +147,8 @@ def transform_along(a, level, scaling_function=B3spline, axis=0, out=None):
     wavelets.py:307-328 over :65-69), plane s of all signals at [s].  One launch per chunk."""
     a, axis = _checked(a, axis)
     O, N, I = _view(a.shape, axis)
-    if I == 1 or not along_eligible(a, level, scaling_function, axis):
+    fam = None if I == 1 else _along_family(a, level, scaling_function, axis)
+    if fam is None:
         # the signal engine's layout (the last axis), or the route a user would write: transpose, transform_signals
         # (which routes further by itself and raises what it raises), rearrange
         if isinstance(level, (int, np.integer)) and level >= 0:
@@ -160,14 +157,10 @@ def transform_along(a, level, scaling_function=B3spline, axis=0, out=None):
         res = _back(transform_signals(sig, level, scaling_function), moved, axis, 1)
         return _hand_over(res, out) if out is not None else np.ascontiguousarray(res)
     level = int(level)
-    res = _target(out, (level + 1,) + a.shape, a.dtype)
-    ctx = _lib.default_context()
-    if res is None:
-        res = _lib.host_empty((level + 1,) + a.shape, ctx, a.dtype)       # page-locked: the downloads land at PCIe rate
+    res, ctx = _result(_target(out, (level + 1,) + a.shape, a.dtype), (level + 1,) + a.shape, a.dtype)
     a3, r4 = a.reshape(O, N, I), res.reshape(level + 1, O, N, I)
     chunks = _chunks(O, N, I, level, a.dtype.itemsize, True)
-    ab = _lib.acquire_along(ctx, max(no * ni for _, no, _, ni in chunks), N, _family_of(scaling_function(1), 1), level,
-                            a.dtype, planes=True)
+    ab = _lib.acquire_along(ctx, max(no * ni for _, no, _, ni in chunks), N, fam, level, a.dtype, planes=True)
     try:
         for o0, no, i0, ni in chunks:
             ab.upload(a3[o0:o0 + no, :, i0:i0 + ni])
@@ -190,26 +183,21 @@ def denoise_along(a, weights, scaling_function=B3spline, axis=0, noise=None, sof
     if isinstance(noise, np.ndarray) and noise.shape != rest:
         raise ValueError(f"noise: an array of shape {rest} expected, one level per signal (got {noise.shape})")
     level = len(weights)
-    if I == 1 or not along_eligible(a, level, scaling_function, axis, noise) or level + 1 > _lib.MAX_SUM_PLANES:
+    fam = None if I == 1 else _along_family(a, level, scaling_function, axis, noise)
+    if fam is None or level + 1 > _lib.MAX_SUM_PLANES:
         out = _target(out, a.shape, _result_dtype(a))
         sig, moved = _moved(a, axis)
         per = list(noise.reshape(-1)) if isinstance(noise, np.ndarray) else noise
         res = _back(denoise_signals(sig, weights, scaling_function, per, soft_threshold), moved, axis, 0)
         return _hand_over(res, out) if out is not None else np.ascontiguousarray(res)
     res = _target(out, a.shape, a.dtype)
-    sf = scaling_function(1)
-    sigma_e = sf.sigma_e()
-    # Coefficients._denoise_sum(weights): sigma = weights, every weight 1, as denoise_signals
-    entries, _, _ = _interleave_split([], level, list(weights), (1,) * level)
-    need_noise = any(s != 0 for _, s, _ in entries)
+    sigma_e, entries, need_noise = _thresholds(weights, scaling_function)       # (as denoise_signals)
     wgts = [w for _, _, w in entries]
-    ctx = _lib.default_context()
-    if res is None:
-        res = _lib.host_empty(a.shape, ctx, a.dtype)
+    res, ctx = _result(res, a.shape, a.dtype)
     a3, r3 = a.reshape(O, N, I), res.reshape(O, N, I)
     levels = noise.reshape(O, I) if isinstance(noise, np.ndarray) else None
     chunks = _chunks(O, N, I, level, a.dtype.itemsize, False)
-    ab = _lib.acquire_along(ctx, max(no * ni for _, no, _, ni in chunks), N, _family_of(sf, 1), level, a.dtype, planes=False)
+    ab = _lib.acquire_along(ctx, max(no * ni for _, no, _, ni in chunks), N, fam, level, a.dtype, planes=False)
     try:
         for o0, no, i0, ni in chunks:
             ab.upload(a3[o0:o0 + no, :, i0:i0 + ni])

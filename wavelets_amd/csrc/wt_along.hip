@@ -4,6 +4,7 @@
 // contiguous, so such data had to be transposed on the host, twice.  This unit views the array as (O, N, I) - N
 // samples I elements apart - and runs a tile of TI neighbouring signals per workgroup with the scales in LDS
 // (wt_along_kernels.h): the device layout is the host layout, and every signal gets the bits of the signal unit.
+// The host text it shares with the signal unit (wt_signals.hip) is wt_lines_host.h, the device text wt_signal_common.h.
 //
 // The LDS budget is the signal unit's 64 KiB (WT_SIGNALS_LDS_BYTES) for the two buffers of N x TI elements - CHOSEN,
 // not a measured optimum: TI = the largest power of two with 2 * N * TI * itemsize <= 64 KiB, at most 256, and runs of
@@ -16,7 +17,7 @@
 #include <cstring>
 #include <vector>
 
-#include "wt_host.h"
+#include "wt_lines_host.h"
 #include "wt_along_kernels.h"
 #include "wt_unit_probe.h"
 
@@ -54,12 +55,7 @@ extern "C" int wt_along_ok(int family, int64_t n_samples, int64_t n_inner, int l
     return (int64_t)along_tile(n_samples, itemsize) * itemsize >= WT_ALONG_MIN_RUN_BYTES ? 1 : 0;
 }
 
-static void along_free(wt_along *b, int *bad)
-{
-    void *dev[] = {b->in, b->planes, b->sum, b->medians, b->d_tab};
-    for (void *q : dev)
-        if (q && hipFree(q) != hipSuccess) *bad = 1;
-}
+static void along_free(wt_along *b, int *bad) { lines_free({b->in, b->planes, b->sum, b->medians, b->d_tab}, bad); }
 
 extern "C" int wt_along_create(wt_ctx *ctx, int64_t n_signals, int n_samples, int family, int max_level, int itemsize, int with_planes, wt_along **out)
 {
@@ -88,28 +84,10 @@ extern "C" int wt_along_create(wt_ctx *ctx, int64_t n_signals, int n_samples, in
         if (e == hipSuccess) e = hipMalloc(&b->sum, block);
         if (e == hipSuccess) e = hipMalloc((void **)&b->d_tab, (size_t)n_signals * 2 * max_level * sizeof(double));
     }
-    if (e != hipSuccess) {
-        int bad = 0;
-        along_free(b, &bad);
-        delete b;
-        wt_set_error("wt_along_create: HIP error %d (%s)", (int)e, hipGetErrorString(e));
-        return 2;
-    }
-    *out = b;
-    return 0;
+    return lines_created(b, out, e, "wt_along_create", along_free);
 }
 
-extern "C" int wt_along_destroy(wt_along *b)
-{
-    if (!b) return 0;
-    WtGuard guard_(b->ctx);
-    (void)hipStreamSynchronize(b->ctx->stream);
-    int bad = 0;
-    along_free(b, &bad);
-    delete b;
-    if (bad) WT_FAIL("wt_along_destroy: a device buffer could not be released");
-    return 0;
-}
+extern "C" int wt_along_destroy(wt_along *b) { return lines_destroy(b, "wt_along_destroy", along_free); }
 
 extern "C" int wt_along_info(wt_along *b, int64_t *info)
 {
@@ -119,20 +97,11 @@ extern "C" int wt_along_info(wt_along *b, int64_t *info)
     return 0;
 }
 
-// oc * N rows of ic elements between a host block (rows `pitch` elements apart) and the dense device block: one
-// linear copy where the pitches agree
+// oc * N rows of ic elements between a host block (rows `pitch` elements apart) and the dense device block
 static int along_copy(wt_along *b, void *dev, void *host, int64_t pitch, bool up)
 {
-    const size_t w = (size_t)b->ic * b->itemsize, hp = (size_t)pitch * b->itemsize, rows = (size_t)b->oc * b->N;
-    hipStream_t st = b->ctx->stream;
-    if (up) {
-        if (w == hp) WT_HIP(hipMemcpyAsync(dev, host, w * rows, hipMemcpyHostToDevice, st));
-        else WT_HIP(hipMemcpy2DAsync(dev, w, host, hp, w, rows, hipMemcpyHostToDevice, st));
-    } else {
-        if (w == hp) WT_HIP(hipMemcpyAsync(host, dev, w * rows, hipMemcpyDeviceToHost, st));
-        else WT_HIP(hipMemcpy2DAsync(host, hp, dev, w, w, rows, hipMemcpyDeviceToHost, st));
-    }
-    return 0;
+    const size_t w = (size_t)b->ic * b->itemsize;
+    return lines_copy(b->ctx->stream, dev, w, host, (size_t)pitch * b->itemsize, w, (size_t)b->oc * b->N, up);
 }
 
 static int along_loaded(const wt_along *b, const char *who)
@@ -187,16 +156,11 @@ extern "C" int wt_along_decompose(wt_along *b, int level)
     a.level = level;
     const size_t lds = along_lds(b);
     if (lds > WT_SIGNALS_LDS_BYTES) WT_FAIL("wt_along_decompose: %zu bytes of LDS per tile", lds);
-    const bool b3 = b->family == WT_B3SPLINE;
     const dim3 grid = along_grid(b, a), block(WT_ALONG_THREADS);
     ProfScope ps(c, b->itemsize == 8 ? "wt_along_decompose_kernel<double>" : "wt_along_decompose_kernel<float>");
-    if (b->itemsize == 4) {
-        if (b3) hipLaunchKernelGGL((wt_along_decompose_kernel<float, 5>), grid, block, lds, c->stream, a);
-        else hipLaunchKernelGGL((wt_along_decompose_kernel<float, 3>), grid, block, lds, c->stream, a);
-    } else {
-        if (b3) hipLaunchKernelGGL((wt_along_decompose_kernel<double, 5>), grid, block, lds, c->stream, a);
-        else hipLaunchKernelGGL((wt_along_decompose_kernel<double, 3>), grid, block, lds, c->stream, a);
-    }
+    lines_by_type_family(b->itemsize, b->family, [&](auto t, auto k) {
+        hipLaunchKernelGGL((wt_along_decompose_kernel<decltype(t), decltype(k)::value>), grid, block, lds, c->stream, a);
+    });
     WT_HIP(hipGetLastError());
     b->level = level;
     return 0;
@@ -215,8 +179,7 @@ extern "C" int wt_along_abs_median(wt_along *b, void *medians)
     if (lds > WT_SIGNALS_LDS_BYTES || (size_t)a.n2 * b->TI * b->itemsize > lds) WT_FAIL("wt_along_abs_median: %zu bytes of LDS per tile", lds);
     {
         ProfScope ps(c, b->itemsize == 8 ? "wt_along_abs_median_kernel<double>" : "wt_along_abs_median_kernel<float>");
-        if (b->itemsize == 4) hipLaunchKernelGGL(wt_along_abs_median_kernel<float>, along_grid(b, a), dim3(WT_ALONG_THREADS), lds, c->stream, a);
-        else hipLaunchKernelGGL(wt_along_abs_median_kernel<double>, along_grid(b, a), dim3(WT_ALONG_THREADS), lds, c->stream, a);
+        lines_by_type(b->itemsize, [&](auto t) { hipLaunchKernelGGL(wt_along_abs_median_kernel<decltype(t)>, along_grid(b, a), dim3(WT_ALONG_THREADS), lds, c->stream, a); });
     }
     WT_HIP(hipGetLastError());
     // all medians of the chunk in one host round trip
@@ -240,14 +203,14 @@ extern "C" int wt_along_denoise(wt_along *b, int level, int n_den, const double 
     if (n_den) {
         const double *src = tau;
         if (f64) {
-            // rows of {tau, 1 / tau}: the host's IEEE division, as wt_signals_denoise_sum
+            // rows of {tau, 1 / tau}
             b->h_tab.resize((size_t)count * 2 * n_den);
             for (int64_t f = 0; f < count; ++f) {
                 double *row = b->h_tab.data() + (size_t)f * 2 * n_den;
                 for (int k = 0; k < n_den; ++k) {
                     const double t = tau[(size_t)f * n_den + k];
                     row[k] = t;
-                    row[n_den + k] = t > 0.0 ? 1.0 / t : 0.0;
+                    row[n_den + k] = lines_inv_tau(t);
                 }
             }
             src = b->h_tab.data();
@@ -263,16 +226,11 @@ extern "C" int wt_along_denoise(wt_along *b, int level, int n_den, const double 
     for (int k = 0; k < n_den; ++k) a.wgt[k] = wgt[k];
     const size_t lds = along_lds(b);
     if (lds > WT_SIGNALS_LDS_BYTES) WT_FAIL("wt_along_denoise: %zu bytes of LDS per tile", lds);
-    const bool b3 = b->family == WT_B3SPLINE;
     const dim3 grid = along_grid(b, a), block(WT_ALONG_THREADS);
     ProfScope ps(c, f64 ? "wt_along_denoise_kernel<double>" : "wt_along_denoise_kernel<float>");
-    if (!f64) {
-        if (b3) hipLaunchKernelGGL((wt_along_denoise_kernel<float, 5>), grid, block, lds, c->stream, a);
-        else hipLaunchKernelGGL((wt_along_denoise_kernel<float, 3>), grid, block, lds, c->stream, a);
-    } else {
-        if (b3) hipLaunchKernelGGL((wt_along_denoise_kernel<double, 5>), grid, block, lds, c->stream, a);
-        else hipLaunchKernelGGL((wt_along_denoise_kernel<double, 3>), grid, block, lds, c->stream, a);
-    }
+    lines_by_type_family(b->itemsize, b->family, [&](auto t, auto k) {
+        hipLaunchKernelGGL((wt_along_denoise_kernel<decltype(t), decltype(k)::value>), grid, block, lds, c->stream, a);
+    });
     WT_HIP(hipGetLastError());
     b->has_sum = true;
     return 0;

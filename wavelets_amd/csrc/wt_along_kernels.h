@@ -4,13 +4,11 @@
 // neighbours in memory.  A workgroup takes one outer index and a tile of TI neighbouring signals, loads all N samples
 // of the tile into LDS as [n][ti] in contiguous runs of TI elements, filters along n with the lanes running along ti,
 // and writes every plane once in the layout of the input: no transpose anywhere.
-// The arithmetic is the signal unit's (wt_signal_smooth of wt_signals_kernels.h, the point text of its thresholded
-// sum), so every sample carries the bits of transform_signals / denoise_signals on the transposed stack.  gfx950 only.
+// The arithmetic is the signal unit's - wt_signal_smooth, wt_signal_point and the median helpers of
+// wt_signal_common.h, which both units include - so every sample carries the bits of transform_signals /
+// denoise_signals on the transposed stack.  gfx950 only.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#define WT_SIGNALS_FILTER_ONLY       // (the signal unit's own sum kernels are definitions: not a second time)
-#include "wt_signals_kernels.h"      // wt_signal_smooth, WT_SIGNALS_LDS_BYTES and the headers of the point text
+#include "wt_signal_common.h"      // WT_SIGNALS_LDS_BYTES, wt_signal_smooth, wt_signal_point and the median helpers
 
 // The tile: the two ping-pong buffers of N x TI elements share the signal unit's 64 KiB (WT_SIGNALS_LDS_BYTES).  A
 // CHOSEN budget, not a measured optimum.  TI is the largest power of two that fits, at most WT_ALONG_MAX_TILE - and it
@@ -115,7 +113,7 @@ __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_decompose_kernel(Wt
 template <typename T>
 __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_abs_median_kernel(WtAlongArgs a)
 {
-    typedef typename std::conditional<sizeof(T) == 8, unsigned long long, uint32_t>::type U;
+    typedef typename WtSignalKey<T>::U U;
     extern __shared__ __align__(16) unsigned char wt_along_lds[];
     const int total = a.N << a.lg;
     U *key = reinterpret_cast<U *>(wt_along_lds);
@@ -125,14 +123,10 @@ __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_abs_median_kernel(W
     const int ti = threadIdx.x & (a.TI - 1);
     wt_along_load(a, src, base, i0);
     __syncthreads();
-    const U sign = (U)1 << (8 * sizeof(T) - 1);
     for (int e = threadIdx.x; e < total; e += WT_ALONG_THREADS) {
         const int n = e >> a.lg;
         const T c = a.k5 ? wt_along_smooth<T, 5>(src, n, ti, a.N, a.lg, 1) : wt_along_smooth<T, 3>(src, n, ti, a.N, a.lg, 1);
-        const T w = src[e] - c;
-        U u;
-        memcpy(&u, &w, sizeof(T));
-        key[e] = u & ~sign;
+        key[e] = wt_signal_abs_key(src[e] - c);
     }
     __syncthreads();
     for (int e = total + threadIdx.x; e < (a.n2 << a.lg); e += WT_ALONG_THREADS) key[e] = ~(U)0;
@@ -141,8 +135,7 @@ __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_abs_median_kernel(W
     for (int k = 2; k <= a.n2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int e = threadIdx.x; e < pairs; e += WT_ALONG_THREADS) {
-                const int t = e >> a.lg;
-                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));      // the rows (lo, lo + j) of column ti
+                const int lo = WT_SIGNAL_PAIR_LO(e >> a.lg, j);            // the rows (lo, lo + j) of column ti
                 const int alo = (lo << a.lg) + ti, ahi = ((lo + j) << a.lg) + ti;
                 const U x = key[alo], y = key[ahi];
                 const bool up = (lo & k) == 0;
@@ -156,36 +149,15 @@ __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_abs_median_kernel(W
     }
     if ((int)threadIdx.x < a.TI && i0 + ti < a.ic) {
         const int klo = (a.N - 1) / 2;
-        const U ulo = key[(klo << a.lg) + ti], uhi = (a.N & 1) ? ulo : key[((klo + 1) << a.lg) + ti];
-        T lo, hi;
-        memcpy(&lo, &ulo, sizeof(T));
-        memcpy(&hi, &uhi, sizeof(T));
+        const T med = wt_signal_median<T>(key, (klo << a.lg) + ti, ((klo + 1) << a.lg) + ti, a.N);
         const int64_t o = blockIdx.x / (unsigned)a.tiles;
-        reinterpret_cast<T *>(a.out)[o * a.ic + i0 + ti] = (a.N & 1) ? lo : (lo + hi) / (T)2;
+        reinterpret_cast<T *>(a.out)[o * a.ic + i0 + ti] = med;
     }
-}
-
-// the point of the thresholded sum on detail plane k < n_den: the text of wt_signals_denoise_sum_kernel<T>.
-// float: wt_sig, the weight rounded to float; tau <= 0: the significance is one
-__device__ __forceinline__ float wt_along_point(float c, double t, double, double wgtd, int soft)
-{
-#pragma clang fp contract(off)
-    const float tauf = (float)t, wgt = (float)wgtd, nn = 1.f;
-    const float sgn = t > 0.0 ? wt_sig(c, tauf * nn, t * (double)nn, soft) : 1.f;
-    return c * (wgt * sgn);
-}
-// double: wt_sig64_inv with the host's 1 / tau
-__device__ __forceinline__ double wt_along_point(double v, double tau, double inv_tau, double wgt, int soft)
-{
-#pragma clang fp contract(off)
-    double sg = 1.0;
-    if (tau > 0.0) sg = wt_sig64_inv(v, tau, inv_tau, soft);
-    return v * (wgt * sg);
 }
 
 // Coefficients.denoise over the first n_den planes + np.sum(planes, axis=0) of every signal of the block
 // (watroo/wavelets.py:145-149, utils.py:98), fused with the transform: the tile is loaded and decomposed in LDS as in
-// wt_along_decompose_kernel, every detail sample is thresholded and weighted as it appears (wt_along_point) and added
+// wt_along_decompose_kernel, every detail sample is thresholded and weighted as it appears (wt_signal_point) and added
 // to its owner's register - in plane order, starting from plane 0, contraction off - the last smooth plane is added,
 // and ONLY the sum is written.  A thread owns elements e = tid + 256 r of the tile through every scale (at most
 // 8192 / 256 = 32 floats or 16 doubles: the LDS budget bounds the register array) and with them one column, so it
@@ -225,7 +197,7 @@ __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_denoise_kernel(WtAl
                 const T c = wt_along_smooth<T, K>(p, e >> a.lg, ti, a.N, a.lg, d);
                 q[e] = c;
                 T w = p[e] - c;
-                if (den) w = wt_along_point(w, tau, inv_tau, wgt, a.soft);
+                if (den) w = wt_signal_point(w, tau, inv_tau, wgt, a.soft);
                 acc[r] = s == 0 ? w : acc[r] + w;
             }
         }

@@ -2,6 +2,7 @@
 // a signal in its 1-D branch (watroo/wavelets.py:65-69 under :408-444); the per-signal call of this library runs it
 // as a 1 x N image, one launch per scale.  This unit runs M signals in one launch, a workgroup per signal, the scales
 // in LDS (wt_signals_kernels.h), and gives every signal the bits of the per-signal call.
+// The host text it shares with the axis unit (wt_along.hip) is wt_lines_host.h, the device text wt_signal_common.h.
 //
 // Device memory of a wt_signals for M signals of N samples over `max_level` scales, Np = N rounded up to the
 // 16-byte group:  in (M, Np) | planes (M, max_level + 1, Np) | sum (M, Np) | medians (M) | the threshold table.
@@ -10,7 +11,7 @@
 #include <cstring>
 #include <vector>
 
-#include "wt_host.h"
+#include "wt_lines_host.h"
 #include "wt_signals_kernels.h"
 #include "wt_unit_probe.h"
 
@@ -40,9 +41,7 @@ extern "C" int wt_signals_ok(int family, int64_t n_samples, int level, int items
 
 static void signals_free(wt_signals *b, int *bad)
 {
-    void *dev[] = {b->in, b->planes, b->sum, b->medians, b->d_tab};
-    for (void *q : dev)
-        if (q && hipFree(q) != hipSuccess) *bad = 1;
+    lines_free({b->in, b->planes, b->sum, b->medians, b->d_tab}, bad);
     if (b->h_tab && hipHostFree(b->h_tab) != hipSuccess) *bad = 1;
     if (b->h_med && hipHostFree(b->h_med) != hipSuccess) *bad = 1;
 }
@@ -75,28 +74,10 @@ extern "C" int wt_signals_create(wt_ctx *ctx, int n_signals, int n_samples, int 
     // (the padding of every row is read by the 16-byte loads and by the thresholded sum, never handed out: finite from the start)
     if (e == hipSuccess) e = hipMemsetAsync(b->in, 0, row * n_signals, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(b->planes, 0, row * n_signals * (max_level + 1), ctx->stream);
-    if (e != hipSuccess) {
-        int bad = 0;
-        signals_free(b, &bad);
-        delete b;
-        wt_set_error("wt_signals_create: HIP error %d (%s)", (int)e, hipGetErrorString(e));
-        return 2;
-    }
-    *out = b;
-    return 0;
+    return lines_created(b, out, e, "wt_signals_create", signals_free);
 }
 
-extern "C" int wt_signals_destroy(wt_signals *b)
-{
-    if (!b) return 0;
-    WtGuard guard_(b->ctx);
-    (void)hipStreamSynchronize(b->ctx->stream);
-    int bad = 0;
-    signals_free(b, &bad);
-    delete b;
-    if (bad) WT_FAIL("wt_signals_destroy: a device buffer could not be released");
-    return 0;
-}
+extern "C" int wt_signals_destroy(wt_signals *b) { return lines_destroy(b, "wt_signals_destroy", signals_free); }
 
 extern "C" int wt_signals_info(wt_signals *b, int64_t *info)
 {
@@ -113,19 +94,12 @@ static int signals_check(const wt_signals *b, int first, int count, const char *
     return 0;
 }
 
-// rows of N elements between a host block (pitch N) and device rows (pitch Np): one linear copy where the pitches agree
+// rows of N elements between a host block (pitch N) and device rows (pitch Np)
 static int signals_copy(wt_signals *b, void *dev, void *host, size_t rows, bool up)
 {
-    const size_t w = (size_t)b->N * b->itemsize, dp = (size_t)b->Np * b->itemsize;
-    hipStream_t st = b->ctx->stream;
-    if (up) {
-        if (w == dp) WT_HIP(hipMemcpyAsync(dev, host, w * rows, hipMemcpyHostToDevice, st));
-        else WT_HIP(hipMemcpy2DAsync(dev, dp, host, w, w, rows, hipMemcpyHostToDevice, st));
-    } else {
-        if (w == dp) WT_HIP(hipMemcpyAsync(host, dev, w * rows, hipMemcpyDeviceToHost, st));
-        else WT_HIP(hipMemcpy2DAsync(host, w, dev, dp, w, rows, hipMemcpyDeviceToHost, st));
-    }
-    WT_HIP(hipStreamSynchronize(st));          // the caller's block is free (or filled) when this returns
+    const size_t w = (size_t)b->N * b->itemsize;
+    WT_TRY(lines_copy(b->ctx->stream, dev, (size_t)b->Np * b->itemsize, host, w, w, rows, up));
+    WT_HIP(hipStreamSynchronize(b->ctx->stream));          // the caller's block is free (or filled) when this returns
     return 0;
 }
 
@@ -145,16 +119,12 @@ extern "C" int wt_signals_decompose(wt_signals *b, int count, int level)
     wt_ctx *c = b->ctx;
     const size_t lds = 2 * (size_t)b->Np * b->itemsize;
     if (lds > WT_SIGNALS_LDS_BYTES) WT_FAIL("wt_signals_decompose: %zu bytes of LDS per signal", lds);
-    const bool b3 = b->family == WT_B3SPLINE;
     const dim3 grid((unsigned)count), block(WT_SIGNALS_THREADS);
     ProfScope ps(c, b->itemsize == 8 ? "wt_signals_decompose_kernel<double>" : "wt_signals_decompose_kernel<float>");
-    if (b->itemsize == 4) {
-        if (b3) hipLaunchKernelGGL((wt_signals_decompose_kernel<float, 5>), grid, block, lds, c->stream, (const float *)b->in, (float *)b->planes, b->N, b->Np, level);
-        else hipLaunchKernelGGL((wt_signals_decompose_kernel<float, 3>), grid, block, lds, c->stream, (const float *)b->in, (float *)b->planes, b->N, b->Np, level);
-    } else {
-        if (b3) hipLaunchKernelGGL((wt_signals_decompose_kernel<double, 5>), grid, block, lds, c->stream, (const double *)b->in, (double *)b->planes, b->N, b->Np, level);
-        else hipLaunchKernelGGL((wt_signals_decompose_kernel<double, 3>), grid, block, lds, c->stream, (const double *)b->in, (double *)b->planes, b->N, b->Np, level);
-    }
+    lines_by_type_family(b->itemsize, b->family, [&](auto t, auto k) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((wt_signals_decompose_kernel<T, decltype(k)::value>), grid, block, lds, c->stream, (const T *)b->in, (T *)b->planes, b->N, b->Np, level);
+    });
     WT_HIP(hipGetLastError());
     b->level = level;
     return 0;
@@ -173,12 +143,11 @@ extern "C" int wt_signals_abs_median(wt_signals *b, int count, void *medians)
     const int64_t stride = (int64_t)(b->level + 1) * b->Np;         // plane 0 of one signal to plane 0 of the next
     {
         ProfScope ps(c, b->itemsize == 8 ? "wt_signals_abs_median_kernel<double>" : "wt_signals_abs_median_kernel<float>");
-        if (b->itemsize == 4)
-            hipLaunchKernelGGL(wt_signals_abs_median_kernel<float>, dim3((unsigned)count), dim3(WT_SIGNALS_THREADS), lds, c->stream, (const float *)b->planes, stride,
-                               b->N, n2, (float *)b->medians);
-        else
-            hipLaunchKernelGGL(wt_signals_abs_median_kernel<double>, dim3((unsigned)count), dim3(WT_SIGNALS_THREADS), lds, c->stream, (const double *)b->planes, stride,
-                               b->N, n2, (double *)b->medians);
+        lines_by_type(b->itemsize, [&](auto t) {
+            typedef decltype(t) T;
+            hipLaunchKernelGGL(wt_signals_abs_median_kernel<T>, dim3((unsigned)count), dim3(WT_SIGNALS_THREADS), lds, c->stream, (const T *)b->planes, stride, b->N, n2,
+                               (T *)b->medians);
+        });
     }
     WT_HIP(hipGetLastError());
     // all medians in one host round trip
@@ -208,7 +177,7 @@ extern "C" int wt_signals_denoise_sum(wt_signals *b, int count, int n_den, const
             const double t = tau[(size_t)f * n_den + k];
             row[k] = t;
             if (f64) {
-                row[n_den + k] = t > 0.0 ? 1.0 / t : 0.0;          // (the host's IEEE division, as wt64_denoise_sum)
+                row[n_den + k] = lines_inv_tau(t);
                 row[2 * n_den + k] = wgt[(size_t)f * n_den + k];
             } else {
                 row[n_den + k] = wgt[(size_t)f * n_den + k];
@@ -228,8 +197,7 @@ extern "C" int wt_signals_denoise_sum(wt_signals *b, int count, int n_den, const
     a.soft = soft;
     const unsigned grid = (unsigned)std::min<int64_t>((a.groups + WT_SIGNALS_THREADS - 1) / WT_SIGNALS_THREADS, (int64_t)c->num_cus * 32);
     ProfScope ps(c, f64 ? "wt_signals_denoise_sum_kernel<double>" : "wt_signals_denoise_sum_kernel<float>");
-    if (f64) hipLaunchKernelGGL(wt_signals_denoise_sum_kernel<double>, dim3(grid), dim3(WT_SIGNALS_THREADS), 0, c->stream, a);
-    else hipLaunchKernelGGL(wt_signals_denoise_sum_kernel<float>, dim3(grid), dim3(WT_SIGNALS_THREADS), 0, c->stream, a);
+    lines_by_type(b->itemsize, [&](auto t) { hipLaunchKernelGGL(wt_signals_denoise_sum_kernel<decltype(t)>, dim3(grid), dim3(WT_SIGNALS_THREADS), 0, c->stream, a); });
     WT_HIP(hipGetLastError());
     return 0;
 }

@@ -4,47 +4,7 @@
 // signal is read from HBM once, its scales ping-pong between two LDS buffers, and every plane is written once.
 // Every sample gets the bits of the per-signal call.  gfx950 only.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include "wt_internal.h"
-#include "wt_device.h"
-#include "wt_math64.h"
-#include "wt_stencil.h"      // wt_sig: the float32 significance of the per-signal thresholded sum
-
-// LDS of one workgroup: the two ping-pong buffers of a signal.  A CHOSEN budget, not a measured optimum: 64 KiB lets
-// two workgroups share the 160 KiB of a CU, and it admits N <= 8192 in float32 and N <= 4096 in float64.  Longer
-// signals keep the per-signal route (wt_signals_ok).
-#define WT_SIGNALS_LDS_BYTES 65536
-#define WT_SIGNALS_THREADS 256
-
-// c_{s+1}(x) from the K samples v[j] = c_s(R(x + (j - hw) d)), R = the 'mirror' rule (wt_refl_b, border 2).
-// float: what the per-scale stencil kernels compute on a 1 x N image under that border (wt_stencil.h): the x taps
-// of wt_hrow_filter - a product, then an FMA chain in tap order - and then WtVert::emit's y taps.  The K rows of the
-// y pass all reflect onto the one row, so they hold the same row sum h; their products with the taps round, which is
-// why the y pass is kept: a plain 1-D filter gives other bits.
-template <int K>
-__device__ __forceinline__ float wt_signal_smooth(const float (&v)[K])
-{
-#pragma clang fp contract(off)
-    float h = wt_tap_s<K, float>(0) * v[0];
-#pragma unroll
-    for (int j = 1; j < K; ++j) h = fmaf(wt_tap_s<K, float>(j), v[j], h);
-    float o = wt_tap_s<K, float>(0) * h;
-#pragma unroll
-    for (int j = 1; j < K; ++j) o = fmaf(wt_tap_s<K, float>(j), h, o);
-    return o;
-}
-// double: what wt64_decompose takes for a signal (smooth64 in wt_f64.h: wt64_rows_kernel / wt64_rows2_kernel of
-// wt_kernels_f64.h, no column pass for a 1 x N image under the 'mirror' border) - the row filter alone.
-template <int K>
-__device__ __forceinline__ double wt_signal_smooth(const double (&v)[K])
-{
-#pragma clang fp contract(off)
-    double acc = wt_tap_s<K, double>(0) * v[0];
-#pragma unroll
-    for (int j = 1; j < K; ++j) acc = fma(wt_tap_s<K, double>(j), v[j], acc);
-    return acc;
-}
+#include "wt_signal_common.h"      // the LDS budget, wt_signal_smooth, wt_signal_point and the median helpers: shared with wt_along_kernels.h
 
 // AtrousTransform.atrous_standard of every signal (watroo/wavelets.py:408-444 over the 1-D branch of convolution(),
 // :65-69).  Grid x = the signal, 256 threads.  in: signals Np elements apart (Np a multiple of the 16-byte group, the
@@ -95,26 +55,20 @@ __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_decompose_kerne
 template <typename T>
 __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_abs_median_kernel(const T *plane, int64_t stride, int N, int n2, T *medians)
 {
-    typedef typename std::conditional<sizeof(T) == 8, unsigned long long, uint32_t>::type U;
+    typedef typename WtSignalKey<T>::U U;
     extern __shared__ __align__(16) unsigned char wt_signals_lds[];
     U *key = reinterpret_cast<U *>(wt_signals_lds);
     const T *w = plane + (int64_t)blockIdx.x * stride;
-    const U sign = (U)1 << (8 * sizeof(T) - 1);
     for (int i = threadIdx.x; i < n2; i += WT_SIGNALS_THREADS) {
         U u = ~(U)0;
-        if (i < N) {
-            const T t = w[i];
-            memcpy(&u, &t, sizeof(T));
-            u &= ~sign;
-        }
+        if (i < N) u = wt_signal_abs_key(w[i]);
         key[i] = u;
     }
     __syncthreads();
     for (int k = 2; k <= n2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int t = threadIdx.x; t < (n2 >> 1); t += WT_SIGNALS_THREADS) {
-                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));      // the pair (lo, lo + j)
-                const int hi = lo + j;
+                const int lo = WT_SIGNAL_PAIR_LO(t, j), hi = lo + j;
                 const U x = key[lo], y = key[hi];
                 const bool up = (lo & k) == 0;
                 if ((x > y) == up) {
@@ -127,23 +81,15 @@ __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_abs_median_kern
     }
     if (threadIdx.x == 0) {
         const int klo = (N - 1) / 2;
-        const U ulo = key[klo], uhi = (N & 1) ? ulo : key[klo + 1];
-        T lo, hi;
-        memcpy(&lo, &ulo, sizeof(T));
-        memcpy(&hi, &uhi, sizeof(T));
-        medians[blockIdx.x] = (N & 1) ? lo : (lo + hi) / (T)2;
+        medians[blockIdx.x] = wt_signal_median<T>(key, klo, klo + 1, N);
     }
 }
 
-// (the thresholded sum is two explicit specialisations - definitions, not templates: a unit that includes this header
-//  for the filter text alone, as wt_along_kernels.h does, leaves them out with WT_SIGNALS_FILTER_ONLY)
-#ifndef WT_SIGNALS_FILTER_ONLY
 // Coefficients.denoise over the first n_den planes of every signal + np.sum(planes, axis=0) (watroo/wavelets.py:
 // 145-149, utils.py:98), from the planes in HBM: the per-signal wt_denoise_sum / wt64_denoise_sum with one row of
 // thresholds and one of weights per signal.  A lane owns one 16-byte group; g = groups per signal (Np / PX).
-// float: the point text of wt_denoise_sum_kernel (wt_kernels_apps.h) - wt_sig, the weight rounded to float as
-// wt_denoise_sum rounds it, the sum in plane order, contraction off.  tab[signal * 2 * n_den + k] = tau (<= 0: the
-// significance is one), [+ n_den + k] = the weight.
+// Every thresholded sample is wt_signal_point's (wt_signal_common.h), the sum in plane order, contraction off.
+// float: tab[signal * 2 * n_den + k] = tau (<= 0: the significance is one), [+ n_den + k] = the weight.
 struct WtSignalsSumArgs {
     const void *planes;     // (signal, n, Np)
     void *dst;              // (signal, Np)
@@ -163,19 +109,14 @@ __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_denoise_sum_ker
         const int r = (int)(i - f * a.g);
         const double *ft = a.tab + f * 2 * a.n_den;
         const float *p = reinterpret_cast<const float *>(a.planes) + f * (int64_t)a.n * a.Np + 4 * r;
-        const float nn[4] = {1.f, 1.f, 1.f, 1.f};
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         for (int k = 0; k < a.n; ++k) {
             const float4 v = *reinterpret_cast<const float4 *>(p + (int64_t)k * a.Np);
             float c[4] = {v.x, v.y, v.z, v.w};
             if (k < a.n_den) {
-                const double t = ft[k];
-                const float tauf = (float)t, wgt = (float)ft[a.n_den + k];
+                const double t = ft[k], wgt = ft[a.n_den + k];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float sgn = t > 0.0 ? wt_sig(c[j], tauf * nn[j], t * (double)nn[j], a.soft) : 1.f;
-                    c[j] = c[j] * (wgt * sgn);
-                }
+                for (int j = 0; j < 4; ++j) c[j] = wt_signal_point(c[j], t, 0.0, wgt, a.soft);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[j] = k == 0 ? c[j] : acc[j] + c[j];
@@ -184,8 +125,10 @@ __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_denoise_sum_ker
     }
 }
 
-// double: the expressions of wt64_denoise_sum_kernel (wt_kernels_f64.h) without a noise plane - wt_sig64_inv with the
-// host's 1 / tau.  tab[signal * 3 * n_den + k] = tau, [+ n_den + k] = 1 / tau, [+ 2 * n_den + k] = the weight.
+// double: tab[signal * 3 * n_den + k] = tau, [+ n_den + k] = the host's 1 / tau, [+ 2 * n_den + k] = the weight.
+// The expressions of the double wt_signal_point, written out for the two samples of a group under ONE test of tau:
+// through two calls of the point the compiler emits two tests and another register allocation - the same values,
+// another instruction stream - so this one kernel keeps its text ("One core for the two 1-D engines").
 template <>
 __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_denoise_sum_kernel<double>(WtSignalsSumArgs a)
 {
@@ -208,4 +151,3 @@ __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_denoise_sum_ker
         reinterpret_cast<double2 *>(a.dst)[i] = acc;
     }
 }
-#endif      // WT_SIGNALS_FILTER_ONLY

@@ -52,31 +52,38 @@ def _noise_list(noise, n):
     return [noise] * n
 
 
+def _engine_family(dtype, level, scaling_function):
+    """the family (an int) the 1-D engines run this element type, level and scaling function with, or None: native
+    float32 or native float64; an int level (not a bool), 1 <= level <= 24; a built-in scaling function with its own taps"""
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)) or not dtype.isnative:
+        return None
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 1 <= level <= _lib.SIGNAL_MAX_LEVEL:
+        return None
+    if _needs_generic(scaling_function):
+        return None
+    try:
+        fam = _family_of(scaling_function(1), 1)
+    except (ValueError, NotImplementedError):
+        return None
+    return fam if isinstance(fam, int) else None
+
+
+def _signals_family(signals, level, scaling_function, noise_per_signal=()):
+    """the family the signal engine computes this stack with, or None (signals_eligible)"""
+    if not isinstance(signals, np.ndarray) or signals.ndim != 2 or signals.shape[0] < 1 or signals.shape[1] < 1:
+        return None
+    fam = _engine_family(signals.dtype, level, scaling_function)
+    if fam is None or noise_per_signal is None or any(n is not None and not _real_scalar(n) for n in noise_per_signal):
+        return None
+    return fam if _lib.signals_ok(fam, signals.shape[1], int(level), signals.dtype.itemsize) else None
+
+
 def signals_eligible(signals, level, scaling_function=B3spline, noise_per_signal=()):
     """True when the signal engine computes this stack (host logic): an (M, N) ndarray, M >= 1 and N >= 1, of native
     float32 or native float64; a built-in scaling function with its own taps; an int level, 1 <= level <= 24; signals
     within the LDS budget of the kernel (_lib.signals_ok: at most 8192 float32 or 4096 float64 samples); noise
     entries that are None or real scalars.  Everything else runs the per-signal loop."""
-    if not isinstance(signals, np.ndarray) or signals.ndim != 2:
-        return False
-    if signals.dtype not in (np.dtype(np.float32), np.dtype(np.float64)) or not signals.dtype.isnative:
-        return False
-    M, N = signals.shape
-    if M < 1 or N < 1:
-        return False
-    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 1 <= level <= _lib.SIGNAL_MAX_LEVEL:
-        return False
-    if _needs_generic(scaling_function):
-        return False
-    try:
-        fam = _family_of(scaling_function(1), 1)
-    except (ValueError, NotImplementedError):
-        return False
-    if not isinstance(fam, int):
-        return False
-    if noise_per_signal is None or any(n is not None and not _real_scalar(n) for n in noise_per_signal):
-        return False
-    return _lib.signals_ok(fam, N, int(level), signals.dtype.itemsize)
+    return _signals_family(signals, level, scaling_function, noise_per_signal) is not None
 
 
 def _transform_one(signal, level, scaling_function):
@@ -109,6 +116,19 @@ def _hand_over(res, out):
     return out
 
 
+def _result(res, shape, dtype):
+    """(the checked `out`, or without one a page-locked block for the result: the downloads land at PCIe rate; the context)"""
+    ctx = _lib.default_context()
+    return (_lib.host_empty(shape, ctx, dtype) if res is None else res), ctx
+
+
+def _thresholds(weights, scaling_function):
+    """(sigma_e, entries, whether any threshold needs a noise level) of Coefficients._denoise_sum(weights): sigma = weights,
+    every weight 1, no fused schedule for a signal"""
+    entries, _, _ = _interleave_split([], len(weights), list(weights), (1,) * len(weights))
+    return scaling_function(1).sigma_e(), entries, any(s != 0 for _, s, _ in entries)
+
+
 def _chunks(M, N, level, itemsize):
     """the chunk rule of a stack over device memory (_lib.signal_chunks)"""
     return _lib.signal_chunks(M, N, level, itemsize=itemsize)
@@ -120,18 +140,16 @@ def transform_signals(signals, level, scaling_function=B3spline, out=None):
     :65-69), one launch per chunk of signals."""
     sig = _as_signals(signals)
     M, N = len(sig), len(sig[0])
-    if not signals_eligible(sig, level, scaling_function):
+    fam = _signals_family(sig, level, scaling_function)
+    if fam is None:
         # (the loop raises what the per-signal call raises; `out` is checked first where the result's shape is known)
         if isinstance(level, (int, np.integer)) and level >= 0:
             out = _target(out, (M, level + 1, N), _loop_dtype(sig))
         return _hand_over(np.stack([_transform_one(s, level, scaling_function) for s in sig]), out)
     level = int(level)
-    res = _target(out, (M, level + 1, N), sig.dtype)
-    ctx = _lib.default_context()
-    if res is None:
-        res = _lib.host_empty((M, level + 1, N), ctx, sig.dtype)         # page-locked: the downloads land at PCIe rate
+    res, ctx = _result(_target(out, (M, level + 1, N), sig.dtype), (M, level + 1, N), sig.dtype)
     chunks = _chunks(M, N, level, sig.dtype.itemsize)
-    sb = _lib.acquire_signals(ctx, max(nf for _, nf in chunks), N, _family_of(scaling_function(1), 1), level, sig.dtype)
+    sb = _lib.acquire_signals(ctx, max(nf for _, nf in chunks), N, fam, level, sig.dtype)
     try:
         for f0, nf in chunks:
             sb.upload(sig[f0:f0 + nf])
@@ -151,21 +169,16 @@ def denoise_signals(signals, weights, scaling_function=B3spline, noise=None, sof
     nl = _noise_list(noise, M)
     level = len(weights)
     # (the thresholded sum folds level + 1 planes in one launch, as the per-signal call's does)
-    if not signals_eligible(sig, level, scaling_function, nl) or level + 1 > _lib.MAX_SUM_PLANES:
+    fam = _signals_family(sig, level, scaling_function, nl)
+    if fam is None or level + 1 > _lib.MAX_SUM_PLANES:
         out = _target(out, (M, N), _loop_dtype(sig))
         return _hand_over(np.stack([denoise(s, weights, scaling_function, n_i, soft_threshold=soft_threshold)
                                     for s, n_i in zip(sig, nl)]), out)
     res = _target(out, (M, N), sig.dtype)
-    sf = scaling_function(1)
-    sigma_e = sf.sigma_e()
-    # Coefficients._denoise_sum(weights): sigma = weights, every weight 1, no fused schedule for a signal
-    entries, _, _ = _interleave_split([], level, list(weights), (1,) * level)
-    need_noise = any(s != 0 for _, s, _ in entries)
-    ctx = _lib.default_context()
-    if res is None:
-        res = _lib.host_empty((M, N), ctx, sig.dtype)
+    sigma_e, entries, need_noise = _thresholds(weights, scaling_function)
+    res, ctx = _result(res, (M, N), sig.dtype)
     chunks = _chunks(M, N, level, sig.dtype.itemsize)
-    sb = _lib.acquire_signals(ctx, max(nf for _, nf in chunks), N, _family_of(sf, 1), level, sig.dtype)
+    sb = _lib.acquire_signals(ctx, max(nf for _, nf in chunks), N, fam, level, sig.dtype)
     try:
         for f0, nf in chunks:
             noises = nl[f0:f0 + nf]
