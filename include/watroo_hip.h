@@ -880,10 +880,24 @@ int wt_signals_abs_median(wt_signals *signals, int count, void *medians);
  * wgt[count * n_den], one row per signal; tau <= 0: significance one.  At most 16 planes (level <= 15) */
 int wt_signals_denoise_sum(wt_signals *signals, int count, int n_den, const double *tau, const double *wgt,
                            int soft);
+/* {sum, sum of squares} of every plane 0 .. level of signals 0 .. count-1 of the last wt_signals_decompose, in double
+ * (c.std() and np.mean(power) of watroo/utils.py:176-189 as wt_reduce / wt64_reduce give them per signal):
+ * moments[count * (level + 1) * 2], one host round trip.  The fold order is fixed: the same bits run to run */
+int wt_signals_moments(wt_signals *signals, int count, double *moments);
+/* the per-scale loop of wow and np.sum(coefficients, axis=0) of signals 0 .. count-1 (watroo/utils.py:174-205 on a
+ * 1-D array, without gamma sum; wt_wow_scale / wt_wow_update / wt_plane_sum and their wt64_ forms per signal) in one
+ * launch: tau[count * n_scales] (tau <= 0: significance one) and factor[count * (n_scales + 1)] (w * power_norm, the
+ * last plane's divided by its local power), one row per signal; `whitening`: the detail planes are divided by the
+ * square root of their local power conv_s(c^2), clipped at 1e-15 (utils.py:193-196).  n_scales: the level of the last
+ * wt_signals_decompose.  The sum goes where wt_signals_download_sum finds it; with `write_planes` the whitened
+ * planes replace the planes in place (wt_signals_download_planes) */
+int wt_signals_wow_sum(wt_signals *signals, int count, int n_scales, const double *tau, const double *factor,
+                       int whitening, int soft, int write_planes);
 /* the planes of signals [first, first + count) of the last wt_signals_decompose -> host (count, level + 1, n_samples)
  * (Coefficients.data per signal, watroo/wavelets.py:426-444) */
 int wt_signals_download_planes(wt_signals *signals, int first, int count, void *host);
-/* the sums of wt_signals_denoise_sum of signals [first, first + count) -> host (count, n_samples) (utils.py:98) */
+/* the sums of wt_signals_denoise_sum / wt_signals_wow_sum of signals [first, first + count) -> host (count, n_samples)
+ * (utils.py:98, :205) */
 int wt_signals_download_sum(wt_signals *signals, int first, int count, void *host);
 
 /* ---- the 1-D transform along an axis that is not the last one (wt_along) -------------------------------------------

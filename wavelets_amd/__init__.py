@@ -14,6 +14,7 @@ from .sequence import map_frames, denoise_many, wow_many, transform_many  # noqa
 from .batch import transform_stack, denoise_stack, wow_stack, enhance_stack, richardson_lucy_stack  # noqa: F401  (stacks of same-shape frames: one launch per pass)
 from .signals import transform_signals, denoise_signals, signals_eligible  # noqa: F401  (stacks of 1-D signals of one length: a workgroup per signal, the scales in LDS)
 from .along import transform_along, denoise_along, along_eligible  # noqa: F401  (the 1-D transform along any axis of an array: a tile of neighbouring signals per workgroup)
+from .wow_signals import wow_signals, wow_along, wow_signals_eligible  # noqa: F401  (wow of stacks of 1-D signals and along an axis: the per-scale loop of a signal in one launch)
 from .rng import normal_frames  # noqa: F401  (seeded standard-normal frames, filled on the GPU)
 
 __version__ = '0.1.0'

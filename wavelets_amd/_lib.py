@@ -299,7 +299,10 @@ SIGNATURES = {
     "wt_signals_abs_median": (_c.c_int, [_vp, _c.c_int, _vp]),
     "wt_signals_denoise_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                                           _c.c_int]),
-    "wt_signals_download_planes": (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp]),
+    "wt_signals_moments": (_c.c_int, [_vp, _c.c_int, _c.POINTER(_c.c_double)]),
+    "wt_signals_wow_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
+                                      _c.c_int, _c.c_int, _c.c_int]),
+    "wt_signals_download_planes":(_c.c_int, [_vp, _c.c_int, _c.c_int, _vp]),
     "wt_signals_download_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp]),
     # the 1-D transform along an axis that is not the last one (wt_along)
     "wt_along_ok": (_c.c_int, [_c.c_int, _i64, _i64, _c.c_int, _c.c_int]),
@@ -1435,19 +1438,22 @@ def signals_ok(family, n_samples, level, itemsize):
     return bool(load().wt_signals_ok(int(family), int(n_samples), int(level), int(itemsize)))
 
 
-def signal_bytes(n_samples, level, itemsize=4):
+def signal_bytes(n_samples, level, itemsize=4, wow=False):
     """device bytes one signal of a SignalBatch takes: the signal, planes 0..level and the sum, at the 16-byte pitch
-    (host logic, wt_signals_create)"""
-    return (level + 3) * _batch_pitch(n_samples, itemsize) * itemsize
+    (host logic, wt_signals_create); `wow`: and the moments and the two tables of the wow route, 4 * level + 3 doubles
+    (wt_signals_moments, wt_signals_wow_sum)"""
+    return (level + 3) * _batch_pitch(n_samples, itemsize) * itemsize + (8 * (4 * level + 3) if wow else 0)
 
 
-def signal_chunks(n, n_samples, level, budget=None, itemsize=4):
+def signal_chunks(n, n_samples, level, budget=None, itemsize=4, wow=False):
     """[(first signal, signals)] of a stack of `n` signals, in the manner of batch_chunks: as many signals per chunk
-    as `budget` bytes of device memory allow (default BATCH_BYTES; at least one), the last chunk the remainder"""
+    as `budget` bytes of device memory allow (default BATCH_BYTES; at least one), the last chunk the remainder;
+    `wow`: signal_bytes of the wow route, and at most (2^31 - 1) // (level + 1) signals (a workgroup per plane)"""
     if n < 0:
         raise ValueError("negative signal count")
     budget = BATCH_BYTES if budget is None else budget
-    per = max(1, min(int(budget // signal_bytes(n_samples, level, itemsize)), (1 << 31) - 1))
+    cap = ((1 << 31) - 1) // (level + 1) if wow else (1 << 31) - 1
+    per = max(1, min(int(budget // signal_bytes(n_samples, level, itemsize, wow)), cap))
     return [(f0, min(per, n - f0)) for f0 in range(0, n, per)]
 
 
@@ -1520,6 +1526,25 @@ class SignalBatch(_LinesBase):
         """Coefficients.denoise + the plane sum of signals 0 .. nf-1: one row of thresholds and one of weights per signal"""
         n, ta, wa = _enhance_rows(nf, taus, wgts)
         self._call("denoise_sum", nf, n, ta, wa, int(soft))
+
+    def moments(self, nf):
+        """(nf, level + 1, 2) float64: {sum, sum of squares} of every plane of signals 0 .. nf-1 of the last decompose,
+        folded in double in a fixed order: one host round trip"""
+        out = np.empty((nf, self.level + 1, 2), np.float64)
+        self._call("moments", nf, out.ctypes.data_as(_c.POINTER(_c.c_double)))
+        return out
+
+    def wow_sum(self, nf, taus, factors, whitening, soft=True, write_planes=False):
+        """the per-scale loop of wow + the plane sum of signals 0 .. nf-1: `taus` (nf, level) thresholds (0 =
+        significance one), `factors` (nf, level + 1); `write_planes`: the whitened planes replace the planes"""
+        ta = np.ascontiguousarray(taus, dtype=np.float64)
+        fa = np.ascontiguousarray(factors, dtype=np.float64)
+        if ta.shape != (nf, self.level) or fa.shape != (nf, self.level + 1):
+            raise ValueError(f"thresholds of shape {ta.shape} and factors of shape {fa.shape} != ({nf}, {self.level}) and "
+                             f"({nf}, {self.level + 1})")
+        dp = _c.POINTER(_c.c_double)
+        self._call("wow_sum", nf, self.level, ta.ctypes.data_as(dp), fa.ctypes.data_as(dp), int(bool(whitening)), int(bool(soft)),
+                   int(bool(write_planes)))
 
     def _target(self, out, shape):
         if out is None:

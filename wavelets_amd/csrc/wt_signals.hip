@@ -7,6 +7,8 @@
 // Device memory of a wt_signals for M signals of N samples over `max_level` scales, Np = N rounded up to the
 // 16-byte group:  in (M, Np) | planes (M, max_level + 1, Np) | sum (M, Np) | medians (M) | the threshold table.
 // A call with fewer scales packs its planes (signal, level + 1, Np) at the head of `planes`.
+// Only a stack that runs wow (wt_signals_moments / wt_signals_wow_sum) also holds, from its first such call on, the
+// moments (M, max_level + 1, 2) and the wow tables (M, 2 * max_level + 1) of doubles: 4 * max_level + 3 doubles per signal.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -24,6 +26,8 @@ struct wt_signals {
     void *in = nullptr, *planes = nullptr, *sum = nullptr, *medians = nullptr;
     double *d_tab = nullptr, *h_tab = nullptr;      // [signal][3 * WT_MAX_SUM_PLANES]
     void *h_med = nullptr;
+    double *d_mom = nullptr, *h_mom = nullptr;      // wow: [signal][max_level + 1][2], allocated by the first wt_signals_moments
+    double *d_wow = nullptr, *h_wow = nullptr;      // wow: tau [signal][level] | factor [signal][level + 1], by the first wt_signals_wow_sum
 };
 
 static inline int signals_pitch(int64_t N, int itemsize) { return (int)((N + 16 / itemsize - 1) / (16 / itemsize) * (16 / itemsize)); }
@@ -41,9 +45,9 @@ extern "C" int wt_signals_ok(int family, int64_t n_samples, int level, int items
 
 static void signals_free(wt_signals *b, int *bad)
 {
-    lines_free({b->in, b->planes, b->sum, b->medians, b->d_tab}, bad);
-    if (b->h_tab && hipHostFree(b->h_tab) != hipSuccess) *bad = 1;
-    if (b->h_med && hipHostFree(b->h_med) != hipSuccess) *bad = 1;
+    lines_free({b->in, b->planes, b->sum, b->medians, b->d_tab, b->d_mom, b->d_wow}, bad);
+    for (void *q : {(void *)b->h_tab, b->h_med, (void *)b->h_mom, (void *)b->h_wow})
+        if (q && hipHostFree(q) != hipSuccess) *bad = 1;
 }
 
 extern "C" int wt_signals_create(wt_ctx *ctx, int n_signals, int n_samples, int family, int max_level, int itemsize, wt_signals **out)
@@ -198,6 +202,80 @@ extern "C" int wt_signals_denoise_sum(wt_signals *b, int count, int n_den, const
     const unsigned grid = (unsigned)std::min<int64_t>((a.groups + WT_SIGNALS_THREADS - 1) / WT_SIGNALS_THREADS, (int64_t)c->num_cus * 32);
     ProfScope ps(c, f64 ? "wt_signals_denoise_sum_kernel<double>" : "wt_signals_denoise_sum_kernel<float>");
     lines_by_type(b->itemsize, [&](auto t) { hipLaunchKernelGGL(wt_signals_denoise_sum_kernel<decltype(t)>, dim3(grid), dim3(WT_SIGNALS_THREADS), 0, c->stream, a); });
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+// a device block and its page-locked twin of `bytes` bytes, allocated on first use
+static int signals_pair(double **dev, double **host, size_t bytes)
+{
+    if (!*dev) WT_HIP(hipMalloc((void **)dev, bytes));
+    if (!*host) WT_HIP(hipHostMalloc((void **)host, bytes, 0));
+    return 0;
+}
+
+extern "C" int wt_signals_moments(wt_signals *b, int count, double *moments)
+{
+    WT_TRY(signals_check(b, 0, count, "wt_signals_moments"));
+    if (!moments) WT_FAIL("wt_signals_moments: null pointer");
+    if (b->level < 1) WT_FAIL("wt_signals_moments: no transform in the stack (wt_signals_decompose first)");
+    const int64_t blocks = (int64_t)count * (b->level + 1);
+    if (blocks > 0x7fffffff) WT_FAIL("wt_signals_moments: %lld planes in one launch", (long long)blocks);
+    WtGuard guard_(b->ctx);
+    wt_ctx *c = b->ctx;
+    WT_TRY(signals_pair(&b->d_mom, &b->h_mom, (size_t)b->n * (b->max_level + 1) * 2 * sizeof(double)));
+    {
+        ProfScope ps(c, b->itemsize == 8 ? "wt_signals_moments_kernel<double>" : "wt_signals_moments_kernel<float>");
+        lines_by_type(b->itemsize, [&](auto t) {
+            typedef decltype(t) T;
+            hipLaunchKernelGGL(wt_signals_moments_kernel<T>, dim3((unsigned)blocks), dim3(WT_SIGNALS_THREADS), 0, c->stream, (const T *)b->planes, b->N, b->Np,
+                               b->d_mom);
+        });
+    }
+    WT_HIP(hipGetLastError());
+    // all moments in one host round trip
+    WT_HIP(hipMemcpyAsync(b->h_mom, b->d_mom, (size_t)blocks * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    WT_HIP(hipStreamSynchronize(c->stream));
+    memcpy(moments, b->h_mom, (size_t)blocks * 2 * sizeof(double));
+    return 0;
+}
+
+extern "C" int wt_signals_wow_sum(wt_signals *b, int count, int n_scales, const double *tau, const double *factor, int whitening, int soft, int write_planes)
+{
+    WT_TRY(signals_check(b, 0, count, "wt_signals_wow_sum"));
+    if (b->level < 1) WT_FAIL("wt_signals_wow_sum: no transform in the stack (wt_signals_decompose first)");
+    if (n_scales != b->level) WT_FAIL("wt_signals_wow_sum: %d scales, the stack holds a transform over %d", n_scales, b->level);
+    if (!tau || !factor) WT_FAIL("wt_signals_wow_sum: null tau / factor");
+    WtGuard guard_(b->ctx);
+    wt_ctx *c = b->ctx;
+    const int L = b->level;
+    const size_t lds = whitening ? 2 * (size_t)b->Np * b->itemsize : 0;
+    if (lds > WT_SIGNALS_LDS_BYTES) WT_FAIL("wt_signals_wow_sum: %zu bytes of LDS per signal", lds);
+    WT_TRY(signals_pair(&b->d_wow, &b->h_wow, (size_t)b->n * (2 * b->max_level + 1) * sizeof(double)));
+    // (the tables of the previous call may still be read: the staging block is reused only behind the stream)
+    WT_HIP(hipStreamSynchronize(c->stream));
+    const size_t nt = (size_t)count * L, nf = (size_t)count * (L + 1);
+    memcpy(b->h_wow, tau, nt * sizeof(double));
+    memcpy(b->h_wow + nt, factor, nf * sizeof(double));
+    WT_HIP(hipMemcpyAsync(b->d_wow, b->h_wow, (nt + nf) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    WtSignalsWowArgs a{};
+    a.planes = b->planes;
+    a.sum = b->sum;
+    a.tau = b->d_wow;
+    a.factor = b->d_wow + nt;
+    a.N = b->N;
+    a.Np = b->Np;
+    a.level = L;
+    a.soft = soft;
+    a.write_planes = write_planes;
+    const dim3 grid((unsigned)count), block(WT_SIGNALS_THREADS);
+    ProfScope ps(c, b->itemsize == 8 ? "wt_signals_wow_kernel<double>" : "wt_signals_wow_kernel<float>");
+    lines_by_type_family(b->itemsize, b->family, [&](auto t, auto k) {
+        typedef decltype(t) T;
+        constexpr int K = decltype(k)::value;
+        if (whitening) hipLaunchKernelGGL((wt_signals_wow_kernel<T, K, true>), grid, block, lds, c->stream, a);
+        else hipLaunchKernelGGL((wt_signals_wow_kernel<T, K, false>), grid, block, 0, c->stream, a);
+    });
     WT_HIP(hipGetLastError());
     return 0;
 }

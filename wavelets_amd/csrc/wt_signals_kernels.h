@@ -151,3 +151,148 @@ __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_denoise_sum_ker
         reinterpret_cast<double2 *>(a.dst)[i] = acc;
     }
 }
+
+// {sum, sum of squares} of every plane of every signal, in double (c.std() / np.mean(power) of watroo/utils.py:176-189;
+// what wt_reduce / wt64_reduce give the per-signal call, in another fold order).  Grid x = signal * nplanes + plane
+// (the planes of a stack lie back to back, Np elements each), 256 threads.
+// THE ORDER IS FIXED, so the doubles are the same run to run: thread t folds its samples t, t + 256, t + 512, ... in
+// index order, the 256 partial results go to LDS and a tree of fixed shape - partner t + 128, then t + 64, ... t + 1,
+// a barrier between the steps - folds them; thread 0 writes moments[(signal * nplanes + plane) * 2 + {0, 1}].  No
+// atomics.  Every partial result is a double PAIR {value, what the additions so far rounded away} (wt_two_sum; the
+// square's own rounding error comes from one FMA), and the pair is folded into one double only at the very end: the
+// factors of wow take sumsq / N - mean^2, which cancels - for a smooth plane on a pedestal to 1e-4 of its terms - so
+// a rounding error of the sums is worth thousands of ulps of the result ("wow of 1-D signals").
+__device__ __forceinline__ void wt_two_sum(double &hi, double &lo, double v, double vlo)
+{
+#pragma clang fp contract(off)
+    const double s = hi + v;
+    const double t = s - hi;
+    const double e = (hi - (s - t)) + (v - t);
+    hi = s;
+    lo = lo + (e + vlo);
+}
+template <typename T>
+__global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_moments_kernel(const T *planes, int N, int Np, double *moments)
+{
+#pragma clang fp contract(off)
+    __shared__ double red[4][WT_SIGNALS_THREADS];
+    const T *p = planes + (int64_t)blockIdx.x * Np;
+    double s = 0.0, sl = 0.0, q = 0.0, ql = 0.0;
+    for (int x = threadIdx.x; x < N; x += WT_SIGNALS_THREADS) {
+        const double v = (double)p[x];
+        const double vv = v * v;
+        wt_two_sum(s, sl, v, 0.0);
+        wt_two_sum(q, ql, vv, fma(v, v, -vv));
+    }
+    red[0][threadIdx.x] = s;
+    red[1][threadIdx.x] = sl;
+    red[2][threadIdx.x] = q;
+    red[3][threadIdx.x] = ql;
+    __syncthreads();
+    for (int off = WT_SIGNALS_THREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+            wt_two_sum(s, sl, red[0][threadIdx.x + off], red[1][threadIdx.x + off]);
+            wt_two_sum(q, ql, red[2][threadIdx.x + off], red[3][threadIdx.x + off]);
+            red[0][threadIdx.x] = s;
+            red[1][threadIdx.x] = sl;
+            red[2][threadIdx.x] = q;
+            red[3][threadIdx.x] = ql;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        moments[(int64_t)blockIdx.x * 2] = s + sl;
+        moments[(int64_t)blockIdx.x * 2 + 1] = q + ql;
+    }
+}
+
+// The per-scale loop of wow + np.sum(coefficients, axis=0) of every signal (watroo/utils.py:174-205 on a 1-D array,
+// h = 0: no gamma sum), from the planes in HBM: per signal what wt_wow_scale / wt_wow_update per scale and
+// wt_plane_sum give (wt64_smooth of the squares + wt64_wow_update + wt64_plane_sum in double), in ONE launch.
+// Grid x = the signal, 256 threads.  A thread owns samples x = tid + 256 r through every scale (at most 8192 / 256 =
+// 32 floats or 16 doubles: the LDS budget bounds the register array, as in wt_along_denoise_kernel) and keeps their
+// running sum in registers - in plane order, starting from plane 0, contraction off.
+// POWER (whitening): per detail scale s the thread squares its samples of plane s into an LDS buffer of Np elements;
+// after ONE barrier the local power is conv_s(c^2) = wt_signal_smooth over the 'mirror' rule at dilation 2^s, read
+// from that buffer.  Two buffers alternate with s: a wave that has passed the barrier of scale s + 1 writes the buffer
+// of scale s + 2 = the buffer of scale s, which every wave has finished reading before it reached that barrier.
+// Without POWER there is no LDS traffic and no barrier.  Every sample is then wt_wow_point's (wt_stencil.h): the
+// significance, then factor * rsq(clip(power)) - the text of the per-frame and the batched 2-D kernels.  The last
+// plane is multiplied by its factor and added.  tau: (signal, level) doubles, <= 0: significance one (the double
+// point takes the quotient c / tau, as wt64_wow_kernel does: a staged 1 / tau would give other bits); factor:
+// (signal, level + 1) doubles, rounded to T as the per-signal call rounds them.
+// HBM traffic: sizeof(T) * (level + 1) read and sizeof(T) written per sample; with write_planes the planes are written
+// back in place, sizeof(T) * (level + 1) more.  LDS: lane l of a wave writes element x0 + l and reads element
+// x0 + l + const (away from the borders): consecutive lanes, consecutive addresses, no bank conflicts.
+struct WtSignalsWowArgs {
+    void *planes;            // (signal, level + 1, Np)
+    void *sum;               // (signal, Np)
+    const double *tau;       // (signal, level)
+    const double *factor;    // (signal, level + 1)
+    int N, Np, level, soft, write_planes;
+};
+template <typename T, int K, bool POWER>
+__global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_wow_kernel(WtSignalsWowArgs a)
+{
+#pragma clang fp contract(off)
+    constexpr int ITEMS = WT_SIGNALS_LDS_BYTES / 2 / (int)sizeof(T) / WT_SIGNALS_THREADS;
+    constexpr int hw = K / 2;
+    extern __shared__ __align__(16) unsigned char wt_signals_lds[];
+    T *sq0 = reinterpret_cast<T *>(wt_signals_lds);
+    T *sq1 = sq0 + a.Np;
+    const int64_t sig = blockIdx.x;
+    T *pl = reinterpret_cast<T *>(a.planes) + sig * (int64_t)(a.level + 1) * a.Np;
+    const double *taus = a.tau + sig * a.level;
+    const double *fac = a.factor + sig * (a.level + 1);
+    T acc[ITEMS];
+#pragma unroll
+    for (int r = 0; r < ITEMS; ++r) acc[r] = (T)0;
+    for (int s = 0; s < a.level; ++s) {
+        const int d = 1 << s;
+        const double tau = taus[s];
+        const T tauf = (T)tau, factor = (T)fac[s];
+        T *w = pl + (int64_t)s * a.Np;
+        T *sq = (s & 1) ? sq1 : sq0;
+        T c[ITEMS];
+#pragma unroll
+        for (int r = 0; r < ITEMS; ++r) {
+            const int x = (int)threadIdx.x + r * WT_SIGNALS_THREADS;
+            c[r] = (T)0;
+            if (x < a.N) {
+                c[r] = w[x];
+                if constexpr (POWER) sq[x] = c[r] * c[r];
+            }
+        }
+        if constexpr (POWER) __syncthreads();
+#pragma unroll
+        for (int r = 0; r < ITEMS; ++r) {
+            const int x = (int)threadIdx.x + r * WT_SIGNALS_THREADS;
+            if (x < a.N) {
+                T pw = (T)0;
+                if constexpr (POWER) {
+                    T v[K];
+#pragma unroll
+                    for (int j = 0; j < K; ++j) v[j] = sq[wt_refl_b(x + (j - hw) * d, a.N, d, 2)];
+                    pw = wt_signal_smooth<K>(v);
+                }
+                T g = (T)0;
+                const T val = wt_wow_point(c[r], pw, POWER, (T)1, tau, tauf, a.soft, factor, g);
+                acc[r] = s == 0 ? val : acc[r] + val;
+                if (a.write_planes) w[x] = val;
+            }
+        }
+    }
+    T *last = pl + (int64_t)a.level * a.Np;
+    T *dst = reinterpret_cast<T *>(a.sum) + sig * a.Np;
+    const T factor = (T)fac[a.level];
+#pragma unroll
+    for (int r = 0; r < ITEMS; ++r) {
+        const int x = (int)threadIdx.x + r * WT_SIGNALS_THREADS;
+        if (x < a.N) {
+            T g = (T)0;
+            const T val = wt_wow_point(last[x], (T)0, false, (T)1, 0.0, (T)0, a.soft, factor, g);
+            dst[x] = acc[r] + val;
+            if (a.write_planes) last[x] = val;
+        }
+    }
+}
