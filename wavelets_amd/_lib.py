@@ -1660,9 +1660,11 @@ class AlongBatch(_LinesBase):
         isz = self.dtype.itemsize
         if a.dtype != self.dtype or a.ndim != len(lead) + 3 or a.shape[-2] != self.n_samples or a.shape[:-3] != tuple(lead):
             raise ValueError(f"a {self.dtype} block of shape {tuple(lead)} + (., {self.n_samples}, .) expected (got {a.dtype} {a.shape})")
-        pitch = a.strides[-2] // isz
-        if (ni > 1 and a.strides[-1] != isz) or a.strides[-2] % isz or pitch < ni \
-                or (no > 1 and a.strides[-3] != self.n_samples * a.strides[-2]):
+        # (numpy keeps any stride for an axis of length one: the one row of a slice then lies where the slices say)
+        row = a.strides[-2] if self.n_samples > 1 else a.strides[-3] if no > 1 else ni * isz
+        pitch = row // isz
+        if (ni > 1 and a.strides[-1] != isz) or row % isz or pitch < ni \
+                or (no > 1 and a.strides[-3] != self.n_samples * row):
             raise ValueError("rows of contiguous elements at one pitch expected")
         return pitch
 

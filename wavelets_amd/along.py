@@ -12,6 +12,10 @@ bit for bit - and transform_signals equals the per-signal loop bit for bit (ref 
 The thresholds are the per-signal path's own (wavelets._interleave_split, _tau_row, _noise_from_median), evaluated for
 all signals of a chunk at once (_tau_table).
 
+Non-finite samples follow signals.py: a signal holding NaN or inf gets what the per-signal call gives it (a NaN median
+makes NaN thresholds in _noise_table / _tau_table, which the kernel takes as significance one), nothing is raised, and
+its neighbours in the tile keep their bits.
+
 The last axis is the signal engine's own layout and goes there.  Inputs the axis engine does not cover (along_eligible:
 more than 512 samples along the axis, other element types, custom scaling functions ...) are transposed on the host,
 go through transform_signals / denoise_signals and return what those return."""

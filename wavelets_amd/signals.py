@@ -10,6 +10,12 @@ bit for bit.  The reference transforms a signal in the 1-D branch of convolution
 'mirror' border); the per-signal call runs it as a 1 x N image, a launch per scale and an upload and a download per
 call.  The thresholds are the per-signal path's own (wavelets._interleave_split, _tau_row, _noise_from_median).
 
+Non-finite samples are data, as in the per-signal call, and nothing is raised for them: NaN spreads through the
+filter's reach, an inf becomes NaN in w_0, and the MAD median is the middle key of the sorted magnitudes with NaN above
+infinity - finite while fewer than half of |w_0| are NaN (np.median would say NaN), else NaN, which gives NaN
+thresholds and leaves that signal unthresholded.  Other signals of the stack are not touched ("Non-finite
+samples in the 1-D engines").
+
 Inputs the engine does not cover run the per-signal loop and return what the loop returns; signals_eligible says
 which."""
 import numpy as np

@@ -305,13 +305,37 @@ def _wow_needs_moments(s, n_scales, preserve_variance, whitening, h):
     return preserve_variance or (s == n_scales and whitening and h < 1)
 
 
-def _wow_factor(s, n_scales, w, moments, npix, preserve_variance, whitening, h, ft):
+# The one-pass variance sumsq / N - mean^2 of two doubles is off by up to some 6 u of the MEAN SQUARE (u = 2^-53: two
+# sums each within an ulp of the exact one, a division, a square, a difference), so the standard deviation is off by
+# 3 u / r relative, r = variance / mean square, and that error goes straight into the whitened last plane.  float64 wow
+# is held to 1e-10 of max|ref| between its routes, which fold the sums in different orders.  Below r = 1e-3 the
+# standard deviation is taken from the samples instead: at the gate the one-pass value is within 3 u / 1e-3 = 3.4e-13
+# of the two-pass one, 1/300 of that bound, so two routes whose sums put them on different sides of the gate still
+# agree, and so do routes on one side.
+_STD_CANCELS = 1e-3
+
+
+def _std_cancels(moments, npix):
+    """whether sumsq / N - mean^2 of a plane's {sum, sumsq} is too cancelled to give the standard deviation: a
+    variance below _STD_CANCELS of the mean square - a smooth last plane on a pedestal of some 30 of its standard
+    deviations, or a flat one.  NaN or inf moments: False."""
+    mean, meansq = moments[0] / npix, moments[1] / npix
+    return bool(meansq > 0 and meansq - mean * mean < _STD_CANCELS * meansq)
+
+
+def _plane_std(plane):
+    """np.std of a downloaded plane in float64 (two passes, as the reference's c.std(), ref:180,186)"""
+    return float(np.std(np.asarray(plane, np.float64)))
+
+
+def _wow_factor(s, n_scales, w, moments, npix, preserve_variance, whitening, h, ft, std=None):
     """w * power_norm / local_power of scale s (ref:176-191, 203) in the data's compute type `ft`; the per-pixel
-    local power of the detail scales is the kernel's.  moments: plan.reduce(s) where _wow_needs_moments, else None"""
+    local power of the detail scales is the kernel's.  moments: plan.reduce(s) where _wow_needs_moments, else None;
+    std: the plane's standard deviation where the caller took it from the samples (_std_cancels)"""
     if moments is not None:
-        tot, tot2, _, _ = moments
+        tot, tot2 = moments[0], moments[1]
         mean = tot / npix
-        std = ft(np.sqrt(max(tot2 / npix - mean * mean, 0.0)))
+        std = ft(np.sqrt(max(tot2 / npix - mean * mean, 0.0))) if std is None else ft(std)
         rms = ft(np.sqrt(tot2 / npix))
     if preserve_variance:                                                 # ref:178-184
         power_norm = std if s == n_scales else rms
@@ -391,7 +415,10 @@ def _wow_scales(plan, coefficients, n_scales, nplanes, recomposition_weights, sd
         if s and s == early_at and hasattr(plan, "plane_sum_early") and plan.plane_sum_early(s, PLANE_OUT):
             early = s
         moments = plan.reduce(s) if _wow_needs_moments(s, n_scales, preserve_variance, whitening, h) else None
-        factor = _wow_factor(s, n_scales, w, moments, npix, preserve_variance, whitening, h, ft)
+        std = None
+        if moments is not None and s == n_scales and coefficients._ndim == 1 and _std_cancels(moments, npix):
+            std = _plane_std(plan.download(s))           # signals: the last plane on a pedestal (one row over PCIe)
+        factor = _wow_factor(s, n_scales, w, moments, npix, preserve_variance, whitening, h, ft, std)
         if s == n_scales:                                                 # ref:185-191
             plan.wow_update(s, PLANE_NONE, 0.0, soft_threshold, PLANE_NONE, factor, gplane)
         else:

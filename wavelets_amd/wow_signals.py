@@ -14,6 +14,15 @@ part and the stack's results equal the per-signal loop bit for bit; with them th
 _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments and _wow_factor, wavelets._tau_row and
 _noise_from_median.
 
+Non-finite samples follow signals.py: nothing is raised for them, the median is the per-signal call's, and without
+moments a signal holding NaN or inf gets the per-signal call's bits.  With moments its sums are NaN or inf, so are its
+factors, and the row is NaN where the loop's is; the other signals of the stack are not touched.
+
+A signal on a pedestal (or a flat one), whose last plane has a variance below 1e-3 of its mean square, gets that
+plane's standard deviation from its samples in float64 instead of from sumsq / N - mean^2, whose cancellation error
+would exceed what the two routes may differ by (utils._STD_CANCELS; the per-signal call does the same): the planes of
+each such signal come down once more, one small download per signal.
+
 Inputs the engine does not cover run the per-signal loop and return what the loop returns; wow_signals_eligible says
 which."""
 import warnings
@@ -22,7 +31,8 @@ import numpy as np
 
 from . import _lib
 from .wavelets import B3spline, _tau_row, _noise_from_median, _result_dtype
-from .utils import wow, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments, _wow_factor
+from .utils import (wow, _wow_n_scales, _wow_scale_limit, _wow_lists, _wow_needs_moments, _wow_factor, _std_cancels,
+                    _plane_std)
 from .signals import _as_signals, _noise_list, _signals_family, _loop_dtype, _target, _hand_over, _result
 from .along import _checked, _moved, _back
 
@@ -76,18 +86,37 @@ def _chunks(M, N, level, itemsize):
     return _lib.signal_chunks(M, N, level, itemsize=itemsize, wow=True)
 
 
-def _factor_rows(moments, base, needs, L, w, npix, preserve_variance, whitening, ft):
+def _factor_rows(moments, base, needs, L, w, npix, preserve_variance, whitening, ft, stds=None):
     """(signals, L + 1) rows of utils._wow_factor: `base` where a scale needs no moments, else from the signal's
-    {sum, sumsq} of that plane (`moments`: nested lists of Python floats, as Plan.reduce hands them over)"""
+    {sum, sumsq} of that plane (`moments`: nested lists of Python floats, as Plan.reduce hands them over); `stds`: per
+    signal None or the standard deviation of its last plane taken from the samples (_cancelled_stds)"""
     if not needs:
         return [base] * len(moments)
     rows = []
-    for mom in moments:
+    for i, mom in enumerate(moments):
         row = list(base)
         for s in needs:
-            row[s] = _wow_factor(s, L, w[s], (mom[s][0], mom[s][1], None, None), npix, preserve_variance, whitening, 0, ft)
+            std = stds[i] if stds is not None and s == L else None
+            row[s] = _wow_factor(s, L, w[s], (mom[s][0], mom[s][1], None, None), npix, preserve_variance, whitening, 0, ft, std)
         rows.append(row)
     return rows
+
+
+def _cancelled_stds(sb, nf, moments, needs, L, npix):
+    """per signal None, or - where sumsq / N - mean^2 of the last plane has cancelled away (utils._std_cancels: a
+    pedestal, a flat signal) - np.std of that plane from its samples, as the per-signal call takes it.  Only those
+    signals come down, before wow_sum updates them: the L + 1 planes of each (the engine downloads whole signals),
+    where the per-signal call downloads the one plane"""
+    if L not in needs:
+        return None
+    bad = [i for i, mom in enumerate(moments) if _std_cancels(mom[L], npix)]
+    if not bad:
+        return None
+    host = _lib.host_empty((1, L + 1, int(npix)), sb.ctx, sb.dtype)
+    stds = [None] * nf
+    for i in bad:
+        stds[i] = _plane_std(sb.download_planes(1, out=host, f0=i)[0, L])
+    return stds
 
 
 def _tau_rows(entries, noises, sigma_e, soft):
@@ -156,7 +185,8 @@ def wow_signals(signals, scaling_function=B3spline, n_scales=None, weights=[], w
             taus = _tau_rows(entries, noises, sigma_e, soft) if need_noise else [[0.0] * L] * nf
             # (the moments of the planes before any update: the reference takes `power` before the significance, ref:177-184)
             moments = sb.moments(nf).tolist() if needs else [None] * nf
-            factors = _factor_rows(moments, base, needs, L, w, float(N), preserve_variance, whitening, ft)
+            stds = _cancelled_stds(sb, nf, moments, needs, L, float(N)) if needs else None
+            factors = _factor_rows(moments, base, needs, L, w, float(N), preserve_variance, whitening, ft, stds)
             sb.wow_sum(nf, taus, factors, whitening, soft, return_coefficients)
             sb.download_sum(nf, out=res[f0:f0 + nf])
             if return_coefficients:
