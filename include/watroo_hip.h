@@ -872,6 +872,11 @@ int wt_signals_upload(wt_signals *signals, int first, int count, const void *hos
 /* AtrousTransform.atrous_standard of signals 0 .. count-1 over `level` scales (watroo/wavelets.py:408-444 over
  * :65-69): one launch; HBM traffic sizeof(element) * (level + 2) bytes per sample */
 int wt_signals_decompose(wt_signals *signals, int count, int level);
+/* wt_signals_decompose with `flags`: bit 0 = Anscombe - every sample goes through generalized_anscombe(x) =
+ * 2 sqrt(max(x + 3/8, 0)) (watroo/wavelets.py:14-21 with alpha = 1, g = 0, sigma = 0; watroo/utils.py:93-94) as it is
+ * loaded, the bits of wt_anscombe / wt64_anscombe; the signals in device memory stay as they are.  The same launch, the
+ * same traffic.  Any other bit is refused; flags = 0 is wt_signals_decompose.  A mode of the call, never of the stack */
+int wt_signals_decompose_ex(wt_signals *signals, int count, int level, int flags);
 /* np.median(np.abs(w_0)) of signals 0 .. count-1 (Coefficients.get_noise, watroo/wavelets.py:126-127), exact and
  * with the even / odd rule of wt_abs_median: medians[count] of the stack's element type, one host round trip */
 int wt_signals_abs_median(wt_signals *signals, int count, void *medians);
@@ -880,6 +885,12 @@ int wt_signals_abs_median(wt_signals *signals, int count, void *medians);
  * wgt[count * n_den], one row per signal; tau <= 0: significance one.  At most 16 planes (level <= 15) */
 int wt_signals_denoise_sum(wt_signals *signals, int count, int n_den, const double *tau, const double *wgt,
                            int soft);
+/* wt_signals_denoise_sum with `flags`: bit 0 = Anscombe - every sum goes through the inverse (x / 2)^2 - 3/8
+ * (watroo/wavelets.py:16-17; watroo/utils.py:99-100) before its one store, the bits of wt_anscombe / wt64_anscombe
+ * with inverse = 1.  tau refers to the transformed data (utils.py:95-97).  Any other bit is refused; flags = 0 is
+ * wt_signals_denoise_sum */
+int wt_signals_denoise_sum_ex(wt_signals *signals, int count, int n_den, const double *tau, const double *wgt,
+                              int soft, int flags);
 /* {sum, sum of squares} of every plane 0 .. level of signals 0 .. count-1 of the last wt_signals_decompose, in double
  * (c.std() and np.mean(power) of watroo/utils.py:176-189 as wt_reduce / wt64_reduce give them per signal):
  * moments[count * (level + 1) * 2], one host round trip.  The fold order is fixed: the same bits run to run */
@@ -931,10 +942,19 @@ int wt_along_decompose(wt_along *along, int level);
  * the even / odd rule of wt_signals_abs_median: scale 0 in LDS only, no plane written; medians[n_outer * n_inner] of
  * the stack's element type, one host round trip */
 int wt_along_abs_median(wt_along *along, void *medians);
+/* wt_along_abs_median with `flags`: bit 0 = Anscombe - the medians of generalized_anscombe(chunk) (watroo/wavelets.py:
+ * 14-21; the noise level of watroo/utils.py:95-97 refers to the transformed data), the forward transform applied as the
+ * chunk is loaded.  Any other bit is refused; flags = 0 is wt_along_abs_median */
+int wt_along_abs_median_ex(wt_along *along, void *medians, int flags);
 /* Coefficients.denoise + np.sum(coefficients, axis=0) of every signal of the chunk (watroo/wavelets.py:145-149,
  * utils.py:97-98) fused with the transform over `level` scales: only the sum is written.  tau[n_outer * n_inner *
  * n_den], one row per signal (tau <= 0: significance one), wgt[n_den] shared; n_den <= level <= 15 */
 int wt_along_denoise(wt_along *along, int level, int n_den, const double *tau, const double *wgt, int soft);
+/* wt_along_denoise with `flags`: bit 0 = Anscombe - generalized_anscombe as the chunk is loaded and its inverse on the
+ * sum before the one store (watroo/wavelets.py:14-21; watroo/utils.py:93-94, 99-100): denoise(..., anscombe=True) of
+ * every signal in the same launch at the same traffic.  Any other bit is refused; flags = 0 is wt_along_denoise */
+int wt_along_denoise_ex(wt_along *along, int level, int n_den, const double *tau, const double *wgt, int soft,
+                        int flags);
 /* the planes of the last wt_along_decompose -> host: plane s at host + s * plane_stride elements, each as the rows of
  * wt_along_upload (Coefficients.data per signal, watroo/wavelets.py:426-444) */
 int wt_along_download_planes(wt_along *along, void *host, int64_t pitch, int64_t plane_stride);

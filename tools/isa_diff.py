@@ -42,6 +42,7 @@ def demangle(names):
 
 def norm_name(n):
     n = re.sub(r"^void ", "", n).split("(")[0]
+    n = n.replace(", false>", ">")          # a trailing compile-time switch the refactor adds, off: the kernel as it was
     n = n.replace("<float, ", "<").replace("FusedArgsT<float>", "FusedArgs")
     return n
 

@@ -296,9 +296,12 @@ SIGNATURES = {
     "wt_signals_info": (_c.c_int, [_vp, _c.POINTER(_i64)]),
     "wt_signals_upload": (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp]),
     "wt_signals_decompose": (_c.c_int, [_vp, _c.c_int, _c.c_int]),
+    "wt_signals_decompose_ex": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int]),
     "wt_signals_abs_median": (_c.c_int, [_vp, _c.c_int, _vp]),
     "wt_signals_denoise_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                                           _c.c_int]),
+    "wt_signals_denoise_sum_ex": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
+                                             _c.c_int, _c.c_int]),
     "wt_signals_moments": (_c.c_int, [_vp, _c.c_int, _c.POINTER(_c.c_double)]),
     "wt_signals_wow_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                                       _c.c_int, _c.c_int, _c.c_int]),
@@ -312,7 +315,10 @@ SIGNATURES = {
     "wt_along_upload": (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp, _i64]),
     "wt_along_decompose": (_c.c_int, [_vp, _c.c_int]),
     "wt_along_abs_median": (_c.c_int, [_vp, _vp]),
+    "wt_along_abs_median_ex": (_c.c_int, [_vp, _vp, _c.c_int]),
     "wt_along_denoise": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.c_int]),
+    "wt_along_denoise_ex": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.c_int,
+                                       _c.c_int]),
     "wt_along_download_planes": (_c.c_int, [_vp, _vp, _i64, _i64]),
     "wt_along_download_sum": (_c.c_int, [_vp, _vp, _i64]),
 }
@@ -1427,6 +1433,7 @@ release_batch64 = release_rl_batch64 = release_batch          # (one cache for e
 # stacks of 1-D signals of one length (wt_signals): one workgroup per signal, the scales in LDS
 # ------------------------------------------------------------------------------------------
 SIGNAL_MAX_LEVEL = 24                     # wt_signals_ok: the per-scale kernels' limit
+LINES_ANSCOMBE = 1                        # bit 0 of the `flags` of the wt_signals_..._ex / wt_along_..._ex entries
 
 
 def signals_ok(family, n_samples, level, itemsize):
@@ -1512,8 +1519,13 @@ class SignalBatch(_LinesBase):
             raise ValueError(f"signals of shape {a.shape} != (., {self.n_samples})")
         self._call("upload", f0, a.shape[0], _vp(a.ctypes.data))
 
-    def decompose(self, nf, level):
-        self._call("decompose", nf, level)
+    def decompose(self, nf, level, anscombe=False):
+        """the transform of signals 0 .. nf-1; `anscombe`: of generalized_anscombe(signal), applied as the signals are
+        loaded (wt_signals_decompose_ex, flags bit 0) - the same launch"""
+        if anscombe:
+            self._call("decompose_ex", nf, level, LINES_ANSCOMBE)
+        else:
+            self._call("decompose", nf, level)
         self.level = level
 
     def abs_median(self, nf):
@@ -1522,10 +1534,14 @@ class SignalBatch(_LinesBase):
         self._call("abs_median", nf, _vp(out.ctypes.data))
         return out
 
-    def denoise_sum(self, nf, taus, wgts, soft=True):
-        """Coefficients.denoise + the plane sum of signals 0 .. nf-1: one row of thresholds and one of weights per signal"""
+    def denoise_sum(self, nf, taus, wgts, soft=True, anscombe=False):
+        """Coefficients.denoise + the plane sum of signals 0 .. nf-1: one row of thresholds and one of weights per signal;
+        `anscombe`: the inverse transform on every sum before its store (wt_signals_denoise_sum_ex, flags bit 0)"""
         n, ta, wa = _enhance_rows(nf, taus, wgts)
-        self._call("denoise_sum", nf, n, ta, wa, int(soft))
+        if anscombe:
+            self._call("denoise_sum_ex", nf, n, ta, wa, int(soft), LINES_ANSCOMBE)
+        else:
+            self._call("denoise_sum", nf, n, ta, wa, int(soft))
 
     def moments(self, nf):
         """(nf, level + 1, 2) float64: {sum, sum of squares} of every plane of signals 0 .. nf-1 of the last decompose,
@@ -1678,21 +1694,29 @@ class AlongBatch(_LinesBase):
         self._call("decompose", level)
         self.level = level
 
-    def abs_median(self):
-        """np.median(np.abs(w_0)) of every signal of the chunk, (no, ni) of the stack's type: one host round trip"""
+    def abs_median(self, anscombe=False):
+        """np.median(np.abs(w_0)) of every signal of the chunk, (no, ni) of the stack's type: one host round trip;
+        `anscombe`: of generalized_anscombe(chunk) (wt_along_abs_median_ex, flags bit 0)"""
         out = np.empty(self.chunk, self.dtype)
-        self._call("abs_median", _vp(out.ctypes.data))
+        if anscombe:
+            self._call("abs_median_ex", _vp(out.ctypes.data), LINES_ANSCOMBE)
+        else:
+            self._call("abs_median", _vp(out.ctypes.data))
         return out
 
-    def denoise(self, level, taus, wgts, soft=True):
+    def denoise(self, level, taus, wgts, soft=True, anscombe=False):
         """the fused transform + Coefficients.denoise + plane sum of the chunk: `taus` one row of thresholds per signal
-        ((no * ni, n_den) doubles, 0 = significance one), `wgts` the one row of weights"""
+        ((no * ni, n_den) doubles, 0 = significance one), `wgts` the one row of weights; `anscombe`: the forward
+        transform at the load and the inverse at the store of the same launch (wt_along_denoise_ex, flags bit 0)"""
         ta = np.ascontiguousarray(taus, dtype=np.float64)
         wa = np.ascontiguousarray(wgts, dtype=np.float64)
         n_den = wa.shape[0]
         if ta.shape != (self.chunk[0] * self.chunk[1], n_den):
             raise ValueError(f"thresholds of shape {ta.shape} != ({self.chunk[0] * self.chunk[1]}, {n_den})")
-        self._call("denoise", level, n_den, ta.ctypes.data_as(_dp), wa.ctypes.data_as(_dp), int(soft))
+        if anscombe:
+            self._call("denoise_ex", level, n_den, ta.ctypes.data_as(_dp), wa.ctypes.data_as(_dp), int(soft), LINES_ANSCOMBE)
+        else:
+            self._call("denoise", level, n_den, ta.ctypes.data_as(_dp), wa.ctypes.data_as(_dp), int(soft))
 
     def download_planes(self, out):
         """the planes of the last decompose into `out`: a (level + 1, no, n_samples, ni) view"""

@@ -175,13 +175,17 @@ def transform_along(a, level, scaling_function=B3spline, axis=0, out=None):
     return res
 
 
-def denoise_along(a, weights, scaling_function=B3spline, axis=0, noise=None, soft_threshold=True, out=None):
+def denoise_along(a, weights, scaling_function=B3spline, axis=0, noise=None, soft_threshold=True, out=None, anscombe=False):
     """a.shape: utils.denoise of every 1-D signal along `axis` (ref utils.py:83-102 on a 1-D array), float32 or float64
     as transform_along.  `noise`: None (each signal's own MAD estimate, ref wavelets.py:126-132), one real scalar, or
     an ndarray of the shape of `a` without `axis`: one level per signal.  The transform, the thresholds and the sum are
     one launch per chunk (no plane reaches device memory); only when a MAD estimate is needed a launch before it
-    brings the medians of all signals of the chunk in one round trip."""
+    brings the medians of all signals of the chunk in one round trip.
+    `anscombe`: denoise_signals(..., anscombe=True) on the transposed stack, bit for bit - hence denoise(signal, ...,
+    anscombe=True) of every signal (ref utils.py:93-94, 99-100): the forward transform where the kernels load the chunk,
+    the inverse where the sum is stored, in the same launches.  Noise levels refer to the transformed data."""
     a, axis = _checked(a, axis)
+    ans = {"anscombe": True} if anscombe else {}               # (without it: the calls as they always were)
     O, N, I = _view(a.shape, axis)
     rest = a.shape[:axis] + a.shape[axis + 1:]
     if isinstance(noise, np.ndarray) and noise.shape != rest:
@@ -192,7 +196,7 @@ def denoise_along(a, weights, scaling_function=B3spline, axis=0, noise=None, sof
         out = _target(out, a.shape, _result_dtype(a))
         sig, moved = _moved(a, axis)
         per = list(noise.reshape(-1)) if isinstance(noise, np.ndarray) else noise
-        res = _back(denoise_signals(sig, weights, scaling_function, per, soft_threshold), moved, axis, 0)
+        res = _back(denoise_signals(sig, weights, scaling_function, per, soft_threshold, **ans), moved, axis, 0)
         return _hand_over(res, out) if out is not None else np.ascontiguousarray(res)
     res = _target(out, a.shape, a.dtype)
     sigma_e, entries, need_noise = _thresholds(weights, scaling_function)       # (as denoise_signals)
@@ -213,9 +217,9 @@ def denoise_along(a, weights, scaling_function=B3spline, axis=0, noise=None, sof
                 elif noise is not None:
                     noises = np.full(no * ni, noise, dtype=np.asarray(noise).dtype)
                 else:
-                    noises = _noise_table(ab.abs_median().reshape(-1), sigma_e)       # ref wavelets.py:131-132 (lazy)
+                    noises = _noise_table(ab.abs_median(**ans).reshape(-1), sigma_e)  # ref wavelets.py:131-132 (lazy)
                 taus = _tau_table(entries, noises, sigma_e, soft_threshold)
-            ab.denoise(level, taus, wgts, soft_threshold)
+            ab.denoise(level, taus, wgts, soft_threshold, **ans)
             ab.download_sum(r3[o0:o0 + no, :, i0:i0 + ni])
     finally:
         _lib.release_along(ab)

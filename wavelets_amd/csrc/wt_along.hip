@@ -166,20 +166,25 @@ extern "C" int wt_along_decompose(wt_along *b, int level)
     return 0;
 }
 
-extern "C" int wt_along_abs_median(wt_along *b, void *medians)
+static int along_abs_median(wt_along *b, void *medians, int flags, const char *who)
 {
-    WT_TRY(along_loaded(b, "wt_along_abs_median"));
-    if (!medians) WT_FAIL("wt_along_abs_median: null pointer");
+    WT_TRY(along_loaded(b, who));
+    WT_TRY(lines_flags(flags, who));
+    if (!medians) WT_FAIL("%s: null pointer", who);
     WtGuard guard_(b->ctx);
     wt_ctx *c = b->ctx;
     WtAlongArgs a = along_args(b, b->medians);
     a.n2 = 1;
     while (a.n2 < b->N) a.n2 <<= 1;
     const size_t lds = along_lds(b);
-    if (lds > WT_SIGNALS_LDS_BYTES || (size_t)a.n2 * b->TI * b->itemsize > lds) WT_FAIL("wt_along_abs_median: %zu bytes of LDS per tile", lds);
+    if (lds > WT_SIGNALS_LDS_BYTES || (size_t)a.n2 * b->TI * b->itemsize > lds) WT_FAIL("%s: %zu bytes of LDS per tile", who, lds);
     {
         ProfScope ps(c, b->itemsize == 8 ? "wt_along_abs_median_kernel<double>" : "wt_along_abs_median_kernel<float>");
-        lines_by_type(b->itemsize, [&](auto t) { hipLaunchKernelGGL(wt_along_abs_median_kernel<decltype(t)>, along_grid(b, a), dim3(WT_ALONG_THREADS), lds, c->stream, a); });
+        lines_by_type(b->itemsize, [&](auto t) {
+            typedef decltype(t) T;
+            if (flags & WT_LINES_ANSCOMBE) hipLaunchKernelGGL((wt_along_abs_median_kernel<T, true>), along_grid(b, a), dim3(WT_ALONG_THREADS), lds, c->stream, a);
+            else hipLaunchKernelGGL((wt_along_abs_median_kernel<T, false>), along_grid(b, a), dim3(WT_ALONG_THREADS), lds, c->stream, a);
+        });
     }
     WT_HIP(hipGetLastError());
     // all medians of the chunk in one host round trip
@@ -187,15 +192,18 @@ extern "C" int wt_along_abs_median(wt_along *b, void *medians)
     WT_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
+extern "C" int wt_along_abs_median(wt_along *b, void *medians) { return along_abs_median(b, medians, 0, "wt_along_abs_median"); }
+extern "C" int wt_along_abs_median_ex(wt_along *b, void *medians, int flags) { return along_abs_median(b, medians, flags, "wt_along_abs_median_ex"); }
 
-extern "C" int wt_along_denoise(wt_along *b, int level, int n_den, const double *tau, const double *wgt, int soft)
+static int along_denoise(wt_along *b, int level, int n_den, const double *tau, const double *wgt, int soft, int flags, const char *who)
 {
-    WT_TRY(along_loaded(b, "wt_along_denoise"));
-    if (b->with_planes) WT_FAIL("wt_along_denoise: a stack with planes (wt_along_create)");
-    if (level < 1 || level > b->max_level) WT_FAIL("wt_along_denoise: %d scales outside [1, %d]", level, b->max_level);
-    if (level + 1 > WT_MAX_SUM_PLANES) WT_FAIL("wt_along_denoise: %d planes (at most %d)", level + 1, WT_MAX_SUM_PLANES);
-    if (n_den < 0 || n_den > level) WT_FAIL("wt_along_denoise: n_den %d outside [0,%d]", n_den, level);
-    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("wt_along_denoise: null tau / wgt");
+    WT_TRY(along_loaded(b, who));
+    WT_TRY(lines_flags(flags, who));
+    if (b->with_planes) WT_FAIL("%s: a stack with planes (wt_along_create)", who);
+    if (level < 1 || level > b->max_level) WT_FAIL("%s: %d scales outside [1, %d]", who, level, b->max_level);
+    if (level + 1 > WT_MAX_SUM_PLANES) WT_FAIL("%s: %d planes (at most %d)", who, level + 1, WT_MAX_SUM_PLANES);
+    if (n_den < 0 || n_den > level) WT_FAIL("%s: n_den %d outside [0,%d]", who, n_den, level);
+    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("%s: null tau / wgt", who);
     WtGuard guard_(b->ctx);
     wt_ctx *c = b->ctx;
     const bool f64 = b->itemsize == 8;
@@ -225,15 +233,26 @@ extern "C" int wt_along_denoise(wt_along *b, int level, int n_den, const double 
     a.soft = soft;
     for (int k = 0; k < n_den; ++k) a.wgt[k] = wgt[k];
     const size_t lds = along_lds(b);
-    if (lds > WT_SIGNALS_LDS_BYTES) WT_FAIL("wt_along_denoise: %zu bytes of LDS per tile", lds);
+    if (lds > WT_SIGNALS_LDS_BYTES) WT_FAIL("%s: %zu bytes of LDS per tile", who, lds);
     const dim3 grid = along_grid(b, a), block(WT_ALONG_THREADS);
     ProfScope ps(c, f64 ? "wt_along_denoise_kernel<double>" : "wt_along_denoise_kernel<float>");
     lines_by_type_family(b->itemsize, b->family, [&](auto t, auto k) {
-        hipLaunchKernelGGL((wt_along_denoise_kernel<decltype(t), decltype(k)::value>), grid, block, lds, c->stream, a);
+        typedef decltype(t) T;
+        constexpr int K = decltype(k)::value;
+        if (flags & WT_LINES_ANSCOMBE) hipLaunchKernelGGL((wt_along_denoise_kernel<T, K, true>), grid, block, lds, c->stream, a);
+        else hipLaunchKernelGGL((wt_along_denoise_kernel<T, K, false>), grid, block, lds, c->stream, a);
     });
     WT_HIP(hipGetLastError());
     b->has_sum = true;
     return 0;
+}
+extern "C" int wt_along_denoise(wt_along *b, int level, int n_den, const double *tau, const double *wgt, int soft)
+{
+    return along_denoise(b, level, n_den, tau, wgt, soft, 0, "wt_along_denoise");
+}
+extern "C" int wt_along_denoise_ex(wt_along *b, int level, int n_den, const double *tau, const double *wgt, int soft, int flags)
+{
+    return along_denoise(b, level, n_den, tau, wgt, soft, flags, "wt_along_denoise_ex");
 }
 
 extern "C" int wt_along_download_planes(wt_along *b, void *host, int64_t pitch, int64_t plane_stride)

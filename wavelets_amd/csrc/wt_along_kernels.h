@@ -40,15 +40,20 @@ __device__ __forceinline__ int64_t wt_along_tile(const WtAlongArgs &a, int *i0)
 
 // the tile of the input into LDS as [n][ti]: element e = n * TI + ti is taken by thread e % 256, so a wave reads
 // HBM runs of TI contiguous elements and writes consecutive LDS addresses.  Columns past the right edge of the chunk
-// (a partial tile) hold zeros: they are computed and never stored.
-template <typename T>
+// (a partial tile) hold zeros: they are computed and never stored.  ANS: every sample of the chunk goes through
+// wt_anscombe_fwd (wt_signal_common.h) on its way into LDS (watroo/utils.py:93-94); the block in HBM stays as it is.
+template <typename T, bool ANS>
 __device__ __forceinline__ void wt_along_load(const WtAlongArgs &a, T *buf, int64_t base, int i0)
 {
     const T *src = reinterpret_cast<const T *>(a.in) + base;
     const int total = a.N << a.lg;
     const int ti = threadIdx.x & (a.TI - 1);
     const bool ok = i0 + ti < a.ic;
-    for (int e = threadIdx.x; e < total; e += WT_ALONG_THREADS) buf[e] = ok ? src[(int64_t)(e >> a.lg) * a.ic + ti] : (T)0;
+    if constexpr (ANS) {
+        for (int e = threadIdx.x; e < total; e += WT_ALONG_THREADS) buf[e] = ok ? wt_anscombe_fwd(src[(int64_t)(e >> a.lg) * a.ic + ti]) : (T)0;
+    } else {
+        for (int e = threadIdx.x; e < total; e += WT_ALONG_THREADS) buf[e] = ok ? src[(int64_t)(e >> a.lg) * a.ic + ti] : (T)0;
+    }
 }
 
 // c_{s+1} at sample n of column ti from the buffer p of c_s, under the 'mirror' rule of the signal unit
@@ -80,7 +85,7 @@ __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_decompose_kernel(Wt
     const int64_t base = wt_along_tile(a, &i0);
     const int ti = threadIdx.x & (a.TI - 1);
     const bool ok = i0 + ti < a.ic;
-    wt_along_load(a, p, base, i0);
+    wt_along_load<T, false>(a, p, base, i0);
     __syncthreads();
     T *out = reinterpret_cast<T *>(a.out) + base + ti;
     for (int s = 0; s < a.level; ++s) {
@@ -110,7 +115,8 @@ __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_decompose_kernel(Wt
 // overwrite the input, which is dead by then (n2 <= 2 N: the keys stay within the two buffers).  A bitonic network
 // sorts every column over n2 rows; its (n2 / 2) * TI compare-exchanges of a stage are spread over the 256 threads with
 // ti fastest: consecutive lanes, consecutive LDS addresses.  out: (oc, ic) medians.
-template <typename T>
+// ANS: the medians of generalized_anscombe(block) - the noise level refers to the transformed data (watroo/utils.py:95-97).
+template <typename T, bool ANS>
 __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_abs_median_kernel(WtAlongArgs a)
 {
     typedef typename WtSignalKey<T>::U U;
@@ -121,7 +127,7 @@ __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_abs_median_kernel(W
     int i0;
     const int64_t base = wt_along_tile(a, &i0);
     const int ti = threadIdx.x & (a.TI - 1);
-    wt_along_load(a, src, base, i0);
+    wt_along_load<T, ANS>(a, src, base, i0);
     __syncthreads();
     for (int e = threadIdx.x; e < total; e += WT_ALONG_THREADS) {
         const int n = e >> a.lg;
@@ -163,7 +169,9 @@ __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_abs_median_kernel(W
 // 8192 / 256 = 32 floats or 16 doubles: the LDS budget bounds the register array) and with them one column, so it
 // reads its signal's thresholds once per scale.  HBM traffic: sizeof(T) read and sizeof(T) written per sample, plus
 // the thresholds; no plane reaches HBM.  LDS: as wt_along_decompose_kernel.
-template <typename T, int K>
+// ANS: wt_anscombe_fwd at the load and wt_anscombe_inv on the sum before its one store (watroo/utils.py:93-94, 99-100):
+// denoise(..., anscombe=True) of every signal at the same traffic, no pass of its own over the block or the sum.
+template <typename T, int K, bool ANS>
 __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_denoise_kernel(WtAlongArgs a)
 {
 #pragma clang fp contract(off)
@@ -177,7 +185,7 @@ __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_denoise_kernel(WtAl
     const int64_t base = wt_along_tile(a, &i0);
     const int ti = threadIdx.x & (a.TI - 1);
     const bool ok = i0 + ti < a.ic;
-    wt_along_load(a, p, base, i0);
+    wt_along_load<T, ANS>(a, p, base, i0);
     __syncthreads();
     const int64_t o = blockIdx.x / (unsigned)a.tiles;
     const double *ft = a.tab + (o * a.ic + i0 + ti) * (int64_t)(per * a.n_den);
@@ -210,6 +218,10 @@ __global__ __launch_bounds__(WT_ALONG_THREADS) void wt_along_denoise_kernel(WtAl
 #pragma unroll
     for (int r = 0; r < ITEMS; ++r) {
         const int e = (int)threadIdx.x + r * WT_ALONG_THREADS;
-        if (e < total && ok) dst[(int64_t)(e >> a.lg) * a.ic] = acc[r] + p[e];
+        if constexpr (ANS) {
+            if (e < total && ok) dst[(int64_t)(e >> a.lg) * a.ic] = wt_anscombe_inv(acc[r] + p[e]);
+        } else {
+            if (e < total && ok) dst[(int64_t)(e >> a.lg) * a.ic] = acc[r] + p[e];
+        }
     }
 }

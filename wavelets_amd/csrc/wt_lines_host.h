@@ -69,3 +69,12 @@ static inline void lines_by_type_family(int itemsize, int family, F f)
 
 // 1 / tau of a float64 threshold: the host's IEEE division, as wt64_denoise_sum; 0 where the significance is one
 static inline double lines_inv_tau(double t) { return t > 0.0 ? 1.0 / t : 0.0; }
+
+// `flags` of the ..._ex entries: bit 0 = Anscombe, any other bit refused.  A mode of the CALL, never of the stack: stacks
+// are cached and reused, and a mode left behind on one would silently change the next caller's result.
+#define WT_LINES_ANSCOMBE 1
+static inline int lines_flags(int flags, const char *who)
+{
+    if (flags & ~WT_LINES_ANSCOMBE) WT_FAIL("%s: flags %d (bit 0 = Anscombe; no other bit is defined)", who, flags);
+    return 0;
+}

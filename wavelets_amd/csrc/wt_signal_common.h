@@ -67,6 +67,59 @@ __device__ __forceinline__ double wt_signal_point(double v, double tau, double i
     return v * (wgt * sg);
 }
 
+// generalized_anscombe (watroo/wavelets.py:14-21) with alpha = 1, g = 0, sigma = 0 - what denoise(..., anscombe=True)
+// runs around the transform of a signal (watroo/utils.py:93-94, 99-100) - as ONE point, so that the 1-D engines
+// apply it where a sample is loaded and where the sum is stored.  The expressions are the per-signal call's device
+// kernels', step by step, with the constants their host entries derive for these arguments:
+// float: wt_anscombe_kernel (wt_kernels_apps.h) after launch_anscombe (wt_apps.hip) - forward c1 = (float)(3 / 8),
+// c2 = 0, c3 = 0; inverse c1 = 0, c2 = 0, c3 = (float)(3 / 8); contraction off, as there.
+// double: wt64_anscombe_kernel (wt_kernels_f64.h) - with alpha = 1 and g = sigma = 0 every product of that kernel is
+// exact and every term it may contract into an FMA is zero, so its value does not depend on contraction:
+// forward 2 sqrt(max(v + 3 / 8, 0)), inverse (v / 2)^2 - 3 / 8, each operation rounded once.
+// Forward: samples <= -3 / 8 and -inf give 0, NaN stays NaN, +inf stays +inf; the square root is the correctly rounded
+// one of those kernels, so the bits are also numpy's 2 * np.sqrt(x + 0.375).
+__device__ __forceinline__ float wt_anscombe_fwd(float x)
+{
+#pragma clang fp contract(off)
+    const float alpha = 1.f, c1 = (float)(3.0 * 1.0 * 1.0 / 8.0), c2 = (float)(0.0 * 0.0), c3 = (float)(1.0 * 0.0);
+    float t = alpha * x;
+    t = t + c1;
+    t = t + c2;
+    t = t - c3;
+    t = t <= 0.f ? 0.f : t;
+    return (2.f * sqrtf(t)) / alpha;
+}
+__device__ __forceinline__ float wt_anscombe_inv(float x)
+{
+#pragma clang fp contract(off)
+    const float alpha = 1.f, c1 = (float)(1.0 * 0.0), c2 = (float)(0.0 * 0.0), c3 = (float)(3.0 * 1.0 / 8.0);
+    float t = alpha * x;
+    t = t / 2.f;
+    t = t * t;
+    t = t + c1;
+    t = t - c2;
+    t = t - c3;
+    return t / alpha;
+}
+__device__ __forceinline__ double wt_anscombe_fwd(double v)
+{
+#pragma clang fp contract(off)
+    const double alpha = 1.0, g = 0.0, sigma = 0.0;
+    double dum = alpha * v + 3.0 * alpha * alpha / 8.0 + sigma * sigma - alpha * g;
+    if (dum <= 0.0) dum = 0.0;
+    return 2.0 * sqrt(dum) / alpha;
+}
+__device__ __forceinline__ double wt_anscombe_inv(double v)
+{
+#pragma clang fp contract(off)
+    const double alpha = 1.0, g = 0.0, sigma = 0.0;
+    const double h = alpha * v / 2.0;
+    return (h * h + alpha * g - sigma * sigma - 3.0 * alpha / 8.0) / alpha;
+}
+// a 16-byte group of samples, point by point
+__device__ __forceinline__ float4 wt_anscombe_fwd(float4 v) { return make_float4(wt_anscombe_fwd(v.x), wt_anscombe_fwd(v.y), wt_anscombe_fwd(v.z), wt_anscombe_fwd(v.w)); }
+__device__ __forceinline__ double2 wt_anscombe_fwd(double2 v) { return make_double2(wt_anscombe_fwd(v.x), wt_anscombe_fwd(v.y)); }
+
 // The exact np.median(np.abs(w_0)): the magnitudes' bit patterns order like the values, so a bitonic network sorts
 // them as unsigned keys (the tail of the power of two filled with all-ones keys).
 template <typename T>

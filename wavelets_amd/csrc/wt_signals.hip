@@ -115,24 +115,31 @@ extern "C" int wt_signals_upload(wt_signals *b, int first, int count, const void
     return signals_copy(b, (char *)b->in + (size_t)first * b->Np * b->itemsize, const_cast<void *>(host), (size_t)count, true);
 }
 
-extern "C" int wt_signals_decompose(wt_signals *b, int count, int level)
+static int signals_decompose(wt_signals *b, int count, int level, int flags, const char *who)
 {
-    WT_TRY(signals_check(b, 0, count, "wt_signals_decompose"));
-    if (level < 1 || level > b->max_level) WT_FAIL("wt_signals_decompose: %d scales outside [1, %d]", level, b->max_level);
+    WT_TRY(signals_check(b, 0, count, who));
+    WT_TRY(lines_flags(flags, who));
+    if (level < 1 || level > b->max_level) WT_FAIL("%s: %d scales outside [1, %d]", who, level, b->max_level);
     WtGuard guard_(b->ctx);
     wt_ctx *c = b->ctx;
     const size_t lds = 2 * (size_t)b->Np * b->itemsize;
-    if (lds > WT_SIGNALS_LDS_BYTES) WT_FAIL("wt_signals_decompose: %zu bytes of LDS per signal", lds);
+    if (lds > WT_SIGNALS_LDS_BYTES) WT_FAIL("%s: %zu bytes of LDS per signal", who, lds);
     const dim3 grid((unsigned)count), block(WT_SIGNALS_THREADS);
     ProfScope ps(c, b->itemsize == 8 ? "wt_signals_decompose_kernel<double>" : "wt_signals_decompose_kernel<float>");
     lines_by_type_family(b->itemsize, b->family, [&](auto t, auto k) {
         typedef decltype(t) T;
-        hipLaunchKernelGGL((wt_signals_decompose_kernel<T, decltype(k)::value>), grid, block, lds, c->stream, (const T *)b->in, (T *)b->planes, b->N, b->Np, level);
+        constexpr int K = decltype(k)::value;
+        if (flags & WT_LINES_ANSCOMBE)
+            hipLaunchKernelGGL((wt_signals_decompose_kernel<T, K, true>), grid, block, lds, c->stream, (const T *)b->in, (T *)b->planes, b->N, b->Np, level);
+        else
+            hipLaunchKernelGGL((wt_signals_decompose_kernel<T, K, false>), grid, block, lds, c->stream, (const T *)b->in, (T *)b->planes, b->N, b->Np, level);
     });
     WT_HIP(hipGetLastError());
     b->level = level;
     return 0;
 }
+extern "C" int wt_signals_decompose(wt_signals *b, int count, int level) { return signals_decompose(b, count, level, 0, "wt_signals_decompose"); }
+extern "C" int wt_signals_decompose_ex(wt_signals *b, int count, int level, int flags) { return signals_decompose(b, count, level, flags, "wt_signals_decompose_ex"); }
 
 extern "C" int wt_signals_abs_median(wt_signals *b, int count, void *medians)
 {
@@ -161,14 +168,15 @@ extern "C" int wt_signals_abs_median(wt_signals *b, int count, void *medians)
     return 0;
 }
 
-extern "C" int wt_signals_denoise_sum(wt_signals *b, int count, int n_den, const double *tau, const double *wgt, int soft)
+static int signals_denoise_sum(wt_signals *b, int count, int n_den, const double *tau, const double *wgt, int soft, int flags, const char *who)
 {
-    WT_TRY(signals_check(b, 0, count, "wt_signals_denoise_sum"));
-    if (b->level < 1) WT_FAIL("wt_signals_denoise_sum: no transform in the stack (wt_signals_decompose first)");
+    WT_TRY(signals_check(b, 0, count, who));
+    WT_TRY(lines_flags(flags, who));
+    if (b->level < 1) WT_FAIL("%s: no transform in the stack (wt_signals_decompose first)", who);
     const int n = b->level + 1;
-    if (n > WT_MAX_SUM_PLANES) WT_FAIL("wt_signals_denoise_sum: %d planes (at most %d)", n, WT_MAX_SUM_PLANES);
-    if (n_den < 0 || n_den > n) WT_FAIL("wt_signals_denoise_sum: n_den %d outside [0,%d]", n_den, n);
-    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("wt_signals_denoise_sum: null tau / wgt");
+    if (n > WT_MAX_SUM_PLANES) WT_FAIL("%s: %d planes (at most %d)", who, n, WT_MAX_SUM_PLANES);
+    if (n_den < 0 || n_den > n) WT_FAIL("%s: n_den %d outside [0,%d]", who, n_den, n);
+    if (n_den > 0 && (!tau || !wgt)) WT_FAIL("%s: null tau / wgt", who);
     WtGuard guard_(b->ctx);
     wt_ctx *c = b->ctx;
     const bool f64 = b->itemsize == 8;
@@ -201,9 +209,21 @@ extern "C" int wt_signals_denoise_sum(wt_signals *b, int count, int n_den, const
     a.soft = soft;
     const unsigned grid = (unsigned)std::min<int64_t>((a.groups + WT_SIGNALS_THREADS - 1) / WT_SIGNALS_THREADS, (int64_t)c->num_cus * 32);
     ProfScope ps(c, f64 ? "wt_signals_denoise_sum_kernel<double>" : "wt_signals_denoise_sum_kernel<float>");
-    lines_by_type(b->itemsize, [&](auto t) { hipLaunchKernelGGL(wt_signals_denoise_sum_kernel<decltype(t)>, dim3(grid), dim3(WT_SIGNALS_THREADS), 0, c->stream, a); });
+    lines_by_type(b->itemsize, [&](auto t) {
+        typedef decltype(t) T;
+        if (flags & WT_LINES_ANSCOMBE) hipLaunchKernelGGL((wt_signals_denoise_sum_kernel<T, true>), dim3(grid), dim3(WT_SIGNALS_THREADS), 0, c->stream, a);
+        else hipLaunchKernelGGL((wt_signals_denoise_sum_kernel<T, false>), dim3(grid), dim3(WT_SIGNALS_THREADS), 0, c->stream, a);
+    });
     WT_HIP(hipGetLastError());
     return 0;
+}
+extern "C" int wt_signals_denoise_sum(wt_signals *b, int count, int n_den, const double *tau, const double *wgt, int soft)
+{
+    return signals_denoise_sum(b, count, n_den, tau, wgt, soft, 0, "wt_signals_denoise_sum");
+}
+extern "C" int wt_signals_denoise_sum_ex(wt_signals *b, int count, int n_den, const double *tau, const double *wgt, int soft, int flags)
+{
+    return signals_denoise_sum(b, count, n_den, tau, wgt, soft, flags, "wt_signals_denoise_sum_ex");
 }
 
 // a device block and its page-locked twin of `bytes` bytes, allocated on first use

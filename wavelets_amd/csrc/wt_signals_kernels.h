@@ -12,7 +12,9 @@
 // HBM traffic: the signal once, level + 1 planes once: sizeof(T) * (level + 2) bytes per sample.
 // LDS: at every dilation lane l of a wave reads element x0 + l + const of the source buffer (away from the borders)
 // and writes element x0 + l of the other one - consecutive lanes, consecutive addresses, no bank conflicts.
-template <typename T, int K>
+// ANS: every sample goes through wt_anscombe_fwd (wt_signal_common.h) on its way into LDS - the transform of
+// generalized_anscombe(signal) (watroo/utils.py:93-95) at the traffic of the plain one; the input in HBM stays as it is.
+template <typename T, int K, bool ANS>
 __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_decompose_kernel(const T *in, T *planes, int N, int Np, int level)
 {
     typedef typename WtVec<T>::V V;
@@ -24,8 +26,10 @@ __global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_decompose_kerne
     const int64_t sig = blockIdx.x;
     const T *src = in + sig * Np;
     T *out = planes + sig * (int64_t)(level + 1) * Np;
-    for (int i = threadIdx.x * PX; i < Np; i += WT_SIGNALS_THREADS * PX)
-        *reinterpret_cast<V *>(a + i) = *reinterpret_cast<const V *>(src + i);
+    for (int i = threadIdx.x * PX; i < Np; i += WT_SIGNALS_THREADS * PX) {
+        if constexpr (ANS) *reinterpret_cast<V *>(a + i) = wt_anscombe_fwd(*reinterpret_cast<const V *>(src + i));
+        else *reinterpret_cast<V *>(a + i) = *reinterpret_cast<const V *>(src + i);
+    }
     __syncthreads();
     for (int s = 0; s < level; ++s) {
         const int d = 1 << s;
@@ -97,58 +101,60 @@ struct WtSignalsSumArgs {
     int64_t groups;         // all signals' groups
     int g, Np, n, n_den, soft;
 };
-template <typename T>
-__global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_denoise_sum_kernel(WtSignalsSumArgs a);
-
-template <>
-__global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_denoise_sum_kernel<float>(WtSignalsSumArgs a)
-{
-#pragma clang fp contract(off)
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.groups; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t f = i / a.g;
-        const int r = (int)(i - f * a.g);
-        const double *ft = a.tab + f * 2 * a.n_den;
-        const float *p = reinterpret_cast<const float *>(a.planes) + f * (int64_t)a.n * a.Np + 4 * r;
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int k = 0; k < a.n; ++k) {
-            const float4 v = *reinterpret_cast<const float4 *>(p + (int64_t)k * a.Np);
-            float c[4] = {v.x, v.y, v.z, v.w};
-            if (k < a.n_den) {
-                const double t = ft[k], wgt = ft[a.n_den + k];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) c[j] = wt_signal_point(c[j], t, 0.0, wgt, a.soft);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = k == 0 ? c[j] : acc[j] + c[j];
-        }
-        reinterpret_cast<float4 *>(a.dst)[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    }
-}
-
+// ANS: every sum goes through wt_anscombe_inv (wt_signal_common.h) before its one store - the inverse of
+// watroo/utils.py:99-100 on np.sum(planes, axis=0), no pass of its own over the sum.
 // double: tab[signal * 3 * n_den + k] = tau, [+ n_den + k] = the host's 1 / tau, [+ 2 * n_den + k] = the weight.
 // The expressions of the double wt_signal_point, written out for the two samples of a group under ONE test of tau:
 // through two calls of the point the compiler emits two tests and another register allocation - the same values,
-// another instruction stream - so this one kernel keeps its text ("One core for the two 1-D engines").
-template <>
-__global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_denoise_sum_kernel<double>(WtSignalsSumArgs a)
+// another instruction stream - so this one branch keeps its text ("One core for the two 1-D engines").
+template <typename T, bool ANS>
+__global__ __launch_bounds__(WT_SIGNALS_THREADS) void wt_signals_denoise_sum_kernel(WtSignalsSumArgs a)
 {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.groups; i += (int64_t)gridDim.x * 256) {
-        const int64_t f = i / a.g;
-        const int r = (int)(i - f * a.g);
-        const double *ft = a.tab + f * 3 * a.n_den;
-        const double *p = reinterpret_cast<const double *>(a.planes) + f * (int64_t)a.n * a.Np + 2 * r;
-        double2 acc = make_double2(0.0, 0.0);
-        for (int k = 0; k < a.n; ++k) {
-            double2 v = *reinterpret_cast<const double2 *>(p + (int64_t)k * a.Np);
-            if (k < a.n_den) {
-                const double tau = ft[k], inv_tau = ft[a.n_den + k], wgt = ft[2 * a.n_den + k];
-                double2 sg = make_double2(1.0, 1.0);
-                if (tau > 0.0) sg = make_double2(wt_sig64_inv(v.x, tau, inv_tau, a.soft), wt_sig64_inv(v.y, tau, inv_tau, a.soft));
-                v = make_double2(v.x * (wgt * sg.x), v.y * (wgt * sg.y));
+    if constexpr (sizeof(T) == 4) {
+#pragma clang fp contract(off)
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.groups; i += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t f = i / a.g;
+            const int r = (int)(i - f * a.g);
+            const double *ft = a.tab + f * 2 * a.n_den;
+            const float *p = reinterpret_cast<const float *>(a.planes) + f * (int64_t)a.n * a.Np + 4 * r;
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int k = 0; k < a.n; ++k) {
+                const float4 v = *reinterpret_cast<const float4 *>(p + (int64_t)k * a.Np);
+                float c[4] = {v.x, v.y, v.z, v.w};
+                if (k < a.n_den) {
+                    const double t = ft[k], wgt = ft[a.n_den + k];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) c[j] = wt_signal_point(c[j], t, 0.0, wgt, a.soft);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] = k == 0 ? c[j] : acc[j] + c[j];
             }
-            acc = k == 0 ? v : make_double2(acc.x + v.x, acc.y + v.y);
+            if constexpr (ANS) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] = wt_anscombe_inv(acc[j]);
+            }
+            reinterpret_cast<float4 *>(a.dst)[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
         }
-        reinterpret_cast<double2 *>(a.dst)[i] = acc;
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.groups; i += (int64_t)gridDim.x * 256) {
+            const int64_t f = i / a.g;
+            const int r = (int)(i - f * a.g);
+            const double *ft = a.tab + f * 3 * a.n_den;
+            const double *p = reinterpret_cast<const double *>(a.planes) + f * (int64_t)a.n * a.Np + 2 * r;
+            double2 acc = make_double2(0.0, 0.0);
+            for (int k = 0; k < a.n; ++k) {
+                double2 v = *reinterpret_cast<const double2 *>(p + (int64_t)k * a.Np);
+                if (k < a.n_den) {
+                    const double tau = ft[k], inv_tau = ft[a.n_den + k], wgt = ft[2 * a.n_den + k];
+                    double2 sg = make_double2(1.0, 1.0);
+                    if (tau > 0.0) sg = make_double2(wt_sig64_inv(v.x, tau, inv_tau, a.soft), wt_sig64_inv(v.y, tau, inv_tau, a.soft));
+                    v = make_double2(v.x * (wgt * sg.x), v.y * (wgt * sg.y));
+                }
+                acc = k == 0 ? v : make_double2(acc.x + v.x, acc.y + v.y);
+            }
+            if constexpr (ANS) acc = make_double2(wt_anscombe_inv(acc.x), wt_anscombe_inv(acc.y));
+            reinterpret_cast<double2 *>(a.dst)[i] = acc;
+        }
     }
 }
 

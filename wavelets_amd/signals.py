@@ -166,10 +166,14 @@ def transform_signals(signals, level, scaling_function=B3spline, out=None):
     return res
 
 
-def denoise_signals(signals, weights, scaling_function=B3spline, noise=None, soft_threshold=True, out=None):
+def denoise_signals(signals, weights, scaling_function=B3spline, noise=None, soft_threshold=True, out=None, anscombe=False):
     """(M, N): utils.denoise of every signal (ref utils.py:83-102 on a 1-D array), float32 or float64 as
     transform_signals.  `noise`: None (each signal's own MAD estimate, ref wavelets.py:126-132), one scalar, or a list
-    of one entry per signal, each None or a scalar; signals with a scalar skip the median."""
+    of one entry per signal, each None or a scalar; signals with a scalar skip the median.
+    `anscombe`: denoise(signal, ..., anscombe=True) of every signal, bit for bit - photon counts (ref utils.py:93-94,
+    99-100).  The forward transform is applied as the transform kernel loads a signal and the inverse on the sum before
+    its one store: the same launches and the same device traffic as without it.  Noise levels, given or estimated, refer
+    to the transformed data (ref utils.py:95-97)."""
     sig = _as_signals(signals)
     M, N = len(sig), len(sig[0])
     nl = _noise_list(noise, M)
@@ -178,23 +182,25 @@ def denoise_signals(signals, weights, scaling_function=B3spline, noise=None, sof
     fam = _signals_family(sig, level, scaling_function, nl)
     if fam is None or level + 1 > _lib.MAX_SUM_PLANES:
         out = _target(out, (M, N), _loop_dtype(sig))
-        return _hand_over(np.stack([denoise(s, weights, scaling_function, n_i, soft_threshold=soft_threshold)
+        more = {"anscombe": True} if anscombe else {}          # (without it: the call as it always was)
+        return _hand_over(np.stack([denoise(s, weights, scaling_function, n_i, soft_threshold=soft_threshold, **more)
                                     for s, n_i in zip(sig, nl)]), out)
     res = _target(out, (M, N), sig.dtype)
     sigma_e, entries, need_noise = _thresholds(weights, scaling_function)
     res, ctx = _result(res, (M, N), sig.dtype)
     chunks = _chunks(M, N, level, sig.dtype.itemsize)
+    ans = {"anscombe": True} if anscombe else {}               # (without it: the calls as they always were)
     sb = _lib.acquire_signals(ctx, max(nf for _, nf in chunks), N, fam, level, sig.dtype)
     try:
         for f0, nf in chunks:
             noises = nl[f0:f0 + nf]
             sb.upload(sig[f0:f0 + nf])
-            sb.decompose(nf, level)
+            sb.decompose(nf, level, **ans)
             if need_noise and any(n is None for n in noises):
                 med = sb.abs_median(nf)                                       # ref wavelets.py:131-132 (lazy)
                 noises = [_noise_from_median(m, sigma_e) if n is None else n for n, m in zip(noises, med)]
             taus = [_tau_row(entries, n, sigma_e, soft_threshold) for n in noises]
-            sb.denoise_sum(nf, taus, [[w for _, _, w in entries]] * nf, soft_threshold)
+            sb.denoise_sum(nf, taus, [[w for _, _, w in entries]] * nf, soft_threshold, **ans)
             sb.download_sum(nf, out=res[f0:f0 + nf])
     finally:
         _lib.release_signals(sb)
