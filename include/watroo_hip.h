@@ -961,6 +961,48 @@ int wt_along_download_planes(wt_along *along, void *host, int64_t pitch, int64_t
 /* the sum of wt_along_denoise -> host rows as wt_along_upload (utils.py:98) */
 int wt_along_download_sum(wt_along *along, void *host, int64_t pitch);
 
+/* ---- arrays that stay on the device (wavelets_amd/resident.py, wt_resident.hip) ----------------------------------
+ * Frames that already lie in device memory - the output of a model, of a calibration kernel, of a previous call - go
+ * into a batch and come out of it without crossing PCIe.  Additive entries: wt_abi_version() stays 8. */
+#define WT_COPY_HOST_TO_DEVICE 1
+#define WT_COPY_DEVICE_TO_HOST 2
+#define WT_COPY_DEVICE_TO_DEVICE 3
+/* how `stream` of the load / store entries is read: nothing to order (the array is ready), the legacy default stream,
+ * the per-thread default stream, or `stream` is a hipStream_t */
+#define WT_STREAM_NONE 0
+#define WT_STREAM_LEGACY 1
+#define WT_STREAM_PER_THREAD 2
+#define WT_STREAM_HANDLE 3
+/* a plain block of `bytes` bytes of device memory on the context's GPU (0 bytes: *ptr = NULL).  Replaces the page-locked
+ * host block of wt_host_alloc as the home of a result: the block behind a resident.DeviceArray */
+int wt_device_alloc(wt_ctx *ctx, size_t bytes, void **ptr);
+/* ... and back (NULL: nothing).  Replaces wt_host_free; waits for the device, so nothing queued still uses the block */
+int wt_device_free(wt_ctx *ctx, void *ptr);
+/* `bytes` contiguous bytes dst <- src, kind WT_COPY_*; complete when it returns.  Replaces the host side of wt_upload /
+ * wt_download for a block that belongs to no plan (DeviceArray.from_numpy, DeviceArray.numpy) */
+int wt_device_copy(wt_ctx *ctx, void *dst, const void *src, size_t bytes, int kind);
+/* frames [f0, f0+nf) of a plane <- the (nf, H, W) DEVICE array at `dev` of element type `dtype` (WT_UINT8 or
+ * WT_FLOAT32), stride_bytes[3] = bytes from frame to frame, row to row, element to element (positive multiples of the
+ * element size; any pitch, any inner stride), each element converted as wt_upload_int converts it.  Replaces
+ * wt_batch_upload for frames that are on the device already: one kernel, one read and one write per element, the
+ * plane's padding columns untouched.  With a stream_kind other than WT_STREAM_NONE the context's stream first waits
+ * for what that stream holds; no host synchronisation either way */
+int wt_batch_load_device(wt_batch *batch, int plane, int f0, int nf, const void *dev, int dtype,
+                         const int64_t stride_bytes[3], void *stream, int stream_kind);
+/* frames [f0, f0+nf) of a plane -> the (nf, H, W) float DEVICE array at `dev`, strides as above.  Replaces
+ * wt_batch_download for a result that stays on the device.  With a stream_kind other than WT_STREAM_NONE that stream
+ * then waits for the copy; no host synchronisation either way */
+int wt_batch_store_device(wt_batch *batch, int plane, int f0, int nf, void *dev, const int64_t stride_bytes[3],
+                          void *stream, int stream_kind);
+/* wt_batch_load_device for the float64 batch: `dtype` WT_UINT8, WT_INT16, WT_UINT16, WT_INT32, WT_FLOAT32 or
+ * WT_FLOAT64, widened as wt_batch64_upload_elems widens (the reference's recast to float64).  Replaces
+ * wt_batch64_upload and wt_batch64_upload_elems, the device staging block of the latter included */
+int wt_batch64_load_device(wt_batch64 *batch, int plane, int f0, int nf, const void *dev, int dtype,
+                           const int64_t stride_bytes[3], void *stream, int stream_kind);
+/* wt_batch_store_device for the float64 batch: a (nf, H, W) double DEVICE array.  Replaces wt_batch64_download */
+int wt_batch64_store_device(wt_batch64 *batch, int plane, int f0, int nf, void *dev, const int64_t stride_bytes[3],
+                            void *stream, int stream_kind);
+
 #ifdef __cplusplus
 }
 #endif

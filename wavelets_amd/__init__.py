@@ -16,5 +16,7 @@ from .signals import transform_signals, denoise_signals, signals_eligible  # noq
 from .along import transform_along, denoise_along, along_eligible  # noqa: F401  (the 1-D transform along any axis of an array: a tile of neighbouring signals per workgroup)
 from .wow_signals import wow_signals, wow_along, wow_signals_eligible  # noqa: F401  (wow of stacks of 1-D signals and along an axis: the per-scale loop of a signal in one launch)
 from .rng import normal_frames  # noqa: F401  (seeded standard-normal frames, filled on the GPU)
+from . import resident  # noqa: F401  (transform_stack / denoise_stack from a device array to a device array: no PCIe crossing)
+from .resident import DeviceArray  # noqa: F401
 
 __version__ = '0.1.0'

@@ -321,6 +321,14 @@ SIGNATURES = {
                                        _c.c_int]),
     "wt_along_download_planes": (_c.c_int, [_vp, _vp, _i64, _i64]),
     "wt_along_download_sum": (_c.c_int, [_vp, _vp, _i64]),
+    # arrays that stay on the device (wt_resident)
+    "wt_device_alloc": (_c.c_int, [_vp, _c.c_size_t, _c.POINTER(_vp)]),
+    "wt_device_free": (_c.c_int, [_vp, _vp]),
+    "wt_device_copy": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _c.c_int]),
+    "wt_batch_load_device": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_int, _c.POINTER(_i64), _vp, _c.c_int]),
+    "wt_batch_store_device": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _vp, _c.POINTER(_i64), _vp, _c.c_int]),
+    "wt_batch64_load_device": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_int, _c.POINTER(_i64), _vp, _c.c_int]),
+    "wt_batch64_store_device": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _vp, _c.POINTER(_i64), _vp, _c.c_int]),
 }
 
 _lib = None
@@ -1080,6 +1088,58 @@ def batch_fft_ok(H, W):
     ok = _c.c_int(0)
     check(load().wt_batch_fft_ok(int(H), int(W), _c.byref(ok)))
     return bool(ok.value)
+
+
+STREAM_NONE, STREAM_LEGACY, STREAM_PER_THREAD, STREAM_HANDLE = 0, 1, 2, 3     # WT_STREAM_*
+COPY_HOST_TO_DEVICE, COPY_DEVICE_TO_HOST, COPY_DEVICE_TO_DEVICE = 1, 2, 3      # WT_COPY_*
+
+
+def stream_arg(stream):
+    """(handle, WT_STREAM_* kind) of a stream in the convention of __cuda_array_interface__: None - nothing to order;
+    1 - the legacy default stream; 2 - the per-thread default stream; any other positive int - a hipStream_t; 0 - the
+    null hipStream_t, which is the legacy default stream (what torch.cuda.current_stream().cuda_stream is on torch's
+    default stream).  A bool or a negative value: ValueError (host logic)."""
+    if stream is None:
+        return None, STREAM_NONE
+    if isinstance(stream, bool) or not isinstance(stream, (int, np.integer)) or int(stream) < 0:
+        raise ValueError(f"stream: None, 1 (legacy default), 2 (per-thread default) or a stream handle expected (got {stream!r})")
+    stream = int(stream)
+    if stream in (0, STREAM_LEGACY, STREAM_PER_THREAD):
+        return None, stream or STREAM_LEGACY
+    return _vp(stream), STREAM_HANDLE
+
+
+def device_alloc(ctx, nbytes):
+    """address of a block of `nbytes` bytes of device memory on the context's GPU (0 for an empty block)"""
+    p = _vp()
+    check(load().wt_device_alloc(ctx._h, int(nbytes), _c.byref(p)))
+    return p.value or 0
+
+
+def device_free(ctx, ptr):
+    check(load().wt_device_free(ctx._h, _vp(ptr)))
+
+
+def device_copy(ctx, dst, src, nbytes, kind):
+    """`nbytes` contiguous bytes dst <- src (addresses), kind COPY_*; complete on return"""
+    check(load().wt_device_copy(ctx._h, _vp(dst), _vp(src), int(nbytes), int(kind)))
+
+
+def batch_load_device(bp, plane, nf, ptr, dtype, strides, f0=0, stream=None):
+    """frames f0 .. f0+nf-1 of a plane of the BatchPlan / BatchPlan64 `bp` <- the (nf, H, W) DEVICE array at `ptr` of
+    element type `dtype`, `strides` its three strides in bytes: upload's device-to-device form, widening included.
+    `stream` (stream_arg's convention): the context's stream first waits for that stream; no host synchronisation.
+    (Functions, not methods: the two classes keep the methods they have.)"""
+    code = _ELEM_CODES[np.dtype(dtype).str[1:]]
+    handle, kind = stream_arg(stream)
+    bp._call("load_device", plane, f0, nf, _vp(ptr), code, (_i64 * 3)(*strides), handle, kind)
+
+
+def batch_store_device(bp, plane, nf, ptr, strides, f0=0, stream=None):
+    """frames f0 .. f0+nf-1 of a plane of `bp` -> the (nf, H, W) DEVICE array at `ptr` of the batch's element type:
+    download's device-to-device form.  `stream`: that stream then waits for the copy; no host synchronisation."""
+    handle, kind = stream_arg(stream)
+    bp._call("store_device", plane, f0, nf, _vp(ptr), (_i64 * 3)(*strides), handle, kind)
 
 
 class _BatchBase:

@@ -387,6 +387,45 @@ def _target(f64, out, shape):
     return _f64_target(out, shape) if f64 else (_f32_target(out, shape), None)
 
 
+class _HostSource:
+    """The frames of a stack that lies in host memory, as the chunk loops take them (_transform_chunks,
+    _denoise_chunks): `shape`, and load(bp, f0, nf) - frames f0 .. f0+nf-1 into the input plane of the batch `bp`
+    (integer / big-endian frames of a float64 batch: widened on the device).  resident.py has the device form."""
+
+    def __init__(self, fr):
+        self.fr = fr
+        self.shape = fr.shape
+
+    def load(self, bp, f0, nf):
+        bp.upload(PLANE_INPUT, self.fr[f0:f0 + nf])
+
+
+class _HostSink:
+    """The result array in host memory, as the chunk loops fill it: store(bp, plane, f0, nf, index, last) - frames
+    0 .. nf-1 of a plane of `bp` into res[f0:f0+nf] or, with `index`, res[f0:f0+nf, index] (straight into the caller's
+    cube); `last`: the final store of the call (nothing to do here: a download is complete when it returns)."""
+
+    def __init__(self, res):
+        self.res = res
+
+    def store(self, bp, plane, f0, nf, index=None, last=False):
+        bp.download(plane, nf, out=self.res[f0:f0 + nf] if index is None else self.res[f0:f0 + nf, index])
+
+
+def _transform_chunks(bp, src, chunks, level, bilateral, bilateral_scaling, sink):
+    """transform_stack's device part on a BatchPlan or BatchPlan64: every chunk of frames from `src` through the
+    transform, planes 0 .. level into `sink`.  `bilateral`: the batched bilateral transform's parameter, else None."""
+    for f0, nf in chunks:
+        src.load(bp, f0, nf)
+        if bilateral is not None:                              # ref:433-442
+            sb = _sigma_bilateral_list(bilateral, level)
+            bp.decompose_bilateral(nf, PLANE_INPUT, level, sb, bilateral_scaling)
+        else:
+            bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
+        for s in range(level + 1):
+            sink.store(bp, s, f0, nf, s, last=f0 + nf == src.shape[0] and s == level)
+
+
 def transform_stack(frames, level, scaling_function=B3spline, out=None, bilateral=None, bilateral_scaling=False):
     """(N, level+1, H, W) float32 (float64 for the stacks the reference computes in float64): the standard
     transform of every frame (AtrousTransform(scaling_function, bilateral, bilateral_scaling)(frame, level).data,
@@ -401,15 +440,7 @@ def transform_stack(frames, level, scaling_function=B3spline, out=None, bilatera
     res, fill = _target(f64, out, (N, level + 1, H, W))
     chunks = _plan_chunks(N, H, W, level, f64)
     with _batch(f64, max(nf for _, nf in chunks), H, W, _family_of(scaling_function(2)), level) as bp:
-        for f0, nf in chunks:
-            bp.upload(PLANE_INPUT, fr[f0:f0 + nf])               # (integer / big-endian frames: widened on the device)
-            if bil:                                                # ref:433-442
-                sb = _sigma_bilateral_list(bilateral, level)
-                bp.decompose_bilateral(nf, PLANE_INPUT, level, sb, bilateral_scaling)
-            else:
-                bp.decompose(nf, PLANE_INPUT, level, FLAG_FUSED)
-            for s in range(level + 1):
-                bp.download(s, nf, out=res[f0:f0 + nf, s])         # straight into the caller's cube
+        _transform_chunks(bp, _HostSource(fr), chunks, level, bilateral if bil else None, bilateral_scaling, _HostSink(res))
     return _hand_over(res, fill)
 
 
@@ -433,19 +464,20 @@ def denoise_stack(frames, weights, scaling_function=B3spline, noise=None, soft_t
     maps = int(noise_map_eligible(fr, nl))                 # (the noise plane: one more plane per frame)
     chunks = _plan_chunks(N, H, W, level, f64, maps)
     with _batch(f64, max(nf for _, nf in chunks), H, W, _family_of(scaling_function(2)), level) as bp:
-        _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe, bilateral if bil else None,
-                        res)
+        _denoise_chunks(bp, _HostSource(fr), chunks, nl, weights, scaling_function, soft_threshold, anscombe,
+                        bilateral if bil else None, _HostSink(res))
     return _hand_over(res, fill)
 
 
-def _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshold, anscombe, bilateral, out):
-    """denoise_stack's device part on a BatchPlan (float32) or a BatchPlan64 (float64): every chunk of frames
-    through the per-frame sequence of utils.denoise (wavelets._decompose_denoise_sum), results into `out`.
+def _denoise_chunks(bp, src, chunks, nl, weights, scaling_function, soft_threshold, anscombe, bilateral, sink):
+    """denoise_stack's device part on a BatchPlan (float32) or a BatchPlan64 (float64): every chunk of frames from
+    `src` (_HostSource, or resident.py's device form) through the per-frame sequence of utils.denoise
+    (wavelets._decompose_denoise_sum), results into `sink`.
     `bilateral`: the batched bilateral transform's parameter (bilateral_eligible / bilateral64_eligible), else None.
     Frames whose noise is a per-pixel map (ref wavelets.py:133-141) get the map thresholds (_map_tau_row) and their map
     in the batch's noise plane (_upload_noise_maps); no MAD estimate is taken for them."""
     bil = bilateral is not None
-    shape = fr.shape[1:]
+    shape = src.shape[1:]
     shared = _shared_map(nl, shape)
     level = len(weights)
     sf = scaling_function(2)
@@ -458,7 +490,7 @@ def _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshol
     entries, k, covered = _interleave_split(sched, level, sigma, wgts)
     for f0, nf in chunks:
         noises = list(nl[f0:f0 + nf])
-        bp.upload(PLANE_INPUT, fr[f0:f0 + nf])
+        src.load(bp, f0, nf)
         if anscombe:
             bp.anscombe(nf, PLANE_INPUT, PLANE_INPUT)                        # ref:93-94
         whole = k == 0 or k == len(sched)
@@ -498,7 +530,7 @@ def _denoise_chunks(bp, fr, chunks, nl, weights, scaling_function, soft_threshol
                 cur = nxt
         if anscombe:
             bp.anscombe(nf, PLANE_OUT, PLANE_OUT, inverse=True)              # ref:99-100
-        bp.download(PLANE_OUT, nf, out=out[f0:f0 + nf])
+        sink.store(bp, PLANE_OUT, f0, nf, last=f0 + nf == src.shape[0])
 
 
 def _shared_map(nl, shape):

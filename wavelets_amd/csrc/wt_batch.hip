@@ -513,6 +513,8 @@ extern "C" int wt_batch_info(wt_batch *b, int64_t *info)
     return batch_info(b, info, "wt_batch_info");
 }
 
+wt_ctx *wt_batch_ctx(wt_batch *b) { return b->ctx; }
+
 extern "C" int wt_batch_plane_ptr(wt_batch *b, int plane, void **ptr, int64_t *frame_stride)
 {
     return batch_plane_ptr(b, plane, ptr, frame_stride, "wt_batch_plane_ptr");

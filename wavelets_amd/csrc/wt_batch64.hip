@@ -559,6 +559,8 @@ extern "C" int wt_batch64_info(wt_batch64 *b, int64_t *info)
     return batch_info(b, info, "wt_batch64_info");
 }
 
+wt_ctx *wt_batch64_ctx(wt_batch64 *b) { return b->ctx; }
+
 extern "C" int wt_batch64_plane_ptr(wt_batch64 *b, int plane, void **ptr, int64_t *frame_stride)
 {
     return batch_plane_ptr(b, plane, ptr, frame_stride, "wt_batch64_plane_ptr");

@@ -102,6 +102,11 @@ void destroy_events(std::vector<hipEvent_t> &ev);
 bool try_pin(const void *host, size_t bytes);
 int halo_exchange_on(wt_plan *p, int plane, int64_t rows, hipStream_t st, const char *prof_name = "rccl_halo_exchange");
 
+// ------------------------------------------------------------------ batches (wt_batch.hip, wt_batch64.hip)
+// the context of a batch, for a unit that reaches the batch through the C ABI alone (wt_resident.hip)
+wt_ctx *wt_batch_ctx(wt_batch *b);
+wt_ctx *wt_batch64_ctx(wt_batch64 *b);
+
 // ------------------------------------------------------------------ per-scale launches (wt_transform.hip)
 int check_scale(const wt_plan *p, int s, const char *who);
 static inline StencilCtx stencil_ctx(const wt_plan *p, hipStream_t st = nullptr)
