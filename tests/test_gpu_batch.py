@@ -266,3 +266,76 @@ def test_upload_download_round_trip_of_both_batches(name):
                 assert np.array_equal(bp.download(L.PLANE_INPUT, 3), typed.astype(np.float64))
     finally:
         bp.close()
+
+
+@pytest.mark.parametrize("engine", ["f32", "f64"])
+def test_threshold_sums_and_wow_update_of_a_batch_are_the_per_frame_calls(engine):
+    """Every instantiation of the shared kernel bodies of the two engines (wt_batch.hip, wt_batch64.hip) against the
+    per-frame Plan / Plan64 calls, bit for bit, on 3 frames of 6 x 10: the threshold sum without a noise plane, with
+    one (a map on frame 1 only) and with per-frame weights (enhance_sum), n_den 2 of count 3 with one tau of 0, soft and
+    hard, write_back on and off; wow_update with and without a gamma plane, with and without the noise plane."""
+    from wavelets_amd import _lib as L
+    f64 = engine == "f64"
+    real = np.float64 if f64 else np.float32
+    ctx = L.default_context()
+    n, H, Wd, S = 3, 6, 10, L.PLANE_SCRATCH
+    rng = np.random.default_rng(5)
+    planes = (rng.standard_normal((3, n, H, Wd)) * 2).astype(real)          # [plane][frame]
+    noise = np.ones((n, H, Wd), real)
+    noise[1] = rng.uniform(0.5, 2.0, (H, Wd)).astype(real)
+    gamma0 = rng.uniform(0.0, 1.0, (n, H, Wd)).astype(real)
+    has_map = [False, True, False]
+    taus = [[1.5, 0.0], [0.0, 0.7], [0.9, 1.1]]
+    wgts = [[0.8, 1.25], [1.0, 0.3], [2.0, 0.6]]                            # enhance_sum: per frame; denoise_sum: wgts[0]
+    wtau, wfac = [1.2, 0.0, 0.6], [0.5, 1.5, 0.25]
+
+    bp = (L.BatchPlan64 if f64 else L.BatchPlan)(ctx, n, H, Wd, L.B3SPLINE, 2)
+    pl = L.Plan64(ctx, H, Wd, (1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16), 2) if f64 else L.Plan(ctx, H, Wd, L.B3SPLINE, 2)
+
+    def load_batch():
+        for k in range(3):
+            bp.upload(k, planes[k])
+        bp.upload(S(5), noise)
+        bp.upload(S(4), gamma0)
+
+    def load_frame(f):
+        for k in range(3):
+            pl.upload(k, planes[k][f])
+        pl.upload(S(5), noise[f])
+        pl.upload(S(4), gamma0[f])
+
+    def same(got, exp, what):
+        assert np.array_equal(np.asarray(got), np.asarray(exp), equal_nan=True), what
+
+    try:
+        for soft in (True, False):
+            for write_back in (True, False):
+                for kind in ("plain", "map", "enhance"):
+                    load_batch()
+                    if kind == "enhance":
+                        bp.enhance_sum(n, 3, taus, wgts, soft=soft, write_back=write_back)
+                    else:
+                        bp.denoise_sum(n, 3, taus, wgts[0], soft=soft, write_back=write_back,
+                                       noise_plane=S(5) if kind == "map" else L.PLANE_NONE, has_map=has_map)
+                    got = [np.array(bp.download(p, n)) for p in (L.PLANE_OUT, 0, 1, 2)]
+                    for f in range(n):
+                        load_frame(f)
+                        pl.denoise_sum(3, taus[f], wgts[f] if kind == "enhance" else wgts[0], soft,
+                                       noise_plane=S(5) if kind == "map" and has_map[f] else L.PLANE_NONE,
+                                       write_back=write_back, dst=L.PLANE_OUT)
+                        for g, p in zip(got, (L.PLANE_OUT, 0, 1, 2)):
+                            same(g[f], pl.download(p), (engine, kind, soft, write_back, f, p))
+            for gamma in (S(4), L.PLANE_NONE):
+                for with_noise in (False, True):
+                    load_batch()
+                    bp.wow_update(n, 2, wtau, soft, wfac, gamma_plane=gamma, noise_plane=S(5) if with_noise else L.PLANE_NONE)
+                    got = [np.array(bp.download(p, n)) for p in (2, S(4))]
+                    for f in range(n):
+                        load_frame(f)
+                        pl.wow_update(2, L.PLANE_NONE, wtau[f], soft, S(5) if with_noise and has_map[f] else L.PLANE_NONE,
+                                      wfac[f], gamma)
+                        for g, p in zip(got, (2, S(4))):
+                            same(g[f], pl.download(p), (engine, "wow", soft, gamma, with_noise, f, p))
+    finally:
+        bp.close()
+        pl.close()

@@ -10,7 +10,14 @@ the core was factored out answered them:
 
 As a test the module replays the list and requires the recorded class and message for every call; a call missing from
 the table, or one the library accepts, fails.  Several calls hold two errors at once (a bad level AND a bad source
-plane, no frames AND no noise plane): they pin the ORDER of the checks, which differs between the engines in places."""
+plane, no frames AND no noise plane): they pin the ORDER of the checks, which differs between the engines in places.
+
+The Richardson-Lucy entry points (wt_batch_rl.h) need a batch with a PSF before their later checks can speak, and the
+float64 batch owns richardson_lucy's planes only from its first set_psf on.  So a method may carry a label after "@":
+"@ok" marks a call the library must ACCEPT (a set_psf, a plane_ptr: an allocation and a copy, no launch) and whose
+acceptance is recorded like a refusal; any other label ("@psf") only tells apart the same call before and after it.
+These entries were recorded on the commit before the Richardson-Lucy half was folded into one header; the older
+entries of the table came out of that recording unchanged."""
 import ctypes as _c
 import json
 import os
@@ -147,7 +154,60 @@ def calls(engine):
     for first, count, dst in ((0, 0, OUT), (0, 33, OUT), (0, 17, OUT), (-1, 2, OUT), (1, 3, OUT), (ML + 1, 1, OUT), (0, 2, 1),
                               (0, 3, 0), (1, 2, 2)):
         add("plane_sum", N, first, count, dst)
+    # ---- richardson_lucy: the calls run in this order on ONE batch, which has no PSF up to the first "set_psf@ok"
+    K9, BAD = R(*([1.0] * 9)), S(2)
+    if f64:
+        for nf in (0, N + 1):                           # (float32: in the active-frame list above)
+            add("filter2d", nf, IN, OUT, 0, 0, 0, 0)
+            add("binary", nf, 0, IN, OUT, S(3))
+            add("mrs_update", nf, 0, S(16), T4, 1, 0, 1.0)
+        # the planes of richardson_lucy are no planes of a float64 batch that has no PSF yet
+        add("binary", N, 0, S(6), S(7), S(8))
+        add("mrs_update", N, 0, S(16), T4, 1, 0, 1.0)
+    add("filter2d", 0, IN, IN, 2, 9, 9, 7)              # (every error at once: the order)
+    for slot in (0, 1, -1, 2):
+        add("filter2d", N, IN, OUT, slot, 0, 0, 0)
+    add("filter2d", N, IN, IN, 0, 9, 9, 7)              # (slot not set AND the rest)
+    for slot in (-1, 2):
+        add("set_psf", slot, K9, 3, 3)
+        add("set_psf", slot, NUL, 3, 3)                 # (two errors: the order)
+        add("set_psf", slot, K9, 1, 513)
+    add("set_psf", 0, NUL, 3, 3)
+    for kh, kw in ((1, 513), (65, 64), (0, 3), (3, 0)) + (((8, 512),) if f64 else ()):   # (8 x 512: the LDS tile, as doubles)
+        add("set_psf", 0, K9, kh, kw)
+    add("set_psf@ok", 0, K9, 3, 3)
+    if f64:
+        for p in (S(6), S(10), S(16), S(17)):
+            add("plane_ptr@ok", p, PTR, I64)
+        for p in (S(2), S(11), S(15), S(18), ML + 1):
+            add("plane_ptr@psf", p, PTR, I64)
+    add("filter2d@psf", N, IN, OUT, 1, 0, 0, 0)         # (the other slot is still not set)
+    for ay, ax in ((3, 0), (0, 3), (-1, 0), (0, -1)):
+        add("filter2d@psf", N, IN, OUT, 0, ay, ax, 0)
+    add("filter2d@psf", N, IN, IN, 0, 3, 0, 7)          # (anchor, src == dst AND border: the order)
+    add("filter2d@psf", N, IN, IN, 0, 1, 1, 7)          # (src == dst AND border)
+    add("filter2d@psf", N, IN, IN, 0, 1, 1, 0)
+    for border in (1, 2, 7, -1):
+        add("filter2d@psf", N, IN, OUT, 0, 1, 1, border)
+    add("filter2d@psf", N, BAD, OUT, 0, 1, 1, 7)        # (border AND a bad plane)
+    for src, dst in ((BAD, OUT), (IN, BAD), (S(18), OUT), (IN, ML + 1), (BAD, S(11))):
+        add("filter2d@psf", N, src, dst, 0, 1, 1, 0)
+        add("filter2d@psf", N, src, dst, 0, 1, 1, 3)
+    for op in (-1, 5, 99):
+        add("binary", N, op, IN, OUT, S(3))
+        add("binary", N, op, BAD, OUT, S(3))            # (two errors: the order)
+    for a, b2, dst in ((BAD, OUT, S(3)), (IN, BAD, S(3)), (IN, OUT, BAD), (BAD, S(11), S(18)), (S(6), S(7), S(18))):
+        add("binary@psf", N, 4, a, b2, dst)
+    add("mrs_update@psf", N, 0, S(16), NUL, 1, 0, 1.0)
+    add("mrs_update@psf", N, 0, 0, NUL, 1, 0, 1.0)      # (null tau AND plane == mrs_plane)
+    add("mrs_update@psf", N, BAD, BAD, T4, 1, 0, 1.0)   # (plane == mrs_plane AND a bad plane)
+    for plane, mrs in ((0, 0), (S(16), S(16)), (BAD, S(16)), (0, BAD), (0, S(18)), (ML + 1, S(17)), (BAD, S(18))):
+        add("mrs_update@psf", N, plane, mrs, T4, 1, 0, 1.0)
     return c
+
+
+def accepted_on_purpose(method):
+    return method.endswith("@ok")
 
 
 def key(engine, method, args):
@@ -187,7 +247,7 @@ def answers():
             for method, args in calls(engine):
                 keep = []
                 try:
-                    bp._call(method, *[_convert(a, bp._real, keep) for a in args])
+                    bp._call(method.split("@")[0], *[_convert(a, bp._real, keep) for a in args])
                     out[key(engine, method, args)] = [None, ""]
                 except L.WatrooHipError as e:
                     out[key(engine, method, args)] = [type(e).__name__, str(e)]
@@ -204,7 +264,8 @@ def test_the_core_refuses_what_the_two_engines_refused_in_their_words():
     missing = [k for k in listed if k not in table]
     assert not missing, f"{len(missing)} listed calls are not in the recorded table, first: {missing[0]}"
     got = answers()
-    accepted = [k for k in listed if got[k][0] is None]
+    on_purpose = {key(e, m, a) for e in ("f32", "f64") for m, a in calls(e) if accepted_on_purpose(m)}
+    accepted = [k for k in listed if got[k][0] is None and k not in on_purpose]
     assert not accepted, f"{len(accepted)} calls were not refused, first: {accepted[0]}"
     wrong = [(k, got[k], table[k]) for k in listed if got[k] != table[k]]
     assert not wrong, f"{len(wrong)} refusals changed, first: {wrong[0][0]}: {wrong[0][1]} != recorded {wrong[0][2]}"
@@ -215,7 +276,7 @@ if __name__ == "__main__":
     if "--record" not in sys.argv:
         sys.exit("usage: python tests/test_gpu_batch_core.py --record [--out FILE]")
     got = answers()
-    accepted = [k for k, v in got.items() if v[0] is None]
+    accepted = [k for k, v in got.items() if v[0] is None and not accepted_on_purpose(json.loads(k)[1])]
     if accepted:
         sys.exit("not refused, so not an argument error - take it off the list:\n" + "\n".join(accepted))
     path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else TABLE

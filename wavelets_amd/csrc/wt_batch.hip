@@ -18,13 +18,17 @@
 // over the stack, the support update takes the frame's threshold from a device table.  With fft=True and a large PSF
 // the two products of an iteration are wt_fft.h's six launches over all frames against one kernel spectrum
 // (wt_batch_fft_spectrum / wt_batch_fft_apply).
+// What lives where: this file has the float32 kernels and launch lines, the median select, the fused schedule and the
+// FFT entry points.  The host side both engines share is wt_batch_core.h (planes, checks, tables, transfers, the
+// loops of the transform) and wt_batch_rl.h (richardson_lucy's planes, PSFs and entry points); wt_rl_point.h has the
+// correlation's tile body.  The three threshold sums are shells around one body (wt_batch_threshold_sum), the two
+// pointwise wow kernels around another (wt_batch_wow_frame).
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
-#include "wt_batch_core.h"
+#include "wt_batch_rl.h"
 #include "wt_reduce.h"
-#include "wt_rl_point.h"
 #include "wt_rng.h"
 #include "wt_stencil_launch.h"
 #include "wt_unit_probe.h"
@@ -37,20 +41,13 @@ struct WtBatchSel {                 // select state of one rank of one frame
     uint32_t nan;                   // NaN pixels of the frame (counted by the first level)
 };
 
-struct wt_batch : WtBatchCore<float> {
-    wt_batch() : WtBatchCore<float>("wt_batch") {}
+struct wt_batch : WtBatchRl<float> {            // (richardson_lucy's planes and PSFs: wt_batch_rl.h; this batch's from its creation)
+    wt_batch() : WtBatchRl<float>("wt_batch") {}
     wt_plan geo;                    // ONE frame's geometry, context and family: what the fused launches read (no planes)
     uint32_t *d_hist = nullptr;     // [n][2 ranks][WT_HIST_BINS]
     WtBatchSel *d_sel = nullptr;    // [n][2 ranks]
     WtBatchSel *h_sel = nullptr;    // pinned copy
     // (d_tau: [n][2 * WT_MAX_SUM_PLANES], the thresholds of wt_batch_denoise_sum; wt_batch_enhance_sum: then the weights)
-    // richardson_lucy: WT_PLANE_SCRATCH(6 .. 10) = data, psi, phi, residual, correlation; WT_PLANE_SCRATCH(16 + s) = the
-    // support plane of scale s (utils.richardson_lucy's plane ids); the forward / backward PSF of wt_batch_set_psf
-    float *rl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    std::vector<float *> mrs;       // max_level entries
-    float *d_psf[2] = {nullptr, nullptr};
-    size_t psf_cap[2] = {0, 0};
-    int psf_kh[2] = {0, 0}, psf_kw[2] = {0, 0};
     // richardson_lucy(fft=True): two complex work arrays of n frames, ONE kernel spectrum and the twiddle tables
     // (wt_fft.h), allocated by the first wt_batch_fft_spectrum
     WtFftState fft;
@@ -136,94 +133,46 @@ __global__ __launch_bounds__(256) void wt_batch_select_kernel(uint32_t *hist, Wt
     for (int i = 0; i < per; ++i) h[threadIdx.x * per + i] = 0;
 }
 
-// wt_denoise_sum_kernel (wt_kernels_apps.h) with one threshold row per frame: tau[frame * n_den + k], the frame
-// from the flat index.  Same arithmetic (no noise plane: nn = 1), contraction off: the bits of the per-frame call.
+// (`block`: blockDim.x, read by the shells - only inside a kernel does the compiler fold it to the one load the
+//  launch bound allows - and handed to the shared bodies below)
+// wt_denoise_sum_kernel (wt_kernels_apps.h) over the frames as one flat range, the frame from the flat index and its
+// row of the table: ft[k] = the threshold of plane k.  Same arithmetic, contraction off: the bits of the per-frame call.
+//   NOISE   nn comes from the batch's noise plane at the same flat index, as wt_denoise_sum_kernel reads its noise
+//           plane (Coefficients.significance with an ndarray noise, watroo/wavelets.py:133-141; a frame whose noise is
+//           a scalar has ones in its slot: tauf * 1.f and t * 1.0 are exact); else nn = 1
+//   ROW_WGT the weight is the frame's too (utils.enhance per channel, watroo/utils.py:60-78): rows of 2 * n_den,
+//           ft[n_den + k] a double rounded to float here as wt_denoise_sum rounds it on the host; else a.wgt[k]
 struct BatchDenoiseArgs {
     float *p[WT_MAX_SUM_PLANES];
     float wgt[WT_MAX_SUM_PLANES];
     int n, n_den, soft, write_back;
 };
-__global__ __launch_bounds__(256) void wt_batch_denoise_sum_kernel(BatchDenoiseArgs a, const double *tau, float *out, int64_t n4, int64_t f4)
-{
-#pragma clang fp contract(off)
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        const double *ft = tau + (i / f4) * a.n_den;
-        const float nn[4] = {1.f, 1.f, 1.f, 1.f};
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int k = 0; k < a.n; ++k) {
-            const float4 v = reinterpret_cast<const float4 *>(a.p[k])[i];
-            float c[4] = {v.x, v.y, v.z, v.w};
-            if (k < a.n_den) {
-                const double t = ft[k];
-                const float tauf = (float)t;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float sgn = t > 0.0 ? wt_sig(c[j], tauf * nn[j], t * (double)nn[j], a.soft) : 1.f;
-                    c[j] = c[j] * (a.wgt[k] * sgn);
-                }
-                if (a.write_back) reinterpret_cast<float4 *>(a.p[k])[i] = make_float4(c[0], c[1], c[2], c[3]);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = k == 0 ? c[j] : acc[j] + c[j];
-        }
-        reinterpret_cast<float4 *>(out)[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    }
-}
-
-// wt_batch_denoise_sum_kernel with a per-pixel noise map (Coefficients.significance with an ndarray noise,
-// watroo/wavelets.py:133-141): nn comes from the batch's noise plane at the same flat index, as wt_denoise_sum_kernel
-// reads its noise plane.  A frame whose noise is a scalar has ones in its slot of the plane (tauf * 1.f and
-// t * 1.0 are exact).  Same arithmetic, contraction off: the bits of the per-frame call.
-__global__ __launch_bounds__(256) void wt_batch_denoise_sum_map_kernel(BatchDenoiseArgs a, const double *tau, const float *noise, float *out,
-                                                                       int64_t n4, int64_t f4)
-{
-#pragma clang fp contract(off)
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        const double *ft = tau + (i / f4) * a.n_den;
-        const float4 nz = reinterpret_cast<const float4 *>(noise)[i];
-        const float nn[4] = {nz.x, nz.y, nz.z, nz.w};
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int k = 0; k < a.n; ++k) {
-            const float4 v = reinterpret_cast<const float4 *>(a.p[k])[i];
-            float c[4] = {v.x, v.y, v.z, v.w};
-            if (k < a.n_den) {
-                const double t = ft[k];
-                const float tauf = (float)t;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float sgn = t > 0.0 ? wt_sig(c[j], tauf * nn[j], t * (double)nn[j], a.soft) : 1.f;
-                    c[j] = c[j] * (a.wgt[k] * sgn);
-                }
-                if (a.write_back) reinterpret_cast<float4 *>(a.p[k])[i] = make_float4(c[0], c[1], c[2], c[3]);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = k == 0 ? c[j] : acc[j] + c[j];
-        }
-        reinterpret_cast<float4 *>(out)[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    }
-}
-
-// wt_batch_denoise_sum_kernel with one WEIGHT row per frame as well (utils.enhance per channel, watroo/utils.py:60-78):
-// tab[frame * 2 * n_den + k] = tau, tab[frame * 2 * n_den + n_den + k] = the weight (a double, rounded to float here as
-// wt_denoise_sum rounds it on the host), the frame from the flat index.  Same arithmetic, contraction off: the bits of
-// the per-frame call.
 struct BatchEnhanceArgs {
     float *p[WT_MAX_SUM_PLANES];
     int n, n_den, soft, write_back;
 };
-__global__ __launch_bounds__(256) void wt_batch_enhance_sum_kernel(BatchEnhanceArgs a, const double *tab, float *out, int64_t n4, int64_t f4)
+template <bool NOISE, bool ROW_WGT, typename Args>
+__device__ __forceinline__ void wt_batch_threshold_sum(const Args &a, const double *tab, const float *noise, float *out, int64_t n4, int64_t f4,
+                                                       unsigned block)
 {
 #pragma clang fp contract(off)
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        const double *ft = tab + (i / f4) * 2 * a.n_den;
-        const float nn[4] = {1.f, 1.f, 1.f, 1.f};
+    for (int64_t i = (int64_t)blockIdx.x * block + threadIdx.x; i < n4; i += (int64_t)gridDim.x * block) {
+        const double *ft = tab + (ROW_WGT ? (i / f4) * 2 * a.n_den : (i / f4) * a.n_den);
+        float nn[4] = {1.f, 1.f, 1.f, 1.f};
+        if constexpr (NOISE) {
+            const float4 nz = reinterpret_cast<const float4 *>(noise)[i];
+            nn[0] = nz.x; nn[1] = nz.y; nn[2] = nz.z; nn[3] = nz.w;
+        }
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         for (int k = 0; k < a.n; ++k) {
             const float4 v = reinterpret_cast<const float4 *>(a.p[k])[i];
             float c[4] = {v.x, v.y, v.z, v.w};
             if (k < a.n_den) {
                 const double t = ft[k];
-                const float tauf = (float)t, wgt = (float)ft[a.n_den + k];
+                const float tauf = (float)t;
+                float wgt;
+                if constexpr (ROW_WGT) wgt = (float)ft[a.n_den + k];
+                else wgt = a.wgt[k];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float sgn = t > 0.0 ? wt_sig(c[j], tauf * nn[j], t * (double)nn[j], a.soft) : 1.f;
@@ -237,52 +186,57 @@ __global__ __launch_bounds__(256) void wt_batch_enhance_sum_kernel(BatchEnhanceA
         reinterpret_cast<float4 *>(out)[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
     }
 }
-
-// wt_wow_kernel (wt_kernels_apps.h) with the frame as grid y: no power plane, no noise map, the frame's {tau, factor}
-// (wow's last plane, whitening=False, h >= 1 - watroo/utils.py:185-203).  Same wt_wow_point: the bits of the per-frame call.
-__global__ __launch_bounds__(256) void wt_batch_wow_kernel(float *c, float *gamma, int64_t f4, const double *ptab, int soft)
+__global__ __launch_bounds__(256) void wt_batch_denoise_sum_kernel(BatchDenoiseArgs a, const double *tau, float *out, int64_t n4, int64_t f4)
 {
-    const int f = blockIdx.y;
-    const double tau = ptab[2 * f];
-    const float tauf = (float)tau, factor = (float)ptab[2 * f + 1];
-    float4 *cf = reinterpret_cast<float4 *>(c) + (int64_t)f * f4;
-    float4 *gf = gamma ? reinterpret_cast<float4 *>(gamma) + (int64_t)f * f4 : nullptr;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < f4; i += (int64_t)gridDim.x * blockDim.x) {
-        const float4 v = cf[i];
-        float4 gm = make_float4(0, 0, 0, 0);
-        if (gf) gm = gf[i];
-        float in[4] = {v.x, v.y, v.z, v.w};
-        float gg[4] = {gm.x, gm.y, gm.z, gm.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) in[k] = wt_wow_point(in[k], 1.f, false, 1.f, tau, tauf, soft, factor, gg[k]);
-        cf[i] = make_float4(in[0], in[1], in[2], in[3]);
-        if (gf) gf[i] = make_float4(gg[0], gg[1], gg[2], gg[3]);
-    }
+    wt_batch_threshold_sum<false, false>(a, tau, nullptr, out, n4, f4, blockDim.x);
+}
+__global__ __launch_bounds__(256) void wt_batch_denoise_sum_map_kernel(BatchDenoiseArgs a, const double *tau, const float *noise, float *out,
+                                                                       int64_t n4, int64_t f4)
+{
+    wt_batch_threshold_sum<true, false>(a, tau, noise, out, n4, f4, blockDim.x);
+}
+__global__ __launch_bounds__(256) void wt_batch_enhance_sum_kernel(BatchEnhanceArgs a, const double *tab, float *out, int64_t n4, int64_t f4)
+{
+    wt_batch_threshold_sum<false, true>(a, tab, nullptr, out, n4, f4, blockDim.x);
 }
 
-// wt_batch_wow_kernel with a per-pixel noise map (watroo/utils.py:199 on an ndarray noise, wavelets.py:133-141): nn[k]
-// from the frame's slot of the batch's noise plane, as wt_wow_kernel reads its noise plane.  Same wt_wow_point.
-__global__ __launch_bounds__(256) void wt_batch_wow_map_kernel(float *c, const float *noise, float *gamma, int64_t f4, const double *ptab, int soft)
+// wt_wow_kernel (wt_kernels_apps.h) with the frame as grid y: no power plane, the frame's {tau, factor} (wow's last
+// plane, whitening=False, h >= 1 - watroo/utils.py:185-203).  NOISE: nn[k] from the frame's slot of the batch's noise
+// plane, as wt_wow_kernel reads its noise plane (watroo/utils.py:199 on an ndarray noise, wavelets.py:133-141); else
+// nn = 1.  Same wt_wow_point: the bits of the per-frame call.
+template <bool NOISE>
+__device__ __forceinline__ void wt_batch_wow_frame(float *c, const float *noise, float *gamma, int64_t f4, const double *ptab, int soft, unsigned block)
 {
     const int f = blockIdx.y;
     const double tau = ptab[2 * f];
     const float tauf = (float)tau, factor = (float)ptab[2 * f + 1];
     float4 *cf = reinterpret_cast<float4 *>(c) + (int64_t)f * f4;
-    const float4 *nf4 = reinterpret_cast<const float4 *>(noise) + (int64_t)f * f4;
+    const float4 *nf4 = NOISE ? reinterpret_cast<const float4 *>(noise) + (int64_t)f * f4 : nullptr;
     float4 *gf = gamma ? reinterpret_cast<float4 *>(gamma) + (int64_t)f * f4 : nullptr;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < f4; i += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t i = (int64_t)blockIdx.x * block + threadIdx.x; i < f4; i += (int64_t)gridDim.x * block) {
         const float4 v = cf[i];
-        const float4 nz = nf4[i];
+        float nn[4] = {1.f, 1.f, 1.f, 1.f};
+        if constexpr (NOISE) {
+            const float4 nz = nf4[i];
+            nn[0] = nz.x; nn[1] = nz.y; nn[2] = nz.z; nn[3] = nz.w;
+        }
         float4 gm = make_float4(0, 0, 0, 0);
         if (gf) gm = gf[i];
         float in[4] = {v.x, v.y, v.z, v.w};
-        const float nn[4] = {nz.x, nz.y, nz.z, nz.w};
         float gg[4] = {gm.x, gm.y, gm.z, gm.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) in[k] = wt_wow_point(in[k], 1.f, false, nn[k], tau, tauf, soft, factor, gg[k]);
         cf[i] = make_float4(in[0], in[1], in[2], in[3]);
         if (gf) gf[i] = make_float4(gg[0], gg[1], gg[2], gg[3]);
     }
+}
+__global__ __launch_bounds__(256) void wt_batch_wow_kernel(float *c, float *gamma, int64_t f4, const double *ptab, int soft)
+{
+    wt_batch_wow_frame<false>(c, nullptr, gamma, f4, ptab, soft, blockDim.x);
+}
+__global__ __launch_bounds__(256) void wt_batch_wow_map_kernel(float *c, const float *noise, float *gamma, int64_t f4, const double *ptab, int soft)
+{
+    wt_batch_wow_frame<true>(c, noise, gamma, f4, ptab, soft, blockDim.x);
 }
 
 // wt_gamma_kernel (wt_kernels_apps.h, watroo/utils.py:212-217) with the frame as grid y and its own {gmin, gmax}
@@ -317,45 +271,21 @@ __global__ __launch_bounds__(256) void wt_batch_gamma_kernel(float *recon, float
 
 __global__ __launch_bounds__(256) void wt_batch_fill_kernel(float *d, int64_t n4, float value)
 {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
-        reinterpret_cast<float4 *>(d)[i] = make_float4(value, value, value, value);
+    batch_fill_groups(reinterpret_cast<float4 *>(d), n4, make_float4(value, value, value, value), blockDim.x);
 }
-
-// frame 0 of a plane -> frames 1 .. gridDim.y (a noise map shared by the frames of a chunk crosses PCIe once)
 __global__ __launch_bounds__(256) void wt_batch_replicate_kernel(float *d, int64_t f4)
 {
-    const float4 *src = reinterpret_cast<const float4 *>(d);
-    float4 *dst = reinterpret_cast<float4 *>(d) + (int64_t)(blockIdx.y + 1) * f4;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < f4; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i];
+    batch_replicate_groups(reinterpret_cast<float4 *>(d), f4, blockDim.x);
 }
 
-// wt_filter2d_kernel (wt_kernels_apps.h) for the frames of a batch: grid z = the frame, each its own image (the
-// border rules act at the frame's borders).  Staging, tile geometry and the chain of fmaf per output are
-// wt_rl_point.h's; !SKEW is the per-image tap loop (one LDS read per FMA), the one wt_batch_filter2d launches; SKEW
-// walks every staged row once for the four output rows of a thread (wt_f2d_taps_skewed: one LDS read per four FMAs,
-// measured slower) - identical bits either way.
+// wt_filter2d_kernel (wt_kernels_apps.h) for the frames of a batch: wt_f2d_batch_tile (wt_rl_point.h).  !SKEW is the
+// one wt_batch_filter2d launches; SKEW (measured slower) only on request.
 template <bool WRAP, bool SKEW>
 __global__ __launch_bounds__(256) void wt_batch_filter2d_kernel(const float *in, float *out, Geo g, int64_t fstride, const float *__restrict__ psf,
                                                                 int kh, int kw, int ay, int ax)
 {
     extern __shared__ float tile[];
-    in += (int64_t)blockIdx.z * fstride;
-    out += (int64_t)blockIdx.z * fstride;
-    const int tw = WT_F2D_TW + kw - 1, th = WT_F2D_TH + kh - 1;
-    const int x0 = blockIdx.x * WT_F2D_TW, ly0 = blockIdx.y * WT_F2D_TH;
-    wt_f2d_stage<WRAP>(tile, in, g, x0, ly0, tw, th, ay, ax);
-    __syncthreads();
-    const int x = x0 + threadIdx.x;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    if (SKEW) wt_f2d_taps_skewed(tile, tw, psf, kh, kw, acc);
-    else wt_f2d_taps(tile, tw, psf, kw, kh, kw, acc);
-    if (x < g.W) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int ly = ly0 + threadIdx.y * 4 + r;
-            if (ly < g.H) out[(int64_t)ly * g.P + x] = acc[r];
-        }
-    }
+    wt_f2d_batch_tile<WRAP, SKEW>(tile, in, out, g, fstride, psf, kh, kw, ay, ax);
 }
 
 // wt_mrs_kernel (wt_kernels_apps.h) with the frame as grid y and its own tau (ptab[2 * f]; <= 0: significance one);
@@ -399,15 +329,6 @@ __global__ __launch_bounds__(256) void wt_batch_reduce_final_kernel(const double
 }
 
 // ------------------------------------------------------------------------------------------------ host
-// the planes only the float32 batch has (WtBatchCore::extra_plane): richardson_lucy's
-static float **batch_rl_plane(WtBatchCore<float> *core, int id)
-{
-    wt_batch *b = static_cast<wt_batch *>(core);
-    if (id <= WT_PLANE_SCRATCH(6) && id >= WT_PLANE_SCRATCH(10)) return &b->rl[WT_PLANE_SCRATCH(6) - id];
-    if (id <= WT_PLANE_SCRATCH(16) && id > WT_PLANE_SCRATCH(16) - (int)b->mrs.size()) return &b->mrs[WT_PLANE_SCRATCH(16) - id];
-    return nullptr;
-}
-
 // the fused schedule of `level` scales, or an error: the passes with a sum run fused kernels only; `single`: a
 // single-scale pass without a fused kernel runs the batched MODE_DECOMP stencil (as wt_decompose_pass on a plan)
 static int batch_schedule(wt_batch *b, int level, int32_t *tr, int *np, const char *who, bool single)
@@ -418,13 +339,6 @@ static int batch_schedule(wt_batch *b, int level, int32_t *tr, int *np, const ch
         if (!wt_fused_has_pass(tr[3 * i], tr[3 * i + 1], b->family) && !(single && tr[3 * i + 1] == 1))
             WT_FAIL("%s: %d scales have no all-fused schedule (wt_plan_fused_ok): not a batch case", who, level);
     return 0;
-}
-
-// x blocks per frame of the batched pointwise kernels (grid y = the frame): about flat_grid's 2048 in all
-static unsigned batch_flat_blocks(const wt_batch *b, int nf)
-{
-    const int64_t f4 = b->fstride / 4;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((f4 + 255) / 256, (2048 + nf - 1) / nf));
 }
 
 static int batch_pass(wt_batch *b, int nf, int cur, int nxt, int s0, int ns, int acc, int sum_plane, bool first)
@@ -454,10 +368,7 @@ static void batch_free(wt_batch *b, int *bad)
     auto f = [&](void *q) { if (q && hipFree(q) != hipSuccess) *bad = 1; };
     f(b->d_hist);
     f(b->d_sel);
-    for (float *q : b->rl) f(q);
-    for (float *q : b->mrs) f(q);
-    f(b->d_psf[0]);
-    f(b->d_psf[1]);
+    batch_rl_release(b, bad);
     for (void *q : b->fft_allocs) f(q);
     if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) *bad = 1;
 }
@@ -472,9 +383,7 @@ extern "C" int wt_batch_create(wt_ctx *ctx, int n, int H, int W, int family, int
     b->geo.family = family;
     b->geo.max_level = max_level;
     b->geo.g = b->g;
-    b->mrs.assign(std::min(max_level, WT_NUM_SCRATCH - 16), nullptr);
-    b->extra_plane = batch_rl_plane;
-    b->extra_planes = ", 6..10, 16.." + std::to_string(15 + (int)b->mrs.size());
+    batch_rl_own_planes(b);
     if (!wt_fused_supported(&b->geo)) {
         delete b;
         WT_FAIL("wt_batch_create: rows of %d pixels are too wide for the fused passes", W);
@@ -638,19 +547,15 @@ static int batch_denoise_sum(wt_batch *b, int nf, int count, int dst, int n_den,
     if (noise_plane != WT_PLANE_NONE && (noise_plane == dst || (noise_plane >= 0 && noise_plane < count)))
         WT_FAIL("%s: the noise plane %d is a plane of the sum", who, noise_plane);
     BatchDenoiseArgs a{};
-    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
-    for (int i = 0; i < count; ++i) {
-        WT_TRY(batch_plane(b, i, &a.p[i]));
-        a.wgt[i] = i < n_den ? (float)wgt[i] : 1.f;
-    }
     float *o = nullptr, *nz = nullptr;
-    WT_TRY(batch_plane(b, dst, &o));
+    WT_TRY(batch_sum_args(b, count, dst, n_den, soft, write_back, &a, &o));
+    for (int i = 0; i < count; ++i) a.wgt[i] = i < n_den ? (float)wgt[i] : 1.f;
     if (noise_plane != WT_PLANE_NONE) WT_TRY(batch_plane(b, noise_plane, &nz));
+    // rows of n_den thresholds (one 0.0 when no plane is thresholded)
     const int nt = std::max(n_den, 1);
-    // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
-    WT_HIP(hipStreamSynchronize(b->ctx->stream));
-    for (int i = 0; i < nf * nt; ++i) b->h_tau[i] = n_den ? tau[i] : 0.0;
-    WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * nt * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    WT_TRY(batch_sum_table(b, nf, nt, [&](int f, double *r) {
+        for (int k = 0; k < nt; ++k) r[k] = n_den ? tau[f * nt + k] : 0.0;
+    }));
     const int64_t n4 = (int64_t)nf * b->fstride / 4;
     if (nz) {
         ProfScope ps(b->ctx, "wt_batch_denoise_sum_map_kernel");
@@ -685,19 +590,15 @@ extern "C" int wt_batch_enhance_sum(wt_batch *b, int nf, int count, int dst, int
     WtGuard guard_(b->ctx);
     WT_TRY(batch_check_sum(b, count, dst, n_den, 1, tau, wgt, "wt_batch_enhance_sum"));
     BatchEnhanceArgs a{};
-    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
-    for (int i = 0; i < count; ++i) WT_TRY(batch_plane(b, i, &a.p[i]));
     float *o = nullptr;
-    WT_TRY(batch_plane(b, dst, &o));
-    // (the table goes up stream-ordered from pinned staging: the previous call's kernel may still read d_tau)
-    WT_HIP(hipStreamSynchronize(b->ctx->stream));
-    const int row = 2 * n_den;                              // nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables
-    for (int f = 0; f < nf; ++f)
+    WT_TRY(batch_sum_args(b, count, dst, n_den, soft, write_back, &a, &o));
+    // rows of n_den thresholds, then n_den weights (nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables)
+    WT_TRY(batch_sum_table(b, nf, 2 * n_den, [&](int f, double *r) {
         for (int k = 0; k < n_den; ++k) {
-            b->h_tau[f * row + k] = tau[f * n_den + k];
-            b->h_tau[f * row + n_den + k] = wgt[f * n_den + k];
+            r[k] = tau[f * n_den + k];
+            r[n_den + k] = wgt[f * n_den + k];
         }
-    WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * row * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    }));
     const int64_t n4 = (int64_t)nf * b->fstride / 4;
     ProfScope ps(b->ctx, "wt_batch_enhance_sum_kernel");
     hipLaunchKernelGGL(wt_batch_enhance_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, b->ctx->stream, a, (const double *)b->d_tau,
@@ -720,29 +621,20 @@ extern "C" int wt_batch_anscombe(wt_batch *b, int nf, int src, int dst, float al
 // ------------------------------------------------------------------------------------------------ wow
 extern "C" int wt_batch_fill(wt_batch *b, int nf, int plane, float value)
 {
-    WT_TRY(batch_check_frames(b, nf, "wt_batch_fill"));
-    WtGuard guard_(b->ctx);
-    float *d = nullptr;
-    WT_TRY(batch_plane(b, plane, &d));
-    const int64_t n4 = (int64_t)nf * b->fstride / 4;
-    ProfScope ps(b->ctx, "wt_batch_fill_kernel");
-    hipLaunchKernelGGL(wt_batch_fill_kernel, dim3(flat_grid(n4)), dim3(256), 0, b->ctx->stream, d, n4, value);
-    WT_HIP(hipGetLastError());
-    return 0;
+    return batch_fill(b, nf, plane, "wt_batch_fill", [&](float *d) {
+        const int64_t n4 = (int64_t)nf * b->fstride / 4;
+        ProfScope ps(b->ctx, "wt_batch_fill_kernel");
+        hipLaunchKernelGGL(wt_batch_fill_kernel, dim3(flat_grid(n4)), dim3(256), 0, b->ctx->stream, d, n4, value);
+    });
 }
 
 extern "C" int wt_batch_replicate(wt_batch *b, int nf, int plane)
 {
-    WT_TRY(batch_check_frames(b, nf, "wt_batch_replicate"));
-    WtGuard guard_(b->ctx);
-    float *d = nullptr;
-    WT_TRY(batch_plane(b, plane, &d));
-    if (nf == 1) return 0;
-    const int64_t f4 = b->fstride / 4;
-    ProfScope ps(b->ctx, "wt_batch_replicate_kernel");
-    hipLaunchKernelGGL(wt_batch_replicate_kernel, dim3(batch_flat_blocks(b, nf), nf - 1), dim3(256), 0, b->ctx->stream, d, f4);
-    WT_HIP(hipGetLastError());
-    return 0;
+    return batch_replicate(b, nf, plane, "wt_batch_replicate", [&](float *d) {
+        const int64_t f4 = b->fstride / 4;
+        ProfScope ps(b->ctx, "wt_batch_replicate_kernel");
+        hipLaunchKernelGGL(wt_batch_replicate_kernel, dim3(batch_frame_blocks(f4, nf), nf - 1), dim3(256), 0, b->ctx->stream, d, f4);
+    });
 }
 
 // frame f of the plane <- the field wt_fill_normal(seed, first_trial + f) gives a wt_plan of the frame's shape
@@ -766,11 +658,11 @@ static int batch_wow_update(wt_batch *b, int nf, int plane, const double *tau, i
     WT_TRY(batch_wow_update_args(b, nf, plane, tau, factor, gamma_plane, noise_plane, who, &c, &gm, &nz, &dt));
     if (nz) {
         ProfScope ps(b->ctx, "wt_batch_wow_map_kernel");
-        hipLaunchKernelGGL(wt_batch_wow_map_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, c, (const float *)nz, gm,
+        hipLaunchKernelGGL(wt_batch_wow_map_kernel, dim3(batch_frame_blocks(b->fstride / 4, nf), nf), dim3(256), 0, b->ctx->stream, c, (const float *)nz, gm,
                            b->fstride / 4, dt, soft);
     } else {
         ProfScope ps(b->ctx, "wt_batch_wow_kernel");
-        hipLaunchKernelGGL(wt_batch_wow_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, c, gm, b->fstride / 4, dt, soft);
+        hipLaunchKernelGGL(wt_batch_wow_kernel, dim3(batch_frame_blocks(b->fstride / 4, nf), nf), dim3(256), 0, b->ctx->stream, c, gm, b->fstride / 4, dt, soft);
     }
     WT_HIP(hipGetLastError());
     return 0;
@@ -843,7 +735,7 @@ extern "C" int wt_batch_gamma_blend(wt_batch *b, int nf, int recon, int gamma_pl
     const double *dt = nullptr;
     WT_TRY(batch_pairs(b, nf, gmin, gmax, &dt));
     ProfScope ps(b->ctx, "wt_batch_gamma_kernel");
-    hipLaunchKernelGGL(wt_batch_gamma_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, r, g, b->fstride / 4, dt, inv_gamma, h);
+    hipLaunchKernelGGL(wt_batch_gamma_kernel, dim3(batch_frame_blocks(b->fstride / 4, nf), nf), dim3(256), 0, b->ctx->stream, r, g, b->fstride / 4, dt, inv_gamma, h);
     WT_HIP(hipGetLastError());
     return 0;
 }
@@ -860,116 +752,44 @@ extern "C" int wt_batch_plane_sum(wt_batch *b, int nf, int first, int count, int
 }
 
 // ------------------------------------------------------------------------------------------------ richardson_lucy
-// host logic: *ok = 1 when wt_batch_set_psf takes a kh x kw PSF - one wt_filter2d_ex applies in ONE launch
+// (wt_batch_rl.h; the planes of richardson_lucy are this batch's from its creation on)
 extern "C" int wt_batch_psf_ok(int kh, int kw, int *ok)
 {
-    if (!ok) WT_FAIL("wt_batch_psf_ok: null pointer");
-    *ok = wt_f2d_single_launch(kh, kw) ? 1 : 0;
-    return 0;
+    return batch_psf_ok<float>(kh, kw, ok, "wt_batch_psf_ok");
 }
 
-// One of the two PSF operands of a richardson_lucy call (slot 0: forward, watroo/utils.py:257; slot 1: backward,
-// utils.py:286) -> device memory of the batch, once per call: the iterations then correlate without a stream drain
-// and without a PSF copy (wt_filter2d_ex does both on every call - its kernel comes from caller-owned memory).
 extern "C" int wt_batch_set_psf(wt_batch *b, int slot, const float *kernel, int kh, int kw)
 {
-    if (!b || !kernel) WT_FAIL("wt_batch_set_psf: null pointer");
-    WtGuard guard_(b->ctx);
-    if (slot < 0 || slot > 1) WT_FAIL("wt_batch_set_psf: slot %d (0: forward, 1: backward)", slot);
-    if (!wt_f2d_single_launch(kh, kw))
-        WT_FAIL("wt_batch_set_psf: a %d x %d PSF is not applied in one launch (at most %d taps, rows of at most %d, an LDS tile of at most %d KB)",
-                kh, kw, WT_F2D_MAX_TAPS, WT_F2D_MAX_KW, WT_F2D_MAX_LDS / 1024);
-    const size_t ntaps = (size_t)kh * kw;
-    // a launch on the stream may still read the slot, and `kernel` is the caller's: drain, then copy synchronously
-    WT_HIP(hipStreamSynchronize(b->ctx->stream));
-    if (ntaps > b->psf_cap[slot]) {
-        (void)hipFree(b->d_psf[slot]);
-        b->d_psf[slot] = nullptr;
-        b->psf_cap[slot] = 0;
-        b->psf_kh[slot] = b->psf_kw[slot] = 0;
-        WT_HIP(hipMalloc((void **)&b->d_psf[slot], ntaps * sizeof(float)));
-        b->psf_cap[slot] = ntaps;
-    }
-    WT_HIP(hipMemcpy(b->d_psf[slot], kernel, ntaps * sizeof(float), hipMemcpyHostToDevice));
-    b->psf_kh[slot] = kh;
-    b->psf_kw[slot] = kw;
-    return 0;
+    return batch_set_psf(b, slot, kernel, kh, kw, "wt_batch_set_psf");
 }
 
-// wt_filter2d_ex per frame (watroo/utils.py:257,286; periodic: the circular products of utils.py:245-254,284) with
-// the PSF of `slot`: one launch for all active frames
 // (measured, tools/bench_rl_stack.py: the per-image tap loop is about twice as fast as the row-skewed one at every
 //  shape - 10 to 18 against 5 to 10 TFMA/s - so the skewed loop runs only on request, for that measurement)
 static int g_batch_f2d_plain = getenv("WT_BATCH_F2D_SKEW") ? 0 : 1;
 extern "C" int wt_batch_filter2d(wt_batch *b, int nf, int src, int dst, int slot, int ay, int ax, int border)
 {
-    WT_TRY(batch_check_frames(b, nf, "wt_batch_filter2d"));
-    WtGuard guard_(b->ctx);
-    if (slot < 0 || slot > 1 || !b->d_psf[slot] || !b->psf_kh[slot]) WT_FAIL("wt_batch_filter2d: PSF slot %d is not set (wt_batch_set_psf)", slot);
-    const int kh = b->psf_kh[slot], kw = b->psf_kw[slot];
-    if (!wt_f2d_single_launch(kh, kw)) WT_FAIL("wt_batch_filter2d: a %d x %d PSF is not applied in one launch", kh, kw);
-    if (ay < 0 || ay >= kh || ax < 0 || ax >= kw) WT_FAIL("wt_batch_filter2d: anchor (%d, %d) outside the %d x %d kernel", ay, ax, kh, kw);
-    if (src == dst) WT_FAIL("wt_batch_filter2d: src and dst must differ");
-    if (border != WT_BORDER_SYMMETRIC && border != WT_BORDER_PERIODIC) WT_FAIL("wt_batch_filter2d: border %d unsupported (symmetric or periodic)", border);
-    const Geo &g = b->geo.g;
-    dim3 grid((g.W + WT_F2D_TW - 1) / WT_F2D_TW, (g.H + WT_F2D_TH - 1) / WT_F2D_TH, nf), block(64, 4);
-    if (grid.y > 65535u) WT_FAIL("wt_batch_filter2d: frames of %d rows are too tall (%u row tiles, at most 65535)", g.H, grid.y);
-    if (grid.z > 65535u) WT_FAIL("wt_batch_filter2d: %d frames in one launch (at most 65535)", nf);
-    float *in = nullptr, *o = nullptr;
-    WT_TRY(batch_plane(b, src, &in));
-    WT_TRY(batch_plane(b, dst, &o));
-    const size_t lds = wt_f2d_lds_bytes(kh, kw);
-    ProfScope ps(b->ctx, "wt_batch_filter2d_kernel");
-    #define WT_BF2D_LAUNCH(WRAP, SKEW)                                                                                               \
-        do {                                                                                                                         \
-            if (lds > 64 * 1024)                                                                                                     \
-                WT_HIP(hipFuncSetAttribute((const void *)wt_batch_filter2d_kernel<WRAP, SKEW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL((wt_batch_filter2d_kernel<WRAP, SKEW>), grid, block, lds, b->ctx->stream, (const float *)in, o, g, b->fstride, \
-                               (const float *)b->d_psf[slot], kh, kw, ay, ax);                                                       \
-        } while (0)
-    if (border == WT_BORDER_PERIODIC) { if (g_batch_f2d_plain) WT_BF2D_LAUNCH(true, false); else WT_BF2D_LAUNCH(true, true); }
-    else { if (g_batch_f2d_plain) WT_BF2D_LAUNCH(false, false); else WT_BF2D_LAUNCH(false, true); }
-    #undef WT_BF2D_LAUNCH
-    WT_HIP(hipGetLastError());
-    return 0;
+    return batch_filter2d(b, nf, src, dst, slot, ay, ax, border, "wt_batch_filter2d", "wt_batch_filter2d_kernel", [](bool periodic) {
+        if (periodic) return g_batch_f2d_plain ? wt_batch_filter2d_kernel<true, false> : wt_batch_filter2d_kernel<true, true>;
+        return g_batch_f2d_plain ? wt_batch_filter2d_kernel<false, false> : wt_batch_filter2d_kernel<false, true>;
+    });
 }
 
-// wt_binary over the active frames (watroo/utils.py:259,280-281,288)
 extern "C" int wt_batch_binary(wt_batch *b, int nf, int op, int a, int b2, int dst)
 {
-    WT_TRY(batch_check_frames(b, nf, "wt_batch_binary"));
-    WtGuard guard_(b->ctx);
-    if (op < 0 || op > WT_OP_ADD_DIV) WT_FAIL("wt_batch_binary: unknown op %d", op);
-    float *pa = nullptr, *pb = nullptr, *pd = nullptr;
-    WT_TRY(batch_plane(b, a, &pa));
-    WT_TRY(batch_plane(b, b2, &pb));
-    WT_TRY(batch_plane(b, dst, &pd));
-    const int64_t n4 = (int64_t)nf * b->fstride / 4;
-    ProfScope ps(b->ctx, "wt_batch_binary_kernel");
-    hipLaunchKernelGGL(wt_batch_binary_kernel, dim3(flat_grid(n4)), dim3(256), 0, b->ctx->stream, (const float *)pa, (const float *)pb, pd, n4, op);
-    WT_HIP(hipGetLastError());
-    return 0;
+    return batch_binary(b, nf, op, a, b2, dst, "wt_batch_binary", [&](const float *pa, const float *pb, float *pd) {
+        const int64_t n4 = (int64_t)nf * b->fstride / 4;
+        ProfScope ps(b->ctx, "wt_batch_binary_kernel");
+        hipLaunchKernelGGL(wt_batch_binary_kernel, dim3(flat_grid(n4)), dim3(256), 0, b->ctx->stream, pa, pb, pd, n4, op);
+    });
 }
 
-// wt_mrs_update per frame (watroo/utils.py:263-276) with the frame's tau[f]; scalar noise only
 extern "C" int wt_batch_mrs_update(wt_batch *b, int nf, int plane, int mrs_plane, const double *tau, int soft, int persistent, float inv_pow)
 {
-    WT_TRY(batch_check_frames(b, nf, "wt_batch_mrs_update"));
-    WtGuard guard_(b->ctx);
-    if (!tau) WT_FAIL("wt_batch_mrs_update: null tau");
-    if (plane == mrs_plane) WT_FAIL("wt_batch_mrs_update: plane and mrs_plane must differ");
-    float *c = nullptr, *m = nullptr;
-    WT_TRY(batch_plane(b, plane, &c));
-    WT_TRY(batch_plane(b, mrs_plane, &m));
-    std::vector<double> pairs((size_t)nf * 2, 0.0);
-    for (int f = 0; f < nf; ++f) pairs[2 * f] = tau[f];
-    const double *dt = nullptr;
-    WT_TRY(batch_table(b, nf, pairs.data(), &dt));
-    ProfScope ps(b->ctx, "wt_batch_mrs_kernel");
-    hipLaunchKernelGGL(wt_batch_mrs_kernel, dim3(batch_flat_blocks(b, nf), nf), dim3(256), 0, b->ctx->stream, c, m, b->fstride / 4, dt, soft, persistent,
-                       inv_pow);
-    WT_HIP(hipGetLastError());
-    return 0;
+    return batch_mrs_update(b, nf, plane, mrs_plane, tau, "wt_batch_mrs_update", [&](float *c, float *m, const double *dt) {
+        const int64_t f4 = b->fstride / 4;
+        ProfScope ps(b->ctx, "wt_batch_mrs_kernel");
+        hipLaunchKernelGGL(wt_batch_mrs_kernel, dim3(batch_frame_blocks(f4, nf), nf), dim3(256), 0, b->ctx->stream, c, m, f4, dt, soft, persistent, inv_pow);
+    });
 }
 
 // ---- the circular products of richardson_lucy(fft=True) through the FFT (wt_fft.h; watroo/utils.py:245-254, 284)

@@ -20,14 +20,18 @@
 // correlation, one support plane per scale): the PSF correlation of all frames is ONE launch of the tiled kernel
 // (wt_batch64_filter2d_kernel: wt_rl_point.h's 64 x 16 tile staged in LDS as doubles, the two operands resident in
 // the batch), the binary ops run once over the frames as a flat range, the support update has the frame as grid y.
+// What lives where: this file has the float64 kernels and launch lines, the median select, the widening upload and
+// the shape rules of the float64 schedules.  The host side both engines share is wt_batch_core.h and wt_batch_rl.h
+// (see wt_batch.hip); what this engine does differently there stays here, in the open: richardson_lucy's planes become
+// planes of the batch at the first wt_batch64_set_psf, and wt_batch64_binary renumbers the op for wt64_binary_point.
+// The three threshold sums are shells around one body in the float64 arithmetic (wt_batch64_threshold_sum).
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
-#include "wt_batch_core.h"
+#include "wt_batch_rl.h"
 #include "wt_math64.h"
 #include "wt_reduce.h"
-#include "wt_rl_point.h"
 #include "wt_wow64.h"
 #include "wt_unit_probe.h"
 
@@ -39,23 +43,16 @@ struct WtBatch64Sel {               // select state of one rank of one frame
     uint32_t failed, pad;           // failed: the rank lies beyond the frame's keys (never, with every key counted)
 };
 
-struct wt_batch64 : WtBatchCore<double> {
-    wt_batch64() : WtBatchCore<double>("wt_batch64") {}
+// (richardson_lucy's planes and PSFs: wt_batch_rl.h.  The planes belong to a batch from its first wt_batch64_set_psf
+//  on: a batch without a PSF keeps the plane list every other stack function sees.)
+struct wt_batch64 : WtBatchRl<double> {
+    wt_batch64() : WtBatchRl<double>("wt_batch64") {}
     wt_plan64 geo;                  // ONE frame's geometry, context and taps: what the fused launches read (no planes)
     void *istage = nullptr;         // frames of another element type on their way into a plane
     size_t istage_cap = 0;
     uint32_t *d_hist = nullptr;     // [n][2 ranks][WT_HIST_BINS] (allocated by the first median)
     WtBatch64Sel *d_sel = nullptr;  // [n][2 ranks]
     WtBatch64Sel *h_sel = nullptr;  // pinned copy
-    // richardson_lucy: WT_PLANE_SCRATCH(6 .. 10) = data, psi, phi, residual, correlation; WT_PLANE_SCRATCH(16 + s) = the
-    // support plane of scale s (utils.richardson_lucy's plane ids); the forward / backward PSF of wt_batch64_set_psf.
-    // The planes belong to a batch from its first wt_batch64_set_psf on (extra_plane): a batch without a PSF keeps
-    // the plane list every other stack function sees.
-    double *rl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    std::vector<double *> mrs;      // max_level entries
-    double *d_psf[2] = {nullptr, nullptr};
-    size_t psf_cap[2] = {0, 0};
-    int psf_kh[2] = {0, 0}, psf_kw[2] = {0, 0};
     // (d_tau: [n][3 * WT_MAX_SUM_PLANES], the thresholds of wt_batch64_denoise_sum, then 1 / tau; wt_batch64_enhance_sum: then the weights)
 };
 
@@ -135,104 +132,51 @@ __global__ __launch_bounds__(256) void wt_batch64_select_kernel(uint32_t *hist, 
     for (int i = 0; i < per; ++i) h[threadIdx.x * per + i] = 0;
 }
 
-// wt64_denoise_sum_kernel (wt_kernels_f64.h) with one threshold row per frame: tab[frame * 2 * n_den + k] = tau,
-// tab[frame * 2 * n_den + n_den + k] = 1 / tau (the host's IEEE division, as wt64_denoise_sum), the frame from the
-// flat index.  Same expressions and accesses (no noise plane): the bits of the per-frame call.
+// wt64_denoise_sum_kernel (wt_kernels_f64.h) over the frames as one flat range, the frame from the flat index and its
+// row of the table: ft[k] = tau, ft[n_den + k] = 1 / tau (the host's IEEE division, as wt64_denoise_sum).  Same
+// expressions and accesses: the bits of the per-frame call.
+//   MAP     rows of 2 * n_den + 1, ft[2 * n_den] = 1.0 for a frame with a per-pixel noise map (Coefficients.significance
+//           with an ndarray noise, watroo/wavelets.py:133-141): such a frame thresholds at tau * nz by the quotient
+//           (wt_sig64), as the per-frame kernel does with a noise plane; a frame whose noise is a scalar keeps the
+//           reciprocal form of the map-free kernel (wt_sig64_inv) - the two differ by a rounding, so each frame takes
+//           the form its per-frame call takes
+//   ROW_WGT rows of 3 * n_den, ft[2 * n_den + k] = the frame's weight (utils.enhance per channel,
+//           watroo/utils.py:60-78); else a.wgt[k]
 struct Batch64DenoiseArgs {
     double *p[WT_MAX_SUM_PLANES];
     double wgt[WT_MAX_SUM_PLANES];
     int n, n_den, soft, write_back;
 };
+struct Batch64EnhanceArgs {
+    double *p[WT_MAX_SUM_PLANES];
+    int n, n_den, soft, write_back;
+};
 typedef double wt_b64_ntd2 __attribute__((ext_vector_type(2)));
-__global__ __launch_bounds__(256) void wt_batch64_denoise_sum_kernel(Batch64DenoiseArgs a, const double *tab, double *dst, int64_t n2, int64_t f2)
+template <bool MAP, bool ROW_WGT, typename Args>
+__device__ __forceinline__ void wt_batch64_threshold_sum(const Args &a, const double *tab, const double *noise, double *dst, int64_t n2, int64_t f2)
 {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (int64_t)gridDim.x * 256) {
-        const double *ft = tab + (i / f2) * 2 * a.n_den;
-        double2 acc = make_double2(0.0, 0.0);
-        for (int k = 0; k < a.n; ++k) {
-            const wt_b64_ntd2 raw = __builtin_nontemporal_load(reinterpret_cast<const wt_b64_ntd2 *>(a.p[k]) + i);   // (read exactly once)
-            double2 v = make_double2(raw.x, raw.y);
-            if (k < a.n_den) {
-                const double tau = ft[k], inv_tau = ft[a.n_den + k];
-                double2 sg = make_double2(1.0, 1.0);
-                if (tau > 0.0) sg = make_double2(wt_sig64_inv(v.x, tau, inv_tau, a.soft), wt_sig64_inv(v.y, tau, inv_tau, a.soft));
-                v = make_double2(v.x * (a.wgt[k] * sg.x), v.y * (a.wgt[k] * sg.y));
-                if (a.write_back) reinterpret_cast<double2 *>(a.p[k])[i] = v;
-            }
-            acc = k == 0 ? v : make_double2(acc.x + v.x, acc.y + v.y);
+        const double *ft = tab + (ROW_WGT ? (i / f2) * 3 * a.n_den : MAP ? (i / f2) * (2 * a.n_den + 1) : (i / f2) * 2 * a.n_den);
+        bool mapped = false;
+        double2 nz = make_double2(1.0, 1.0);
+        if constexpr (MAP) {
+            mapped = ft[2 * a.n_den] != 0.0;
+            nz = reinterpret_cast<const double2 *>(noise)[i];
         }
-        __builtin_nontemporal_store((wt_b64_ntd2){acc.x, acc.y}, reinterpret_cast<wt_b64_ntd2 *>(dst) + i);
-    }
-}
-
-// wt_batch64_denoise_sum_kernel with a per-pixel noise map (Coefficients.significance with an ndarray noise,
-// watroo/wavelets.py:133-141), the batched twin of wt64_denoise_sum_kernel with its `noise` operand: a frame with a map
-// thresholds at tau * nz by the quotient (wt_sig64), as the per-frame kernel does with a noise plane; a frame whose
-// noise is a scalar (tab[frame * row + 2 * n_den] == 0: no map) keeps the reciprocal form of the map-free kernel
-// (wt_sig64_inv) - the two differ by a rounding, so each frame takes the form its per-frame call takes.
-// tab[frame * row + k] = tau, [+ n_den + k] = 1 / tau, [+ 2 * n_den] = 1.0 for a frame with a map; row = 2 * n_den + 1.
-__global__ __launch_bounds__(256) void wt_batch64_denoise_sum_map_kernel(Batch64DenoiseArgs a, const double *tab, const double *noise, double *dst,
-                                                                         int64_t n2, int64_t f2)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (int64_t)gridDim.x * 256) {
-        const double *ft = tab + (i / f2) * (2 * a.n_den + 1);
-        const bool mapped = ft[2 * a.n_den] != 0.0;
-        const double2 nz = reinterpret_cast<const double2 *>(noise)[i];
         double2 acc = make_double2(0.0, 0.0);
         for (int k = 0; k < a.n; ++k) {
             const wt_b64_ntd2 raw = __builtin_nontemporal_load(reinterpret_cast<const wt_b64_ntd2 *>(a.p[k]) + i);   // (read exactly once)
             double2 v = make_double2(raw.x, raw.y);
             if (k < a.n_den) {
                 const double tau = ft[k], inv_tau = ft[a.n_den + k];
+                double wgt;
+                if constexpr (ROW_WGT) wgt = ft[2 * a.n_den + k];
+                else wgt = a.wgt[k];
                 double2 sg = make_double2(1.0, 1.0);
                 if (tau > 0.0) {
                     if (mapped) sg = make_double2(wt_sig64(v.x, tau * nz.x, a.soft), wt_sig64(v.y, tau * nz.y, a.soft));
                     else sg = make_double2(wt_sig64_inv(v.x, tau, inv_tau, a.soft), wt_sig64_inv(v.y, tau, inv_tau, a.soft));
                 }
-                v = make_double2(v.x * (a.wgt[k] * sg.x), v.y * (a.wgt[k] * sg.y));
-                if (a.write_back) reinterpret_cast<double2 *>(a.p[k])[i] = v;
-            }
-            acc = k == 0 ? v : make_double2(acc.x + v.x, acc.y + v.y);
-        }
-        __builtin_nontemporal_store((wt_b64_ntd2){acc.x, acc.y}, reinterpret_cast<wt_b64_ntd2 *>(dst) + i);
-    }
-}
-
-// plane <- value over the active frames, pitch padding included (the noise plane before the maps go up: no lane
-// computes on what hipMalloc left there)
-__global__ __launch_bounds__(256) void wt_batch64_fill_kernel(double *d, int64_t n2, double value)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (int64_t)gridDim.x * 256)
-        reinterpret_cast<double2 *>(d)[i] = make_double2(value, value);
-}
-
-// frame 0 of a plane -> frames 1 .. gridDim.y (a noise map shared by the frames of a chunk crosses PCIe once)
-__global__ __launch_bounds__(256) void wt_batch64_replicate_kernel(double *d, int64_t f2)
-{
-    const double2 *src = reinterpret_cast<const double2 *>(d);
-    double2 *dst = reinterpret_cast<double2 *>(d) + (int64_t)(blockIdx.y + 1) * f2;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < f2; i += (int64_t)gridDim.x * 256) dst[i] = src[i];
-}
-
-// wt_batch64_denoise_sum_kernel with one WEIGHT row per frame as well (utils.enhance per channel, watroo/utils.py:60-78):
-// tab[frame * 3 * n_den + k] = tau, [+ n_den + k] = 1 / tau (the host's IEEE division), [+ 2 * n_den + k] = the weight.
-// Same expressions and accesses: the bits of the per-frame call.
-struct Batch64EnhanceArgs {
-    double *p[WT_MAX_SUM_PLANES];
-    int n, n_den, soft, write_back;
-};
-__global__ __launch_bounds__(256) void wt_batch64_enhance_sum_kernel(Batch64EnhanceArgs a, const double *tab, double *dst, int64_t n2, int64_t f2)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (int64_t)gridDim.x * 256) {
-        const double *ft = tab + (i / f2) * 3 * a.n_den;
-        double2 acc = make_double2(0.0, 0.0);
-        for (int k = 0; k < a.n; ++k) {
-            const wt_b64_ntd2 raw = __builtin_nontemporal_load(reinterpret_cast<const wt_b64_ntd2 *>(a.p[k]) + i);   // (read exactly once)
-            double2 v = make_double2(raw.x, raw.y);
-            if (k < a.n_den) {
-                const double tau = ft[k], inv_tau = ft[a.n_den + k], wgt = ft[2 * a.n_den + k];
-                double2 sg = make_double2(1.0, 1.0);
-                if (tau > 0.0) sg = make_double2(wt_sig64_inv(v.x, tau, inv_tau, a.soft), wt_sig64_inv(v.y, tau, inv_tau, a.soft));
                 v = make_double2(v.x * (wgt * sg.x), v.y * (wgt * sg.y));
                 if (a.write_back) reinterpret_cast<double2 *>(a.p[k])[i] = v;
             }
@@ -240,6 +184,30 @@ __global__ __launch_bounds__(256) void wt_batch64_enhance_sum_kernel(Batch64Enha
         }
         __builtin_nontemporal_store((wt_b64_ntd2){acc.x, acc.y}, reinterpret_cast<wt_b64_ntd2 *>(dst) + i);
     }
+}
+__global__ __launch_bounds__(256) void wt_batch64_denoise_sum_kernel(Batch64DenoiseArgs a, const double *tab, double *dst, int64_t n2, int64_t f2)
+{
+    wt_batch64_threshold_sum<false, false>(a, tab, nullptr, dst, n2, f2);
+}
+__global__ __launch_bounds__(256) void wt_batch64_denoise_sum_map_kernel(Batch64DenoiseArgs a, const double *tab, const double *noise, double *dst,
+                                                                         int64_t n2, int64_t f2)
+{
+    wt_batch64_threshold_sum<true, false>(a, tab, noise, dst, n2, f2);
+}
+__global__ __launch_bounds__(256) void wt_batch64_enhance_sum_kernel(Batch64EnhanceArgs a, const double *tab, double *dst, int64_t n2, int64_t f2)
+{
+    wt_batch64_threshold_sum<false, true>(a, tab, nullptr, dst, n2, f2);
+}
+
+// plane <- value over the active frames, pitch padding included (the noise plane before the maps go up: no lane
+// computes on what hipMalloc left there); frame 0 of a plane -> frames 1 .. gridDim.y
+__global__ __launch_bounds__(256) void wt_batch64_fill_kernel(double *d, int64_t n2, double value)
+{
+    batch_fill_groups(reinterpret_cast<double2 *>(d), n2, make_double2(value, value), 256u);
+}
+__global__ __launch_bounds__(256) void wt_batch64_replicate_kernel(double *d, int64_t f2)
+{
+    batch_replicate_groups(reinterpret_cast<double2 *>(d), f2, 256u);
 }
 
 // generalized_anscombe (watroo/wavelets.py:14-21) over the frames as one tall image: wt64_anscombe_kernel's expressions
@@ -342,8 +310,7 @@ __global__ __launch_bounds__(256) void wt_batch64_plane_sum_kernel(Sum64Args a, 
     wt64_plane_sum_groups(a, dst, n2);
 }
 
-// wt64_filter2d_kernel (wt_kernels_f64.h) for the frames of a batch, tiled: grid z = the frame, each its own image
-// (the border rules act at the frame's borders).  Staging, tile geometry and tap loop are wt_rl_point.h's with
+// wt64_filter2d_kernel (wt_kernels_f64.h) for the frames of a batch, tiled: wt_f2d_batch_tile (wt_rl_point.h) with
 // T = double - the (64 + kw - 1) x (16 + kh - 1) window of a 64 x 16 output tile in dynamic LDS, four output rows per
 // thread, taps as wave-uniform loads from the batch's device copy.  Every output is the chain
 // acc = fma(psf[i * kw + j], v, acc) from 0.0, i outer, j inner, over the same samples (wt_refl / a true modulo
@@ -353,22 +320,7 @@ __global__ __launch_bounds__(256) void wt_batch64_filter2d_kernel(const double *
                                                                   const double *__restrict__ psf, int kh, int kw, int ay, int ax)
 {
     extern __shared__ double tile64[];
-    in += (int64_t)blockIdx.z * fstride;
-    out += (int64_t)blockIdx.z * fstride;
-    const int tw = WT_F2D_TW + kw - 1, th = WT_F2D_TH + kh - 1;
-    const int x0 = blockIdx.x * WT_F2D_TW, ly0 = blockIdx.y * WT_F2D_TH;
-    wt_f2d_stage<WRAP>(tile64, in, g, x0, ly0, tw, th, ay, ax);
-    __syncthreads();
-    const int x = x0 + threadIdx.x;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    wt_f2d_taps(tile64, tw, psf, kw, kh, kw, acc);
-    if (x < g.W) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int ly = ly0 + threadIdx.y * 4 + r;
-            if (ly < g.H) out[(int64_t)ly * g.P + x] = acc[r];
-        }
-    }
+    wt_f2d_batch_tile<WRAP, false>(tile64, in, out, g, fstride, psf, kh, kw, ay, ax);
 }
 
 // wt64_binary_kernel (wt_kernels_f64.h) over the active frames, one flat range of 16-byte groups (wt64_binary_point;
@@ -400,15 +352,6 @@ __global__ __launch_bounds__(256) void wt_batch64_mrs_kernel(double *c, double *
 }
 
 // ------------------------------------------------------------------------------------------------ host
-// richardson_lucy's planes (WtBatchCore::extra_plane, set by the first wt_batch64_set_psf)
-static double **batch64_rl_plane(WtBatchCore<double> *core, int id)
-{
-    wt_batch64 *b = static_cast<wt_batch64 *>(core);
-    if (id <= WT_PLANE_SCRATCH(6) && id >= WT_PLANE_SCRATCH(10)) return &b->rl[WT_PLANE_SCRATCH(6) - id];
-    if (id <= WT_PLANE_SCRATCH(16) && id > WT_PLANE_SCRATCH(16) - (int)b->mrs.size()) return &b->mrs[WT_PLANE_SCRATCH(16) - id];
-    return nullptr;
-}
-
 // fused64_ok (wt_f64.h) for one frame of this shape: an image (H >= 2) whose rows the fused passes take at 8 bytes
 // per pixel and whose float64 schedule of `level` scales is fused passes only
 static bool batch64_all_fused(int family, int64_t H, int64_t W, int level, int32_t *tr, int *np)
@@ -504,10 +447,7 @@ static void batch64_free(wt_batch64 *b, int *bad)
     f(b->istage);
     f(b->d_hist);
     f(b->d_sel);
-    for (double *q : b->rl) f(q);
-    for (double *q : b->mrs) f(q);
-    f(b->d_psf[0]);
-    f(b->d_psf[1]);
+    batch_rl_release(b, bad);
     if (b->h_sel && hipHostFree(b->h_sel) != hipSuccess) *bad = 1;
 }
 
@@ -519,7 +459,6 @@ extern "C" int wt_batch64_create(wt_ctx *ctx, int n, int H, int W, int family, i
     if (!wt_fused_supported_bytes((int64_t)(W + 1) / 2 * 2 * 8)) WT_FAIL("wt_batch64_create: rows of %d pixels are too wide for the fused float64 passes", W);
     wt_batch64 *b = new wt_batch64;
     batch_init(b, ctx, n, H, W, (W + 1) / 2 * 2, family, max_level);
-    b->mrs.assign(std::min(max_level, WT_NUM_SCRATCH - 16), nullptr);
     // the geometry and taps a wt_plan64 of this shape has (wt64_plan_create)
     static const double b3[5] = {1. / 16, 1. / 4, 3. / 8, 1. / 4, 1. / 16}, tri[3] = {1. / 4, 1. / 2, 1. / 4};
     b->geo.ctx = ctx;
@@ -763,22 +702,16 @@ extern "C" int wt_batch64_abs_median(wt_batch64 *b, int nf, int plane, double *m
     return 0;
 }
 
-// What the threshold sums share once their arguments hold: the drain before d_tau is rewritten (the table goes up
-// stream-ordered from pinned staging, and the previous call's kernel may still read it), then tau and 1 / tau (the
-// host's IEEE division: wt64_denoise_sum's inv_tau) of every active frame at the head of its `row` of the staging table.
-static int batch64_tau_rows(wt_batch64 *b, int nf, int n_den, int row, const double *tau)
+// the head of a frame's row of the threshold table: tau, then 1 / tau (the host's IEEE division: wt64_denoise_sum's inv_tau)
+static void batch64_tau_row(double *r, const double *tau, int n_den)
 {
-    WT_HIP(hipStreamSynchronize(b->ctx->stream));
-    for (int f = 0; f < nf; ++f)
-        for (int k = 0; k < n_den; ++k) {
-            const double t = tau[f * n_den + k];
-            b->h_tau[f * row + k] = t;
-            b->h_tau[f * row + n_den + k] = t > 0.0 ? 1.0 / t : 0.0;
-        }
-    return 0;
+    for (int k = 0; k < n_den; ++k) {
+        r[k] = tau[k];
+        r[n_den + k] = tau[k] > 0.0 ? 1.0 / tau[k] : 0.0;
+    }
 }
 
-// x blocks of the flat kernels over n2 16-byte groups
+// x blocks of the flat kernels over n2 16-byte groups (not wt_host.h's flat_grid: that one stops at 2048 blocks)
 static dim3 batch64_flat_grid(int64_t n2)
 {
     return dim3((unsigned)std::min<int64_t>((n2 + 255) / 256, 256 * 16 * 8));
@@ -794,22 +727,18 @@ static int batch64_denoise_sum(wt_batch64 *b, int nf, int count, int dst, int n_
     if (map && noise_plane == WT_PLANE_NONE) WT_FAIL("%s: no noise plane (wt_batch64_denoise_sum is the call without a map)", who);
     if (map && (noise_plane == dst || (noise_plane >= 0 && noise_plane < count))) WT_FAIL("%s: the noise plane %d is a plane of the sum", who, noise_plane);
     Batch64DenoiseArgs a{};
-    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
-    for (int i = 0; i < count; ++i) {
-        WT_TRY(batch_plane(b, i, &a.p[i]));
-        a.wgt[i] = i < n_den ? wgt[i] : 1.0;
-    }
     double *o = nullptr, *nz = nullptr;
-    WT_TRY(batch_plane(b, dst, &o));
+    WT_TRY(batch_sum_args(b, count, dst, n_den, soft, write_back, &a, &o));
+    for (int i = 0; i < count; ++i) a.wgt[i] = i < n_den ? wgt[i] : 1.0;
     if (map) WT_TRY(batch_plane(b, noise_plane, &nz));
-    // rows of {tau, 1 / tau}; with a map: then 1.0 for a frame that has one (nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables)
+    // rows of {tau, 1 / tau} (two 0.0 when no plane is thresholded); with a map: then 1.0 for a frame that has one
+    // (nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables)
     const int row = map ? 2 * n_den + 1 : 2 * std::max(n_den, 1);
-    WT_TRY(batch64_tau_rows(b, nf, n_den, row, tau));
-    if (map)
-        for (int f = 0; f < nf; ++f) b->h_tau[f * row + 2 * n_den] = (!has_map || has_map[f]) ? 1.0 : 0.0;
-    else if (n_den == 0)
-        for (int i = 0; i < nf * row; ++i) b->h_tau[i] = 0.0;
-    WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * row * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    WT_TRY(batch_sum_table(b, nf, row, [&](int f, double *r) {
+        batch64_tau_row(r, tau + f * n_den, n_den);
+        if (map) r[2 * n_den] = (!has_map || has_map[f]) ? 1.0 : 0.0;
+        else if (n_den == 0) r[0] = r[1] = 0.0;
+    }));
     const int64_t n2 = (int64_t)nf * b->fstride / 2;
     if (map) {
         ProfScope ps(b->ctx, "wt_batch64_denoise_sum_map_kernel");
@@ -838,30 +767,20 @@ extern "C" int wt_batch64_denoise_sum_map(wt_batch64 *b, int nf, int count, int 
 
 extern "C" int wt_batch64_fill(wt_batch64 *b, int nf, int plane, double value)
 {
-    WT_TRY(batch_check_frames(b, nf, "wt_batch64_fill"));
-    WtGuard guard_(b->ctx);
-    double *d = nullptr;
-    WT_TRY(batch_plane(b, plane, &d));
-    const int64_t n2 = (int64_t)nf * b->fstride / 2;
-    ProfScope ps(b->ctx, "wt_batch64_fill_kernel");
-    hipLaunchKernelGGL(wt_batch64_fill_kernel, batch64_flat_grid(n2), dim3(256), 0, b->ctx->stream, d, n2, value);
-    WT_HIP(hipGetLastError());
-    return 0;
+    return batch_fill(b, nf, plane, "wt_batch64_fill", [&](double *d) {
+        const int64_t n2 = (int64_t)nf * b->fstride / 2;
+        ProfScope ps(b->ctx, "wt_batch64_fill_kernel");
+        hipLaunchKernelGGL(wt_batch64_fill_kernel, batch64_flat_grid(n2), dim3(256), 0, b->ctx->stream, d, n2, value);
+    });
 }
 
 extern "C" int wt_batch64_replicate(wt_batch64 *b, int nf, int plane)
 {
-    WT_TRY(batch_check_frames(b, nf, "wt_batch64_replicate"));
-    WtGuard guard_(b->ctx);
-    double *d = nullptr;
-    WT_TRY(batch_plane(b, plane, &d));
-    if (nf == 1) return 0;
-    const int64_t f2 = b->fstride / 2;
-    const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((f2 + 255) / 256, (2048 + nf - 1) / nf));
-    ProfScope ps(b->ctx, "wt_batch64_replicate_kernel");
-    hipLaunchKernelGGL(wt_batch64_replicate_kernel, dim3(bx, nf - 1), dim3(256), 0, b->ctx->stream, d, f2);
-    WT_HIP(hipGetLastError());
-    return 0;
+    return batch_replicate(b, nf, plane, "wt_batch64_replicate", [&](double *d) {
+        const int64_t f2 = b->fstride / 2;
+        ProfScope ps(b->ctx, "wt_batch64_replicate_kernel");
+        hipLaunchKernelGGL(wt_batch64_replicate_kernel, dim3(batch_frame_blocks(f2, nf), nf - 1), dim3(256), 0, b->ctx->stream, d, f2);
+    });
 }
 
 extern "C" int wt_batch64_enhance_sum(wt_batch64 *b, int nf, int count, int dst, int n_den, const double *tau, const double *wgt, int soft,
@@ -871,15 +790,13 @@ extern "C" int wt_batch64_enhance_sum(wt_batch64 *b, int nf, int count, int dst,
     WtGuard guard_(b->ctx);
     WT_TRY(batch_check_sum(b, count, dst, n_den, 1, tau, wgt, "wt_batch64_enhance_sum"));
     Batch64EnhanceArgs a{};
-    a.n = count; a.n_den = n_den; a.soft = soft; a.write_back = write_back;
-    for (int i = 0; i < count; ++i) WT_TRY(batch_plane(b, i, &a.p[i]));
     double *o = nullptr;
-    WT_TRY(batch_plane(b, dst, &o));
-    const int row = 3 * n_den;                              // nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables
-    WT_TRY(batch64_tau_rows(b, nf, n_den, row, tau));
-    for (int f = 0; f < nf; ++f)
-        for (int k = 0; k < n_den; ++k) b->h_tau[f * row + 2 * n_den + k] = wgt[f * n_den + k];
-    WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * row * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    WT_TRY(batch_sum_args(b, count, dst, n_den, soft, write_back, &a, &o));
+    // rows of {tau, 1 / tau, the weights} (nf <= n, n_den <= WT_MAX_SUM_PLANES: within the tables)
+    WT_TRY(batch_sum_table(b, nf, 3 * n_den, [&](int f, double *r) {
+        batch64_tau_row(r, tau + f * n_den, n_den);
+        for (int k = 0; k < n_den; ++k) r[2 * n_den + k] = wgt[f * n_den + k];
+    }));
     const int64_t n2 = (int64_t)nf * b->fstride / 2;
     ProfScope ps(b->ctx, "wt_batch64_enhance_sum_kernel");
     hipLaunchKernelGGL(wt_batch64_enhance_sum_kernel, batch64_flat_grid(n2), dim3(256), 0, b->ctx->stream, a, (const double *)b->d_tau, o, n2,
@@ -1024,118 +941,42 @@ extern "C" int wt_batch64_plane_sum(wt_batch64 *b, int nf, int first, int count,
 }
 
 // ------------------------------------------------------------------------------------------------ richardson_lucy
-// host logic: *ok = 1 when wt_batch64_set_psf takes a kh x kw PSF - wt_batch64_filter2d applies it in ONE launch
+// (wt_batch_rl.h with T = double: the LDS tile holds doubles, so fewer PSFs go in one launch than in float32)
 extern "C" int wt_batch64_psf_ok(int kh, int kw, int *ok)
 {
-    if (!ok) WT_FAIL("wt_batch64_psf_ok: null pointer");
-    *ok = wt64_f2d_single_launch(kh, kw) ? 1 : 0;
-    return 0;
+    return batch_psf_ok<double>(kh, kw, ok, "wt_batch64_psf_ok");
 }
 
-// One of the two PSF operands of a richardson_lucy call (slot 0: forward, watroo/utils.py:257; slot 1: backward,
-// utils.py:286) -> device memory of the batch, once per call: the iterations then correlate without a stream drain
-// and without a PSF copy (wt64_filter2d does both on every call - its kernel comes from caller-owned memory).
 // The first PSF makes richardson_lucy's planes planes of this batch.
 extern "C" int wt_batch64_set_psf(wt_batch64 *b, int slot, const double *kernel, int kh, int kw)
 {
-    if (!b || !kernel) WT_FAIL("wt_batch64_set_psf: null pointer");
-    WtGuard guard_(b->ctx);
-    if (slot < 0 || slot > 1) WT_FAIL("wt_batch64_set_psf: slot %d (0: forward, 1: backward)", slot);
-    if (!wt64_f2d_single_launch(kh, kw))
-        WT_FAIL("wt_batch64_set_psf: a %d x %d PSF is not applied in one launch (at most %d taps, rows of at most %d, an LDS tile of at most %d KB)",
-                kh, kw, WT_F2D_MAX_TAPS, WT_F2D_MAX_KW, WT_F2D_MAX_LDS / 1024);
-    const size_t ntaps = (size_t)kh * kw;
-    // a launch on the stream may still read the slot, and `kernel` is the caller's: drain, then copy synchronously
-    WT_HIP(hipStreamSynchronize(b->ctx->stream));
-    if (ntaps > b->psf_cap[slot]) {
-        (void)hipFree(b->d_psf[slot]);
-        b->d_psf[slot] = nullptr;
-        b->psf_cap[slot] = 0;
-        b->psf_kh[slot] = b->psf_kw[slot] = 0;
-        WT_HIP(hipMalloc((void **)&b->d_psf[slot], ntaps * sizeof(double)));
-        b->psf_cap[slot] = ntaps;
-    }
-    WT_HIP(hipMemcpy(b->d_psf[slot], kernel, ntaps * sizeof(double), hipMemcpyHostToDevice));
-    b->psf_kh[slot] = kh;
-    b->psf_kw[slot] = kw;
-    if (!b->extra_plane) {
-        b->extra_plane = batch64_rl_plane;
-        b->extra_planes = ", 6..10, 16.." + std::to_string(15 + (int)b->mrs.size());
-    }
+    WT_TRY(batch_set_psf(b, slot, kernel, kh, kw, "wt_batch64_set_psf"));
+    batch_rl_own_planes(b);
     return 0;
 }
 
-// wt64_filter2d per frame (watroo/utils.py:257,286; periodic: the circular products of utils.py:245-254,284) with
-// the PSF of `slot`: one launch of the tiled kernel for all active frames
 extern "C" int wt_batch64_filter2d(wt_batch64 *b, int nf, int src, int dst, int slot, int ay, int ax, int border)
 {
-    WT_TRY(batch_check_frames(b, nf, "wt_batch64_filter2d"));
-    WtGuard guard_(b->ctx);
-    if (slot < 0 || slot > 1 || !b->d_psf[slot] || !b->psf_kh[slot]) WT_FAIL("wt_batch64_filter2d: PSF slot %d is not set (wt_batch64_set_psf)", slot);
-    const int kh = b->psf_kh[slot], kw = b->psf_kw[slot];
-    if (!wt64_f2d_single_launch(kh, kw)) WT_FAIL("wt_batch64_filter2d: a %d x %d PSF is not applied in one launch", kh, kw);
-    if (ay < 0 || ay >= kh || ax < 0 || ax >= kw) WT_FAIL("wt_batch64_filter2d: anchor (%d, %d) outside the %d x %d kernel", ay, ax, kh, kw);
-    if (src == dst) WT_FAIL("wt_batch64_filter2d: src and dst must differ");
-    if (border != WT_BORDER_SYMMETRIC && border != WT_BORDER_PERIODIC) WT_FAIL("wt_batch64_filter2d: border %d unsupported (symmetric or periodic)", border);
-    const Geo &g = b->geo.g;
-    dim3 grid((g.W + WT_F2D_TW - 1) / WT_F2D_TW, (g.H + WT_F2D_TH - 1) / WT_F2D_TH, nf), block(64, 4);
-    if (grid.y > 65535u) WT_FAIL("wt_batch64_filter2d: frames of %d rows are too tall (%u row tiles, at most 65535)", g.H, grid.y);
-    if (grid.z > 65535u) WT_FAIL("wt_batch64_filter2d: %d frames in one launch (at most 65535)", nf);
-    double *in = nullptr, *o = nullptr;
-    WT_TRY(batch_plane(b, src, &in));
-    WT_TRY(batch_plane(b, dst, &o));
-    const size_t lds = wt_f2d_lds_bytes(kh, kw, sizeof(double));
-    ProfScope ps(b->ctx, "wt_batch64_filter2d_kernel");
-    #define WT_B64F2D_LAUNCH(WRAP)                                                                                                   \
-        do {                                                                                                                         \
-            if (lds > 64 * 1024)                                                                                                     \
-                WT_HIP(hipFuncSetAttribute((const void *)wt_batch64_filter2d_kernel<WRAP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL((wt_batch64_filter2d_kernel<WRAP>), grid, block, lds, b->ctx->stream, (const double *)in, o, g, b->fstride, \
-                               (const double *)b->d_psf[slot], kh, kw, ay, ax);                                                      \
-        } while (0)
-    if (border == WT_BORDER_PERIODIC) WT_B64F2D_LAUNCH(true);
-    else WT_B64F2D_LAUNCH(false);
-    #undef WT_B64F2D_LAUNCH
-    WT_HIP(hipGetLastError());
-    return 0;
+    return batch_filter2d(b, nf, src, dst, slot, ay, ax, border, "wt_batch64_filter2d", "wt_batch64_filter2d_kernel",
+                          [](bool periodic) { return periodic ? wt_batch64_filter2d_kernel<true> : wt_batch64_filter2d_kernel<false>; });
 }
 
-// wt64_binary over the active frames (watroo/utils.py:259,280-281,288); op: wt_batch_binary's numbering (WT_OP_*)
+// op: wt_batch_binary's numbering (WT_OP_*); wt64_binary_point counts add, sub, ...
 extern "C" int wt_batch64_binary(wt_batch64 *b, int nf, int op, int a, int b2, int dst)
 {
-    WT_TRY(batch_check_frames(b, nf, "wt_batch64_binary"));
-    WtGuard guard_(b->ctx);
-    if (op < 0 || op > WT_OP_ADD_DIV) WT_FAIL("wt_batch64_binary: unknown op %d", op);
-    double *pa = nullptr, *pb = nullptr, *pd = nullptr;
-    WT_TRY(batch_plane(b, a, &pa));
-    WT_TRY(batch_plane(b, b2, &pb));
-    WT_TRY(batch_plane(b, dst, &pd));
-    const int op64 = op == WT_OP_SUB ? 1 : op == WT_OP_ADD ? 0 : op;      // (wt64_binary counts add, sub, ...)
-    const int64_t n2 = (int64_t)nf * b->fstride / 2;
-    ProfScope ps(b->ctx, "wt_batch64_binary_kernel");
-    hipLaunchKernelGGL(wt_batch64_binary_kernel, batch64_flat_grid(n2), dim3(256), 0, b->ctx->stream, (const double *)pa, (const double *)pb, pd, n2, op64);
-    WT_HIP(hipGetLastError());
-    return 0;
+    return batch_binary(b, nf, op, a, b2, dst, "wt_batch64_binary", [&](const double *pa, const double *pb, double *pd) {
+        const int op64 = op == WT_OP_SUB ? 1 : op == WT_OP_ADD ? 0 : op;
+        const int64_t n2 = (int64_t)nf * b->fstride / 2;
+        ProfScope ps(b->ctx, "wt_batch64_binary_kernel");
+        hipLaunchKernelGGL(wt_batch64_binary_kernel, batch64_flat_grid(n2), dim3(256), 0, b->ctx->stream, pa, pb, pd, n2, op64);
+    });
 }
 
-// wt64_mrs_update per frame (watroo/utils.py:263-276) with the frame's tau[f]; scalar noise only
 extern "C" int wt_batch64_mrs_update(wt_batch64 *b, int nf, int plane, int mrs_plane, const double *tau, int soft, int persistent, double inv_pow)
 {
-    WT_TRY(batch_check_frames(b, nf, "wt_batch64_mrs_update"));
-    WtGuard guard_(b->ctx);
-    if (!tau) WT_FAIL("wt_batch64_mrs_update: null tau");
-    if (plane == mrs_plane) WT_FAIL("wt_batch64_mrs_update: plane and mrs_plane must differ");
-    double *c = nullptr, *m = nullptr;
-    WT_TRY(batch_plane(b, plane, &c));
-    WT_TRY(batch_plane(b, mrs_plane, &m));
-    std::vector<double> pairs((size_t)nf * 2, 0.0);
-    for (int f = 0; f < nf; ++f) pairs[2 * f] = tau[f];
-    const double *dt = nullptr;
-    WT_TRY(batch_table(b, nf, pairs.data(), &dt));
-    const int64_t f2 = b->fstride / 2;
-    const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((f2 + 255) / 256, (2048 + nf - 1) / nf));
-    ProfScope ps(b->ctx, "wt_batch64_mrs_kernel");
-    hipLaunchKernelGGL(wt_batch64_mrs_kernel, dim3(bx, nf), dim3(256), 0, b->ctx->stream, c, m, f2, dt, soft, persistent, inv_pow);
-    WT_HIP(hipGetLastError());
-    return 0;
+    return batch_mrs_update(b, nf, plane, mrs_plane, tau, "wt_batch64_mrs_update", [&](double *c, double *m, const double *dt) {
+        const int64_t f2 = b->fstride / 2;
+        ProfScope ps(b->ctx, "wt_batch64_mrs_kernel");
+        hipLaunchKernelGGL(wt_batch64_mrs_kernel, dim3(batch_frame_blocks(f2, nf), nf), dim3(256), 0, b->ctx->stream, c, m, f2, dt, soft, persistent, inv_pow);
+    });
 }

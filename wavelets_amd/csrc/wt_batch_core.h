@@ -1,11 +1,14 @@
 // Host core of the two batch engines, written once over the element type: wt_batch (wt_batch.hip, float) and
 // wt_batch64 (wt_batch64.hip, double) derive from WtBatchCore<T>.  It holds what both have - the common planes and
 // their lazy allocation, the frame checks, the table ring of per-frame parameter pairs, the host <-> plane copy, the
-// schedule run and the bilateral loop, the shared argument checks, the reduce buffers, the release of every common
-// buffer.  Kernels, launch lines, the median select and each engine's own planes stay in the engine's file; where a
-// shared loop needs one of them the engine hands it in as a callable.  Every message carries the engine's prefix
-// (`name`) or the entry point's name (`who`), so the texts are the ones each engine had of its own.
-// Host only; included by the two engine files and by nothing else.
+// schedule run and the bilateral loop, the shared argument checks, the arguments and the table of the threshold sums,
+// fill and replicate, the reduce buffers, the release of every common buffer.  Kernels, launch lines and the median
+// select stay in the engine's file; where a shared function needs one of them the engine hands it in as a callable.
+// Every message carries the engine's prefix (`name`) or the entry point's name (`who`), so the texts are the ones
+// each engine had of its own.  The Richardson-Lucy half is wt_batch_rl.h, on top of this header.
+// Host code, but for the two loops of fill and replicate over 16-byte groups (batch_fill_groups,
+// batch_replicate_groups), which each engine wraps in its kernel; included by the two engine files (through
+// wt_batch_rl.h) and by nothing else.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -379,6 +382,80 @@ static int batch_check_sum(const WtBatchCore<T> *b, int count, int dst, int n_de
     if (n_den < min_den || n_den > count) WT_FAIL("%s: n_den %d outside [%d,%d]", who, n_den, min_den, count);
     if (n_den > 0 && (!tau || !wgt)) WT_FAIL("%s: null tau/wgt", who);
     if (dst >= 0 && dst < count) WT_FAIL("%s: dst plane %d is one of the summed planes", who, dst);
+    return 0;
+}
+
+// the head of a threshold sum's kernel arguments (Args: the engine's struct - p[], n, n_den, soft, write_back) with
+// planes 0 .. count - 1, then the destination plane
+template <typename T, typename Args>
+static int batch_sum_args(WtBatchCore<T> *b, int count, int dst, int n_den, int soft, int write_back, Args *a, T **o)
+{
+    a->n = count; a->n_den = n_den; a->soft = soft; a->write_back = write_back;
+    for (int i = 0; i < count; ++i) WT_TRY(batch_plane(b, i, &a->p[i]));
+    return batch_plane(b, dst, o);
+}
+
+// The per-frame rows of a threshold sum -> d_tau: fill_row(f, r) writes the `row` doubles of frame f (what a row
+// holds is the engine's; nf <= n and row <= the doubles per frame the engine allocated).  The table goes up
+// stream-ordered from pinned staging, and the previous call's kernel may still read d_tau: drain first.
+template <typename T, typename FillRow>
+static int batch_sum_table(WtBatchCore<T> *b, int nf, int row, FillRow fill_row)
+{
+    WT_HIP(hipStreamSynchronize(b->ctx->stream));
+    for (int f = 0; f < nf; ++f) fill_row(f, b->h_tau + (size_t)f * row);
+    WT_HIP(hipMemcpyAsync(b->d_tau, b->h_tau, (size_t)nf * row * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ fill, replicate
+// x blocks per frame of the batched pointwise kernels (grid y = the frame) over `groups` 16-byte groups per frame:
+// about 2048 blocks in all
+static inline unsigned batch_frame_blocks(int64_t groups, int nf)
+{
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 255) / 256, (2048 + nf - 1) / nf));
+}
+
+// V = float4 / double2: `n` 16-byte groups <- value, by blocks of `block` threads on any grid
+template <typename V>
+__device__ __forceinline__ void batch_fill_groups(V *d, int64_t n, V value, unsigned block)
+{
+    for (int64_t i = (int64_t)blockIdx.x * block + threadIdx.x; i < n; i += (int64_t)gridDim.x * block) d[i] = value;
+}
+
+// frame 0 of a plane -> frames 1 .. gridDim.y, `fg` groups apart (a noise map shared by the frames of a chunk crosses PCIe once)
+template <typename V>
+__device__ __forceinline__ void batch_replicate_groups(V *d, int64_t fg, unsigned block)
+{
+    const V *src = d;
+    V *dst = d + (int64_t)(blockIdx.y + 1) * fg;
+    for (int64_t i = (int64_t)blockIdx.x * block + threadIdx.x; i < fg; i += (int64_t)gridDim.x * block) dst[i] = src[i];
+}
+
+// plane <- value over the active frames, pitch padding included: launch(d) runs the engine's fill kernel
+template <typename T, typename Launch>
+static int batch_fill(WtBatchCore<T> *b, int nf, int plane, const char *who, Launch launch)
+{
+    WT_TRY(batch_check_frames(b, nf, who));
+    WtGuard guard_(b->ctx);
+    T *d = nullptr;
+    WT_TRY(batch_plane(b, plane, &d));
+    launch(d);
+    WT_HIP(hipGetLastError());
+    return 0;
+}
+
+// frame 0 of the plane -> the other active frames: launch(d) runs the engine's replicate kernel on a grid of
+// (batch_frame_blocks, nf - 1)
+template <typename T, typename Launch>
+static int batch_replicate(WtBatchCore<T> *b, int nf, int plane, const char *who, Launch launch)
+{
+    WT_TRY(batch_check_frames(b, nf, who));
+    WtGuard guard_(b->ctx);
+    T *d = nullptr;
+    WT_TRY(batch_plane(b, plane, &d));
+    if (nf == 1) return 0;
+    launch(d);
+    WT_HIP(hipGetLastError());
     return 0;
 }
 

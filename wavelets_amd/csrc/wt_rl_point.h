@@ -1,5 +1,6 @@
-// Richardson-Lucy support shared by the per-image kernels (wt_kernels_apps.h) and the batched ones (wt_batch.hip):
-// the PSF correlation's tile geometry, staging and border rules, and the pointwise arithmetic of the binary ops and
+// Richardson-Lucy support shared by the per-image kernels (wt_kernels_apps.h) and the batched ones (wt_batch.hip,
+// wt_batch64.hip): the PSF correlation's tile geometry, staging, border rules and the batched tile body, and the
+// pointwise arithmetic of the binary ops and
 // of the multiresolution-support update.  One text for both, so a frame of a batch gets the bits of the per-image
 // call (watroo/utils.py:222-290).
 #pragma once
@@ -28,11 +29,7 @@ static inline bool wt_f2d_single_launch(int kh, int kw, size_t elem = sizeof(flo
 {
     return kh >= 1 && kw >= 1 && kw <= WT_F2D_MAX_KW && (int64_t)kh * kw <= WT_F2D_MAX_TAPS && wt_f2d_lds_bytes(kh, kw, elem) <= WT_F2D_MAX_LDS;
 }
-// the same rule with the tile staged as doubles: the same tile geometry at twice the bytes (wt_batch64_psf_ok)
-static inline bool wt64_f2d_single_launch(int kh, int kw)
-{
-    return wt_f2d_single_launch(kh, kw, sizeof(double));
-}
+// (the float64 batch asks with elem = sizeof(double): the same tile geometry at twice the bytes, wt_batch_rl.h)
 
 // WRAP: periodic border (the circular convolution of the reference's rFFT path,
 // watroo/utils.py:245-254,284), whole-image plans only; (ay, ax) = anchor of the correlation.
@@ -103,6 +100,34 @@ __device__ __forceinline__ void wt_f2d_taps_skewed(const float *tile, int tw, co
                 for (int r = 0; r < 4; ++r)
                     if (t - r >= 0 && t - r < kh) acc[r] = fmaf(k0[j - r * kw], v, acc[r]);
             }
+        }
+    }
+}
+
+// One 64 x 16 output tile of the batched correlation (wt_batch_filter2d_kernel, wt_batch64_filter2d_kernel: block
+// (64, 4), grid z = the frame, each frame its own image - the border rules act at the frame's borders): the window
+// staged in `tile` (dynamic LDS), then per output the chain of fma from 0, i outer, j inner.  !SKEW is the per-image
+// tap loop (one LDS read per FMA); SKEW (float only) walks every staged row once for the four output rows of a
+// thread - identical bits either way.
+template <bool WRAP, bool SKEW, typename T>
+__device__ __forceinline__ void wt_f2d_batch_tile(T *tile, const T *in, T *out, const Geo &g, int64_t fstride, const T *__restrict__ psf, int kh,
+                                                  int kw, int ay, int ax)
+{
+    in += (int64_t)blockIdx.z * fstride;
+    out += (int64_t)blockIdx.z * fstride;
+    const int tw = WT_F2D_TW + kw - 1, th = WT_F2D_TH + kh - 1;
+    const int x0 = blockIdx.x * WT_F2D_TW, ly0 = blockIdx.y * WT_F2D_TH;
+    wt_f2d_stage<WRAP>(tile, in, g, x0, ly0, tw, th, ay, ax);
+    __syncthreads();
+    const int x = x0 + threadIdx.x;
+    T acc[4] = {0, 0, 0, 0};
+    if constexpr (SKEW) wt_f2d_taps_skewed(tile, tw, psf, kh, kw, acc);
+    else wt_f2d_taps(tile, tw, psf, kw, kh, kw, acc);
+    if (x < g.W) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ly = ly0 + threadIdx.y * 4 + r;
+            if (ly < g.H) out[(int64_t)ly * g.P + x] = acc[r];
         }
     }
 }
