@@ -356,6 +356,12 @@ int wt_gamma_blend(wt_plan *plan, int recon, int gamma_plane, float gmin, float 
 int wt_smooth3d(wt_plan *plan, int src, int dst, int s, int depth);
 /* atrous_standard on the cube: planes[0..level-1] <- detail, planes[level] <- smooth. */
 int wt_decompose3d(wt_plan *plan, int src, int level, int depth);
+/* The float32 cube engine: the planes of wt_decompose3d, bit for bit, with ONE launch per scale (x, y and z
+ * filters and the detail subtraction fused; a scale whose z chains are too short runs on the sequence of
+ * wt_decompose3d).  Same plane contract: planes[0..level], `src` intact, WT_PLANE_SCRATCH(0/1) as ping-pong.
+ * Built-in scaling functions, one rank and the symmetric border only: anything else is refused before any
+ * device work. */
+int wt_decompose_cube(wt_plan *plan, int src, int level, int depth);
 /* bilateral transform of cubes, one scale at a time (watroo/wavelets.py:433-440 on 3-D input):
  * wt_local_variance3d = sdev_loc(cube, variance=True) * f1 * f2 (3-D smoothing of I and I^2,
  * scratch planes 13-15); wt_bilateral3d_conv = atrous_convolution with the K^3 kernel and that

@@ -119,6 +119,7 @@ SIGNATURES = {
                                   _c.c_float]),
     "wt_smooth3d": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "wt_decompose3d": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_decompose_cube": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int]),
     "wt_local_variance3d": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float]),
     "wt_bilateral3d_conv": (_c.c_int, [_vp] + [_c.c_int] * 5),
     "wt_filter2d": (_c.c_int, [_vp, _c.c_int, _c.c_int, _fp, _c.c_int, _c.c_int, _c.c_int]),
@@ -966,6 +967,10 @@ class Plan:
 
     def decompose3d(self, src, level, depth):
         check(load().wt_decompose3d(self._h, src, level, depth))
+
+    def decompose_cube(self, src, level, depth):
+        """decompose3d's planes, bit for bit, with one launch per scale (the float32 cube engine, cubes.py)"""
+        check(load().wt_decompose_cube(self._h, src, level, depth))
 
     def filter2d(self, src, dst, kernel, flags=0, anchor=None, periodic=False):
         k = np.ascontiguousarray(kernel, dtype=np.float32)

@@ -1,0 +1,126 @@
+// One scale of the a-trous transform of a (Z, Y, X) float32 cube in ONE launch: the x, y and z filters of the 3-D
+// branch of convolution() (watroo/wavelets.py:46-64) and the detail subtraction (wavelets.py:442).  The cube is
+// stored as everywhere in the library, a (Z*Y) x X image with pitch P.  gfx950 only.
+//
+// A workgroup of 4 waves owns 256 columns (64 lanes x one float4 group, 16-byte accesses), TY = 8 rows of one
+// polyphase row class y = q_y + d (r0 + i) and a chunk of one polyphase chain along z, z = q_z + d t.  Per chain
+// step it
+//   1. x-filters the TY + 2 hw rows y + (j - hw) d of slice z + hw d into LDS (wt_hrow_filter, the row filter of
+//      every per-scale kernel; the rows go round the waves so that the wave that owns output row i is the one that
+//      filters row i + hw and keeps its centre samples, c_s, in registers),
+//   2. y-filters its two output rows from LDS,
+//   3. pushes the result into a K-deep register ring whose z-filter is c_{s+1}(z), and stores c_{s+1}(z) and
+//      w_s(z) = c_s(z) - c_{s+1}(z), c_s(z) being the centre sample that entered hw steps earlier.
+// The LDS rows are double-buffered: one barrier per step.  Reflected rows and slices (wt_refl_b under the symmetric
+// border) may lie in another residue class: they are simply filtered where they are needed; a chunk pays K - 1
+// warm-up slices.  The ring and the centres are indexed through fully unrolled loops only (registers, no scratch).
+//
+// Bit contract: every K-tap sum is tap(0) v_0 followed by fma(tap(j), v_j, acc) for ascending j, x first, then y,
+// then z - the arithmetic of wt_hrow_filter + WtVert (wt_stencil.h) on each slice followed by wt_zfilter_kernel
+// and wt_binary(SUB) (wt_kernels_apps.h), so the planes equal those of wt_decompose3d bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "wt_internal.h"
+#include "wt_device.h"
+#include "wt_stencil.h"
+
+#define WT_CUBE_TY 8          // output rows of a workgroup (two per wave)
+
+struct CubeArgs {
+    const float *in;   // c_s
+    float *out_c;      // c_{s+1}
+    float *out_w;      // w_s
+    int W, P;          // columns, row pitch (elements)
+    int Y, Z;          // rows per slice, slices
+    int d;             // dilation 2^s
+    int ycls, zcls;    // row classes min(d, Y), z chains min(d, Z)
+    int S;             // chain steps per chunk
+    int nt;            // streaming stores (planes far larger than the caches)
+};
+
+// grid: x = 256-column blocks, y = row class + ycls * row group, z = z chain + zcls * chunk
+template <int K, bool SMALL_D>
+__global__ __launch_bounds__(256) void wt_cube_scale_kernel(CubeArgs a)
+{
+    constexpr int hw = K / 2;
+    constexpr int TY = WT_CUBE_TY;
+    constexpr int NR = TY + 2 * hw;          // x-filtered rows per step
+    constexpr int RPW = (NR + 3) / 4;        // ... per wave
+    __shared__ float4 xf[2][NR][64];
+
+    const int lane = threadIdx.x;
+    const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.y);      // wave-uniform by construction
+    const int d = a.d;
+    const int x = (blockIdx.x * 64 + lane) * 4;
+    const int qy = blockIdx.y % a.ycls, rg = blockIdx.y / a.ycls;
+    const int qz = blockIdx.z % a.zcls, ck = blockIdx.z / a.zcls;
+    const int ny = (a.Y - qy + d - 1) / d;   // rows of this class
+    const int nz = (a.Z - qz + d - 1) / d;   // steps of this chain
+    const int r0 = rg * TY;
+    const int t0 = ck * a.S, t1 = min(t0 + a.S, nz);
+    if (r0 >= ny || t0 >= t1) return;        // (the whole workgroup: no barrier is left waiting)
+    const bool lane_ok = x < a.W;
+
+    // rows this wave x-filters: rr = first + 4 m; output row i = wv + 4 mi has its centre in rr = i + hw
+    const int first = (wv + hw) & 3;
+    const int mshift = (wv + hw) >> 2;       // m of output row mi is mi + mshift
+    int yrow[RPW];
+#pragma unroll
+    for (int m = 0; m < RPW; ++m)
+        yrow[m] = wt_refl_b(qy + d * (r0 + first + 4 * m - hw), a.Y, d, 0);
+
+    float4 ring[2][K], cen[2][hw + 1];
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) ring[mi][j] = wt_vzero<float4>();
+#pragma unroll
+        for (int j = 0; j <= hw; ++j) cen[mi][j] = wt_vzero<float4>();
+    }
+
+    const int nsteps = (t1 - t0) + K - 1;    // K - 1 warm-up slices, then one output slice per step
+    for (int k = 0; k < nsteps; ++k) {
+        const int buf = k & 1;
+        const int zc = qz + d * (t0 + k - (K - 1));          // the slice this step completes (k >= K - 1)
+        const int zs = wt_refl_b(zc + hw * d, a.Z, d, 0);    // the slice that enters
+        const float *slice = a.in + (int64_t)zs * a.Y * a.P;
+        float4 cnew[2];
+        cnew[0] = cnew[1] = wt_vzero<float4>();
+#pragma unroll
+        for (int m = 0; m < RPW; ++m) {
+            const int rr = first + 4 * m;
+            if (rr < NR) {
+                float4 raw[K], h = wt_vzero<float4>(), h2 = wt_vzero<float4>(), c;
+                wt_hrow_load<float, K, SMALL_D>(slice + (int64_t)yrow[m] * a.P, x, d, a.W, raw, 0);
+                wt_hrow_filter<float, K, MODE_SMOOTH, SMALL_D>(raw, d, h, h2, c);
+                xf[buf][rr][lane] = h;
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi)
+                    if (m == mi + mshift) cnew[mi] = c;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+            const int i = wv + 4 * mi;
+            float4 v = f4_scale(wt_tap<K>(0), xf[buf][i][lane]);
+#pragma unroll
+            for (int j = 1; j < K; ++j) v = f4_fma(wt_tap<K>(j), xf[buf][i + j][lane], v);
+#pragma unroll
+            for (int j = 0; j < K - 1; ++j) ring[mi][j] = ring[mi][j + 1];
+            ring[mi][K - 1] = v;
+#pragma unroll
+            for (int j = 0; j < hw; ++j) cen[mi][j] = cen[mi][j + 1];
+            cen[mi][hw] = cnew[mi];
+            if (k >= K - 1 && r0 + i < ny) {
+                float4 o = f4_scale(wt_tap<K>(0), ring[mi][0]);
+#pragma unroll
+                for (int j = 1; j < K; ++j) o = f4_fma(wt_tap<K>(j), ring[mi][j], o);
+                const int64_t off = ((int64_t)zc * a.Y + (qy + d * (r0 + i))) * a.P;
+                wt_store4(a.out_c + off, x, a.P, o, a.nt, lane_ok);
+                wt_store4(a.out_w + off, x, a.P, f4_sub(cen[mi][0], o), a.nt, lane_ok);
+            }
+        }
+    }
+}

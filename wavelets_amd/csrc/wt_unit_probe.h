@@ -19,7 +19,7 @@
     X(fused_f64_k3_acc0) X(fused_f64_k3_acc1) X(fused_f64_k3_acc2) X(fused_f64_k3_acc3)                       \
     X(batch64) X(fused_f64_k5_batch_acc0) X(fused_f64_k5_batch_acc1) X(fused_f64_k5_batch_acc2)                 \
     X(fused_f64_k3_batch_acc0) X(fused_f64_k3_batch_acc1) X(fused_f64_k3_batch_acc2) X(bilateral64_batch)           \
-    X(stencil64_batch) X(signals) X(along) X(resident)
+    X(stencil64_batch) X(signals) X(along) X(resident) X(cubes)
 
 #define WT_PROBE_CAT2(a, b) a##b
 #define WT_PROBE_CAT(a, b) WT_PROBE_CAT2(a, b)
