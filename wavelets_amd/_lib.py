@@ -2067,6 +2067,11 @@ def acquire_plan64(ctx, H, W, taps, max_level):
         for i in range(len(_pool) - 1, -1, -1):
             if _pool[i][0] == key:
                 plan = _pool.pop(i)[1]
+                if not plan._h:
+                    # closed while pooled: a Coefficients object and its plan collected in one pass of the cyclic
+                    # garbage collector run both finalizers, in either order (Coefficients.__del__ pools the plan,
+                    # Plan.__del__ closes it)
+                    continue
                 plan.set_border(0)
                 return plan
     return Plan64(ctx, H, W, taps, max_level)
@@ -2089,6 +2094,11 @@ def acquire_plan(ctx, H, W, family, max_level):
         for i in range(len(_pool) - 1, -1, -1):
             if _pool[i][0] == key:
                 plan = _pool.pop(i)[1]
+                if not plan._h:
+                    # closed while pooled: a Coefficients object and its plan collected in one pass of the cyclic
+                    # garbage collector run both finalizers, in either order (Coefficients.__del__ pools the plan,
+                    # Plan.__del__ closes it)
+                    continue
                 plan.set_border(0)
                 return plan
     if not _COLD_FIRST_USE:
