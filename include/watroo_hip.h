@@ -494,6 +494,13 @@ int wt64_decompose(wt_plan64 *plan, int src, int level, int depth);
  * radix level of |w_0| (as flag bit4 of wt_decompose): a wt64_abs_median(plan, 0) that follows -
  * Coefficients.get_noise, watroo/wavelets.py:126-127 - then reads the plane once less */
 int wt64_decompose_ex(wt_plan64 *plan, int src, int level, int depth, int flags);
+/* The float64 cube engine (watroo/wavelets.py:432,442 over the 3-D branch of convolution(), :46-64, on the float64 and
+ * recast inputs of :297,319-320): the planes of wt64_decompose(plan, src, level, depth) on a (Z, Y, X) cube, depth = Z
+ * >= 1, bit for bit, with ONE launch per scale (x, y and z filters and the detail subtraction fused, no private
+ * temporary; a scale whose grid does not fit runs the sequence of wt64_decompose).  Same plane contract:
+ * planes[0..level], `src` intact, WT_PLANE_SCRATCH(0/1) as ping-pong.  The taps of a built-in family and the symmetric
+ * border only: anything else is refused before any device work.  Additive entry: wt_abi_version() stays 8. */
+int wt64_decompose_cube(wt_plan64 *plan, int src, int level, int depth);
 /* Pass-level entry points of the fused float64 schedule (wt_schedule; as wt_decompose_pass /
  * wt_decompose_pass_sum / wt_plan_fused_ok): they let the caller place Coefficients.denoise between
  * the passes (watroo/utils.py:95-98: transform, denoise, sum) */

@@ -143,6 +143,7 @@ SIGNATURES = {
     "wt64_upload_int": (_c.c_int, [_vp, _c.c_int, _vp, _i64, _c.c_int]),
     "wt64_download": (_c.c_int, [_vp, _c.c_int, _c.POINTER(_c.c_double), _i64]),
     "wt64_decompose": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int]),
+    "wt64_decompose_cube": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int]),
     "wt64_decompose_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
     "wt64_smooth": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "wt64_local_variance": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_double,
@@ -1929,6 +1930,10 @@ class Plan64:
 
     def decompose3d(self, src, level, depth):
         check(load().wt64_decompose(self._h, src, level, depth))
+
+    def decompose_cube(self, src, level, depth):
+        """decompose3d's planes, bit for bit, with one launch per scale (the float64 cube engine, cubes.py)"""
+        check(load().wt64_decompose_cube(self._h, src, level, depth))
 
     def smooth(self, src, dst, s, square_input=False, flags=0):
         check(load().wt64_smooth(self._h, src, dst, s, int(square_input), 0))

@@ -6,7 +6,7 @@
 #include <cstdlib>
 
 #include "wt_host.h"
-#include "wt_cubes_kernels.h"
+#include "wt_cubes_host.h"
 #include "wt_rl_point.h"      // WT_OP_SUB
 #include "wt_unit_probe.h"
 
@@ -17,51 +17,16 @@ WT_UNIT_PROBE_DEFINE
 // tools/bench_cubes.py times every scale both ways (profiles/r25_cubes.json, MI355X; table in DESIGN.md section 3.21):
 // the fused kernel won at every (Z, d) measured, chains of ONE step included - 8x512x512 d = 8: 0.043 against
 // 0.098 ms, 16x64x64 d = 16: 0.022 against 0.101 ms, 4x1024x1024 Triangle d = 4: 0.032 against 0.057 ms - so the
-// constant is 1 and the old sequence serves only a scale whose grid does not fit (cube_geometry).
-// WT_CUBE_FUSED=1 / 0 in the environment forces the fused kernel / the old sequence at every scale (tests, the bench).
+// constant is 1 and the old sequence serves only a scale whose grid does not fit (cube_geometry_t, wt_cubes_host.h,
+// which also reads the WT_CUBE_FUSED switch).
 #define WT_CUBE_MIN_STEPS 1
-
-static int cube_forced()
-{
-    const char *e = getenv("WT_CUBE_FUSED");     // read at every call: the tests switch it within one process
-    return (e && *e) ? (atoi(e) != 0) : -1;
-}
-
-// geometry of one fused scale; false: the grid does not fit (the old sequence serves the scale)
-static bool cube_geometry(const wt_plan *p, int s, int depth, CubeArgs &a, dim3 &grid)
-{
-    if (s > 24) return false;
-    const int K = family_taps(p->family);
-    a.W = p->g.W; a.P = p->g.P;
-    a.Z = depth; a.Y = p->g.H / depth;
-    a.d = 1 << s;
-    a.ycls = std::min(a.d, a.Y);
-    a.zcls = std::min(a.d, a.Z);
-    const int ny = (a.Y + a.d - 1) / a.d, nz = (a.Z + a.d - 1) / a.d;      // longest row class / z chain
-    const int64_t gx = (a.W + 255) / 256;
-    const int64_t gy = (int64_t)a.ycls * ((ny + WT_CUBE_TY - 1) / WT_CUBE_TY);
-    // chunks of the z chains: about two rounds of resident workgroups (4 per CU), chunks of at least 4 (K - 1) steps so
-    // that the warm-up slices stay a fifth of the work
-    const int64_t want = (int64_t)p->ctx->num_cus * 8;
-    const int64_t have = gx * gy * a.zcls;
-    int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(nz, (want + have - 1) / have));
-    int S = (nz + chunks - 1) / chunks;
-    S = std::min(nz, std::max(S, 4 * (K - 1)));
-    chunks = (nz + S - 1) / S;
-    a.S = S;
-    const int64_t gz = (int64_t)a.zcls * chunks;
-    if (gx > 0x7fffffff || gy > 65535 || gz > 65535) return false;
-    a.nt = (int64_t)p->g.H * a.P * (int64_t)sizeof(float) >= ((int64_t)32 << 20);      // planes >> L2: streaming stores
-    grid = dim3((unsigned)gx, (unsigned)gy, (unsigned)gz);
-    return true;
-}
 
 static int cube_scale_launch(wt_plan *p, const float *in, float *oc, float *ow, int s, int depth, bool *done)
 {
     CubeArgs a{};
     dim3 grid;
     *done = false;
-    if (!cube_geometry(p, s, depth, a, grid)) return 0;
+    if (!cube_geometry_t<float>(p->g, p->ctx->num_cus, family_taps(p->family), s, depth, a, grid)) return 0;
     const int forced = cube_forced();
     const int steps = (a.Z + a.d - 1) / a.d;
     if (forced == 0 || (forced < 0 && steps < WT_CUBE_MIN_STEPS)) return 0;
@@ -70,11 +35,11 @@ static int cube_scale_launch(wt_plan *p, const float *in, float *oc, float *ow, 
     const bool small = a.d < 4;
     ProfScope ps(p->ctx, "wt_cube_scale_kernel");
     if (p->family == WT_B3SPLINE) {
-        if (small) hipLaunchKernelGGL((wt_cube_scale_kernel<5, true>), grid, block, 0, p->ctx->stream, a);
-        else hipLaunchKernelGGL((wt_cube_scale_kernel<5, false>), grid, block, 0, p->ctx->stream, a);
+        if (small) hipLaunchKernelGGL((wt_cube_scale_kernel<float, 5, true>), grid, block, 0, p->ctx->stream, a);
+        else hipLaunchKernelGGL((wt_cube_scale_kernel<float, 5, false>), grid, block, 0, p->ctx->stream, a);
     } else {
-        if (small) hipLaunchKernelGGL((wt_cube_scale_kernel<3, true>), grid, block, 0, p->ctx->stream, a);
-        else hipLaunchKernelGGL((wt_cube_scale_kernel<3, false>), grid, block, 0, p->ctx->stream, a);
+        if (small) hipLaunchKernelGGL((wt_cube_scale_kernel<float, 3, true>), grid, block, 0, p->ctx->stream, a);
+        else hipLaunchKernelGGL((wt_cube_scale_kernel<float, 3, false>), grid, block, 0, p->ctx->stream, a);
     }
     WT_HIP(hipGetLastError());
     *done = true;

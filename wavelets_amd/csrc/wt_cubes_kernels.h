@@ -1,9 +1,11 @@
-// One scale of the a-trous transform of a (Z, Y, X) float32 cube in ONE launch: the x, y and z filters of the 3-D
+// One scale of the a-trous transform of a (Z, Y, X) cube in ONE launch: the x, y and z filters of the 3-D
 // branch of convolution() (watroo/wavelets.py:46-64) and the detail subtraction (wavelets.py:442).  The cube is
-// stored as everywhere in the library, a (Z*Y) x X image with pitch P.  gfx950 only.
+// stored as everywhere in the library, a (Z*Y) x X image with pitch P.  One text for both element types (WtVec<T>):
+// T = float - a lane owns a float4 group - or T = double - a double2 group; 16 bytes per access and the same
+// registers and LDS either way.  gfx950 only.
 //
-// A workgroup of 4 waves owns 256 columns (64 lanes x one float4 group, 16-byte accesses), TY = 8 rows of one
-// polyphase row class y = q_y + d (r0 + i) and a chunk of one polyphase chain along z, z = q_z + d t.  Per chain
+// A workgroup of 4 waves owns 64 PX columns (64 lanes x one group: 256 float / 128 double columns), TY = 8 rows of
+// one polyphase row class y = q_y + d (r0 + i) and a chunk of one polyphase chain along z, z = q_z + d t.  Per chain
 // step it
 //   1. x-filters the TY + 2 hw rows y + (j - hw) d of slice z + hw d into LDS (wt_hrow_filter, the row filter of
 //      every per-scale kernel; the rows go round the waves so that the wave that owns output row i is the one that
@@ -17,7 +19,9 @@
 //
 // Bit contract: every K-tap sum is tap(0) v_0 followed by fma(tap(j), v_j, acc) for ascending j, x first, then y,
 // then z - the arithmetic of wt_hrow_filter + WtVert (wt_stencil.h) on each slice followed by wt_zfilter_kernel
-// and wt_binary(SUB) (wt_kernels_apps.h), so the planes equal those of wt_decompose3d bit for bit.
+// and wt_binary(SUB) (wt_kernels_apps.h), so the planes equal those of wt_decompose3d bit for bit.  For double it is
+// the arithmetic of wt64_rows_kernel / wt64_rows2_kernel and of wt64_axis_kernel on axis 1, then on axis 0 with the
+// detail cen - acc (wt_kernels_f64.h: smooth64 with depth > 0), with the dyadic taps fused64_family recognises.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,10 +31,11 @@
 
 #define WT_CUBE_TY 8          // output rows of a workgroup (two per wave)
 
-struct CubeArgs {
-    const float *in;   // c_s
-    float *out_c;      // c_{s+1}
-    float *out_w;      // w_s
+template <typename T>
+struct CubeArgsT {
+    const T *in;       // c_s
+    T *out_c;          // c_{s+1}
+    T *out_w;          // w_s
     int W, P;          // columns, row pitch (elements)
     int Y, Z;          // rows per slice, slices
     int d;             // dilation 2^s
@@ -38,21 +43,24 @@ struct CubeArgs {
     int S;             // chain steps per chunk
     int nt;            // streaming stores (planes far larger than the caches)
 };
+typedef CubeArgsT<float> CubeArgs;
 
-// grid: x = 256-column blocks, y = row class + ycls * row group, z = z chain + zcls * chunk
-template <int K, bool SMALL_D>
-__global__ __launch_bounds__(256) void wt_cube_scale_kernel(CubeArgs a)
+// grid: x = blocks of 64 PX columns, y = row class + ycls * row group, z = z chain + zcls * chunk
+template <typename T, int K, bool SMALL_D>
+__global__ __launch_bounds__(256) void wt_cube_scale_kernel(CubeArgsT<T> a)
 {
+    typedef typename WtVec<T>::V V;
+    constexpr int PX = WtVec<T>::PX;
     constexpr int hw = K / 2;
     constexpr int TY = WT_CUBE_TY;
     constexpr int NR = TY + 2 * hw;          // x-filtered rows per step
     constexpr int RPW = (NR + 3) / 4;        // ... per wave
-    __shared__ float4 xf[2][NR][64];
+    __shared__ V xf[2][NR][64];
 
     const int lane = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.y);      // wave-uniform by construction
     const int d = a.d;
-    const int x = (blockIdx.x * 64 + lane) * 4;
+    const int x = (blockIdx.x * 64 + lane) * PX;
     const int qy = blockIdx.y % a.ycls, rg = blockIdx.y / a.ycls;
     const int qz = blockIdx.z % a.zcls, ck = blockIdx.z / a.zcls;
     const int ny = (a.Y - qy + d - 1) / d;   // rows of this class
@@ -70,13 +78,13 @@ __global__ __launch_bounds__(256) void wt_cube_scale_kernel(CubeArgs a)
     for (int m = 0; m < RPW; ++m)
         yrow[m] = wt_refl_b(qy + d * (r0 + first + 4 * m - hw), a.Y, d, 0);
 
-    float4 ring[2][K], cen[2][hw + 1];
+    V ring[2][K], cen[2][hw + 1];
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
-        for (int j = 0; j < K; ++j) ring[mi][j] = wt_vzero<float4>();
+        for (int j = 0; j < K; ++j) ring[mi][j] = wt_vzero<V>();
 #pragma unroll
-        for (int j = 0; j <= hw; ++j) cen[mi][j] = wt_vzero<float4>();
+        for (int j = 0; j <= hw; ++j) cen[mi][j] = wt_vzero<V>();
     }
 
     const int nsteps = (t1 - t0) + K - 1;    // K - 1 warm-up slices, then one output slice per step
@@ -84,16 +92,16 @@ __global__ __launch_bounds__(256) void wt_cube_scale_kernel(CubeArgs a)
         const int buf = k & 1;
         const int zc = qz + d * (t0 + k - (K - 1));          // the slice this step completes (k >= K - 1)
         const int zs = wt_refl_b(zc + hw * d, a.Z, d, 0);    // the slice that enters
-        const float *slice = a.in + (int64_t)zs * a.Y * a.P;
-        float4 cnew[2];
-        cnew[0] = cnew[1] = wt_vzero<float4>();
+        const T *slice = a.in + (int64_t)zs * a.Y * a.P;
+        V cnew[2];
+        cnew[0] = cnew[1] = wt_vzero<V>();
 #pragma unroll
         for (int m = 0; m < RPW; ++m) {
             const int rr = first + 4 * m;
             if (rr < NR) {
-                float4 raw[K], h = wt_vzero<float4>(), h2 = wt_vzero<float4>(), c;
-                wt_hrow_load<float, K, SMALL_D>(slice + (int64_t)yrow[m] * a.P, x, d, a.W, raw, 0);
-                wt_hrow_filter<float, K, MODE_SMOOTH, SMALL_D>(raw, d, h, h2, c);
+                V raw[K], h = wt_vzero<V>(), h2 = wt_vzero<V>(), c;
+                wt_hrow_load<T, K, SMALL_D>(slice + (int64_t)yrow[m] * a.P, x, d, a.W, raw, 0);
+                wt_hrow_filter<T, K, MODE_SMOOTH, SMALL_D>(raw, d, h, h2, c);
                 xf[buf][rr][lane] = h;
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
@@ -104,9 +112,9 @@ __global__ __launch_bounds__(256) void wt_cube_scale_kernel(CubeArgs a)
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
             const int i = wv + 4 * mi;
-            float4 v = f4_scale(wt_tap<K>(0), xf[buf][i][lane]);
+            V v = f4_scale(wt_tap_s<K, T>(0), xf[buf][i][lane]);
 #pragma unroll
-            for (int j = 1; j < K; ++j) v = f4_fma(wt_tap<K>(j), xf[buf][i + j][lane], v);
+            for (int j = 1; j < K; ++j) v = f4_fma(wt_tap_s<K, T>(j), xf[buf][i + j][lane], v);
 #pragma unroll
             for (int j = 0; j < K - 1; ++j) ring[mi][j] = ring[mi][j + 1];
             ring[mi][K - 1] = v;
@@ -114,12 +122,12 @@ __global__ __launch_bounds__(256) void wt_cube_scale_kernel(CubeArgs a)
             for (int j = 0; j < hw; ++j) cen[mi][j] = cen[mi][j + 1];
             cen[mi][hw] = cnew[mi];
             if (k >= K - 1 && r0 + i < ny) {
-                float4 o = f4_scale(wt_tap<K>(0), ring[mi][0]);
+                V o = f4_scale(wt_tap_s<K, T>(0), ring[mi][0]);
 #pragma unroll
-                for (int j = 1; j < K; ++j) o = f4_fma(wt_tap<K>(j), ring[mi][j], o);
+                for (int j = 1; j < K; ++j) o = f4_fma(wt_tap_s<K, T>(j), ring[mi][j], o);
                 const int64_t off = ((int64_t)zc * a.Y + (qy + d * (r0 + i))) * a.P;
-                wt_store4(a.out_c + off, x, a.P, o, a.nt, lane_ok);
-                wt_store4(a.out_w + off, x, a.P, f4_sub(cen[mi][0], o), a.nt, lane_ok);
+                wt_storev<T, V>(a.out_c + off, x, a.P, o, a.nt, lane_ok);
+                wt_storev<T, V>(a.out_w + off, x, a.P, f4_sub(cen[mi][0], o), a.nt, lane_ok);
             }
         }
     }

@@ -11,6 +11,7 @@
 #include "wt_fft.h"
 #include "wt_axis.h"
 #include "wt_f64.h"
+#include "wt_cubes64.h"       // wt64_decompose_cube: the fused cube scale kernel for double beside smooth64
 #include "wt_unit_probe.h"
 
 WT_UNIT_PROBE_DEFINE

@@ -1,31 +1,33 @@
-"""(Z, Y, X) cubes - solar image sequences, spectral cubes - through the float32 cube engine (wt_cubes): ONE launch
-per scale computes the x, y and z filters of the 3-D branch of convolution() (ref wavelets.py:46-64) and the detail
-subtraction (ref wavelets.py:442), where AtrousTransform launches the 2-D filter once per slice, a z filter and a
-subtraction.
+"""(Z, Y, X) cubes - solar image sequences, spectral cubes - through the cube engines (wt_cubes, float32; wt_cubes64,
+float64): ONE launch per scale computes the x, y and z filters of the 3-D branch of convolution() (ref wavelets.py:46-64)
+and the detail subtraction (ref wavelets.py:442), where AtrousTransform launches the 2-D filter once per slice, a z
+filter and a subtraction (float32) or three one-sample-per-thread filters through two temporaries (float64).
 
     transform_cube(cube, level).data  == AtrousTransform(sf)(cube, level).data
     denoise_cube(cube, weights, ...)  == denoise(cube, weights, sf, ...)
 
 bit for bit: the kernel keeps the arithmetic of the kernels it replaces (x, then y, then z; every K-tap sum in
-ascending tap order), and a scale whose z chains are too short for the fused march still runs
-on them.  Cubes the engine does not cover - float64 and integer cubes, bilateral or recursive transforms, user-defined
-scaling functions - return what AtrousTransform / denoise return; cube_eligible says which.  AtrousTransform, denoise
-and wow keep their own routing."""
+ascending tap order, DESIGN.md sections 3.21 and 3.22), and a scale the fused march does not serve still runs on them.
+float64 cubes and the cubes the reference recasts to float64 (ref wavelets.py:297,319-320: int16 / uint16 / int32 /
+big-endian FITS data) run in float64, integers and big-endian floats crossing PCIe as they are.  Cubes the engines do
+not cover - bilateral or recursive transforms, user-defined scaling functions - return what AtrousTransform / denoise
+return; cube_eligible and cube64_eligible say which.  AtrousTransform, denoise and wow keep their own routing."""
 import numpy as np
 
-from ._lib import PLANE_INPUT, PLANE_OUT, acquire_plan, default_context
+from ._lib import PLANE_INPUT, PLANE_OUT, acquire_plan, acquire_plan64, default_context, device_widens
 from .wavelets import (AtrousTransform, B3spline, Coefficients, _family_of, _is_f64, _needs_generic, _result_dtype,
-                       generalized_anscombe)
+                       _taps_f64, generalized_anscombe)
 from .utils import denoise
 
-__all__ = ['transform_cube', 'denoise_cube', 'cube_eligible']
+__all__ = ['transform_cube', 'denoise_cube', 'cube_eligible', 'cube64_eligible']
 
 
-def _cube_family(cube, level, scaling_function, bilateral=None, recursive=False):
-    """the family (an int) the cube engine computes this cube with, or None (cube_eligible)"""
+def _cube_family(cube, level, scaling_function, bilateral=None, recursive=False, f64=False):
+    """the family (an int) the float32 (f64: the float64) cube engine computes this cube with, or None (cube_eligible,
+    cube64_eligible)"""
     if not isinstance(cube, np.ndarray) or cube.ndim != 3 or min(cube.shape) < 1:
         return None
-    if _is_f64(cube) or bilateral is not None or recursive:
+    if _is_f64(cube) != f64 or bilateral is not None or recursive:
         return None
     if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level < 0:
         return None
@@ -39,15 +41,41 @@ def _cube_family(cube, level, scaling_function, bilateral=None, recursive=False)
 
 
 def cube_eligible(cube, level, scaling_function=B3spline, bilateral=None, recursive=False):
-    """True when the cube engine computes this transform (host logic): a 3-D ndarray with every side >= 1 that the
-    reference would not compute in float64 (ref wavelets.py:297,319-320); a built-in scaling function with its own
-    taps; no bilateral filtering, the standard algorithm, an int level >= 0.  Everything else runs AtrousTransform."""
+    """True when the float32 cube engine computes this transform (host logic): a 3-D ndarray with every side >= 1 that
+    the reference would not compute in float64 (ref wavelets.py:297,319-320); a built-in scaling function with its own
+    taps; no bilateral filtering, the standard algorithm, an int level >= 0.  Everything else runs the float64 engine
+    (cube64_eligible) or AtrousTransform."""
     return _cube_family(cube, level, scaling_function, bilateral, recursive) is not None
+
+
+def cube64_eligible(cube, level, scaling_function=B3spline, bilateral=None, recursive=False):
+    """True when the float64 cube engine computes this transform (host logic): the rule of cube_eligible for the cubes
+    the reference DOES compute in float64 (ref wavelets.py:297,319-320) - float64, and the integer and big-endian types
+    it recasts.  Never true together with cube_eligible."""
+    return _cube_family(cube, level, scaling_function, bilateral, recursive, f64=True) is not None
+
+
+def _cube64_coefficients(cube, level, scaling_function, anscombe=False):
+    """transform_cube on the float64 engine: ``Coefficients`` on a Plan64 (anscombe: of the Anscombe transform of the
+    cube, taken on the plan's input plane - the pointwise kernel generalized_anscombe runs, ref utils.py:93-94).  Element
+    types Plan64.upload widens on the device - integers, big-endian floats - go up as they are, as (Z*Y, X) rows."""
+    a = np.asarray(cube)
+    a = np.ascontiguousarray(a) if device_widens(a.dtype) else np.ascontiguousarray(a, dtype=np.float64)
+    Z, Y, X = a.shape
+    sf = scaling_function(3)
+    plan = acquire_plan64(default_context(), Z * Y, X, _taps_f64(sf, 3), level)
+    plan.upload(PLANE_INPUT, a.reshape(Z * Y, X))
+    if anscombe:
+        plan.anscombe(PLANE_INPUT, PLANE_INPUT)
+    plan.decompose_cube(PLANE_INPUT, level, Z)
+    return Coefficients(plan, sf, None, _shape=(Z, Y, X), _dtype=np.float64)
 
 
 def transform_cube(cube, level, scaling_function=B3spline):
     """``Coefficients`` of the standard transform of a (Z, Y, X) cube, AtrousTransform(scaling_function)(cube, level)
     bit for bit (ref wavelets.py:307-328 over :46-64), one launch per scale."""
+    if cube64_eligible(cube, level, scaling_function):
+        return _cube64_coefficients(cube, int(level), scaling_function)
     fam = _cube_family(cube, level, scaling_function)
     if fam is None:
         return AtrousTransform(scaling_function)(cube, level)
@@ -64,12 +92,16 @@ def transform_cube(cube, level, scaling_function=B3spline):
 def denoise_cube(cube, weights, scaling_function=B3spline, noise=None, soft_threshold=True, anscombe=False):
     """utils.denoise(cube, weights, scaling_function, noise, soft_threshold=..., anscombe=...) bit for bit (ref
     utils.py:83-102 on a 3-D array): its call sequence on transform_cube's coefficients."""
-    if not cube_eligible(cube, len(weights), scaling_function):
+    f64 = cube64_eligible(cube, len(weights), scaling_function)
+    if not f64 and not cube_eligible(cube, len(weights), scaling_function):
         return denoise(cube, weights, scaling_function, noise, soft_threshold=soft_threshold, anscombe=anscombe)
-    arr = np.asarray(cube, np.float32)
-    if anscombe:
-        arr = generalized_anscombe(arr)
-    coefficients = transform_cube(arr, len(weights), scaling_function)
+    if f64:
+        coefficients = _cube64_coefficients(cube, len(weights), scaling_function, anscombe)
+    else:
+        arr = np.asarray(cube, np.float32)
+        if anscombe:
+            arr = generalized_anscombe(arr)
+        coefficients = transform_cube(arr, len(weights), scaling_function)
     coefficients.noise = noise
     plan = coefficients._denoise_sum(weights, soft_threshold=soft_threshold, write_back=False)
     if anscombe:
