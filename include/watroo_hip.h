@@ -362,6 +362,16 @@ int wt_decompose3d(wt_plan *plan, int src, int level, int depth);
  * Built-in scaling functions, one rank and the symmetric border only: anything else is refused before any
  * device work. */
 int wt_decompose_cube(wt_plan *plan, int src, int level, int depth);
+/* One scale of the whitening loop of wow on a (Z, Y, X) cube, depth = Z (watroo/utils.py:193-203 over the 3-D branch of
+ * convolution(), watroo/wavelets.py:46-64): the local power conv_s(plane^2) of the 3-D filter and the update of
+ * wt_wow_update in ONE launch - the squares are taken on load, the power never leaves the registers - where
+ * wt_binary(mul) + wt_smooth3d + wt_wow_update take depth + 3.  The updated plane replaces `plane` (0 .. max_level) by
+ * a pointer swap with WT_PLANE_SCRATCH(3), as in wt_wow_scale.  Bit-identical to that sequence, which still serves a
+ * scale the rule of wt_decompose_cube or the grid limit refuses (through WT_PLANE_SCRATCH(6), (7) and (15)).
+ * noise_plane / gamma_plane: as wt_wow_update; they must not alias the plane or those scratch planes.  Refusals as
+ * wt_decompose_cube.  Additive entry: wt_abi_version() stays 8. */
+int wt_wow_cube_scale(wt_plan *plan, int plane, int s, int depth, double tau, int soft, int noise_plane,
+                      float factor, int gamma_plane);
 /* bilateral transform of cubes, one scale at a time (watroo/wavelets.py:433-440 on 3-D input):
  * wt_local_variance3d = sdev_loc(cube, variance=True) * f1 * f2 (3-D smoothing of I and I^2,
  * scratch planes 13-15); wt_bilateral3d_conv = atrous_convolution with the K^3 kernel and that
@@ -501,6 +511,13 @@ int wt64_decompose_ex(wt_plan64 *plan, int src, int level, int depth, int flags)
  * planes[0..level], `src` intact, WT_PLANE_SCRATCH(0/1) as ping-pong.  The taps of a built-in family and the symmetric
  * border only: anything else is refused before any device work.  Additive entry: wt_abi_version() stays 8. */
 int wt64_decompose_cube(wt_plan64 *plan, int src, int level, int depth);
+/* wt_wow_cube_scale on a float64 plan (watroo/utils.py:193-203 over watroo/wavelets.py:46-64, float64 and recast
+ * cubes): one launch where wt64_binary(mul) + wt64_smooth(depth) + wt64_wow_update take five through cube-sized
+ * temporaries; the updated plane replaces `plane` by a pointer swap with the plan's first private temporary, as in
+ * wt64_wow_scale.  Bit-identical to that sequence, which serves a scale the rule of wt64_decompose_cube or the grid
+ * limit refuses (through WT_PLANE_SCRATCH(6) and (7)).  Additive entry: wt_abi_version() stays 8. */
+int wt64_wow_cube_scale(wt_plan64 *plan, int plane, int s, int depth, double tau, int soft, int noise_plane,
+                        double factor, int gamma_plane);
 /* Pass-level entry points of the fused float64 schedule (wt_schedule; as wt_decompose_pass /
  * wt_decompose_pass_sum / wt_plan_fused_ok): they let the caller place Coefficients.denoise between
  * the passes (watroo/utils.py:95-98: transform, denoise, sum) */

@@ -15,7 +15,7 @@ from .batch import transform_stack, denoise_stack, wow_stack, enhance_stack, ric
 from .signals import transform_signals, denoise_signals, signals_eligible  # noqa: F401  (stacks of 1-D signals of one length: a workgroup per signal, the scales in LDS)
 from .along import transform_along, denoise_along, along_eligible  # noqa: F401  (the 1-D transform along any axis of an array: a tile of neighbouring signals per workgroup)
 from .wow_signals import wow_signals, wow_along, wow_signals_eligible  # noqa: F401  (wow of stacks of 1-D signals and along an axis: the per-scale loop of a signal in one launch)
-from .cubes import transform_cube, denoise_cube, cube_eligible, cube64_eligible  # noqa: F401  ((Z, Y, X) cubes, float32 and float64 / integer: the x, y and z filters and the detail of a scale in one launch)
+from .cubes import transform_cube, denoise_cube, wow_cube, cube_eligible, cube64_eligible, wow_cube_eligible  # noqa: F401  ((Z, Y, X) cubes, float32 and float64 / integer: the x, y and z filters and the detail of a scale in one launch; wow's whitening of a scale in one more)
 from .rng import normal_frames  # noqa: F401  (seeded standard-normal frames, filled on the GPU)
 from . import resident  # noqa: F401  (transform_stack / denoise_stack from a device array to a device array: no PCIe crossing)
 from .resident import DeviceArray  # noqa: F401

@@ -120,6 +120,7 @@ SIGNATURES = {
     "wt_smooth3d": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "wt_decompose3d": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int]),
     "wt_decompose_cube": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int]),
+    "wt_wow_cube_scale": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _c.c_float, _c.c_int]),
     "wt_local_variance3d": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float]),
     "wt_bilateral3d_conv": (_c.c_int, [_vp] + [_c.c_int] * 5),
     "wt_filter2d": (_c.c_int, [_vp, _c.c_int, _c.c_int, _fp, _c.c_int, _c.c_int, _c.c_int]),
@@ -144,6 +145,7 @@ SIGNATURES = {
     "wt64_download": (_c.c_int, [_vp, _c.c_int, _c.POINTER(_c.c_double), _i64]),
     "wt64_decompose": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int]),
     "wt64_decompose_cube": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int]),
+    "wt64_wow_cube_scale": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _c.c_double, _c.c_int]),
     "wt64_decompose_sum": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
     "wt64_smooth": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "wt64_local_variance": (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_double,
@@ -972,6 +974,10 @@ class Plan:
     def decompose_cube(self, src, level, depth):
         """decompose3d's planes, bit for bit, with one launch per scale (the float32 cube engine, cubes.py)"""
         check(load().wt_decompose_cube(self._h, src, level, depth))
+
+    def wow_cube_scale(self, plane, s, depth, tau, soft, noise_plane, factor, gamma_plane):
+        """binary("mul") + smooth3d + wow_update of one scale of a cube, bit for bit, in one launch (wt_wow_cube_scale)"""
+        check(load().wt_wow_cube_scale(self._h, plane, s, depth, float(tau), int(soft), noise_plane, float(factor), gamma_plane))
 
     def filter2d(self, src, dst, kernel, flags=0, anchor=None, periodic=False):
         k = np.ascontiguousarray(kernel, dtype=np.float32)
@@ -1934,6 +1940,10 @@ class Plan64:
     def decompose_cube(self, src, level, depth):
         """decompose3d's planes, bit for bit, with one launch per scale (the float64 cube engine, cubes.py)"""
         check(load().wt64_decompose_cube(self._h, src, level, depth))
+
+    def wow_cube_scale(self, plane, s, depth, tau, soft, noise_plane, factor, gamma_plane):
+        """binary("mul") + smooth3d + wow_update of one scale of a cube, bit for bit, in one launch (wt64_wow_cube_scale)"""
+        check(load().wt64_wow_cube_scale(self._h, plane, s, depth, float(tau), int(soft), noise_plane, float(factor), gamma_plane))
 
     def smooth(self, src, dst, s, square_input=False, flags=0):
         check(load().wt64_smooth(self._h, src, dst, s, int(square_input), 0))

@@ -1,13 +1,14 @@
 // libwatroo_hip.so - the float32 cube engine: wt_decompose_cube, the a-trous transform of a (Z, Y, X) cube with one
 // launch per scale (wt_cube_scale_kernel, wt_cubes_kernels.h) where wt_decompose3d (wt_apps.hip) takes Z + 2.  The
 // planes are those of wt_decompose3d bit for bit, so the host chooses per scale between the fused kernel and the old
-// sequence (wt_smooth3d + wt_binary(SUB)).  gfx950 only.
+// sequence (wt_smooth3d + wt_binary(SUB)).  wt_wow_cube_scale is the whitening step of wow on such a cube, one launch
+// per scale (wt_cube_wow_kernel) where mul + wt_smooth3d + wt_wow_update take Z + 3.  gfx950 only.
 #include <algorithm>
 #include <cstdlib>
 
 #include "wt_host.h"
 #include "wt_cubes_host.h"
-#include "wt_rl_point.h"      // WT_OP_SUB
+#include "wt_rl_point.h"      // WT_OP_SUB, WT_OP_MUL
 #include "wt_unit_probe.h"
 
 WT_UNIT_PROBE_DEFINE
@@ -76,5 +77,69 @@ extern "C" int wt_decompose_cube(wt_plan *p, int src, int level, int depth)
         }
         cur = nxt;
     }
+    return 0;
+}
+
+template <bool PLAIN>
+static void cube_wow_launch(wt_plan *p, const CubeWowArgsT<float> &a, dim3 grid)
+{
+    const dim3 block(64, 4);
+    const bool small = a.c.d < 4;
+    if (p->family == WT_B3SPLINE) {
+        if (small) hipLaunchKernelGGL((wt_cube_wow_kernel<float, 5, true, PLAIN>), grid, block, 0, p->ctx->stream, a);
+        else hipLaunchKernelGGL((wt_cube_wow_kernel<float, 5, false, PLAIN>), grid, block, 0, p->ctx->stream, a);
+    } else {
+        if (small) hipLaunchKernelGGL((wt_cube_wow_kernel<float, 3, true, PLAIN>), grid, block, 0, p->ctx->stream, a);
+        else hipLaunchKernelGGL((wt_cube_wow_kernel<float, 3, false, PLAIN>), grid, block, 0, p->ctx->stream, a);
+    }
+}
+
+// One scale of the whitening loop of wow on a cube (watroo/utils.py:193-203 over wavelets.py:46-64): plane <- the
+// update of wt_wow_update with the local power conv_s(plane^2) of the 3-D filter, in one launch; the result is written
+// to WT_PLANE_SCRATCH(3), whose pointer is then swapped with the plane's, as wt_wow_scale does.  The per-scale rule is
+// that of wt_decompose_cube (WT_CUBE_MIN_STEPS, the WT_CUBE_FUSED switch); a scale it or the grid limit refuses runs
+// wt_binary(MUL) -> scratch 6, wt_smooth3d -> scratch 7 (through scratch 15), wt_wow_update: the same bits.
+extern "C" int wt_wow_cube_scale(wt_plan *p, int plane, int s, int depth, double tau, int soft, int noise_plane, float factor,
+                                 int gamma_plane)
+{
+    WtGuard guard_(ctx_of(p));
+    if (!p) WT_FAIL("wt_wow_cube_scale: null plan");
+    if (p->nranks != 1) WT_FAIL("wt_wow_cube_scale: single-GPU plans only (%d ranks)", p->nranks);
+    if (p->g.border != 0) WT_FAIL("wt_wow_cube_scale: the symmetric border only (plan border %d)", p->g.border);
+    if (p->ntaps) WT_FAIL("wt_wow_cube_scale: built-in scaling functions only (the plan holds %d user-defined taps)", p->ntaps);
+    if (depth < 1 || p->g.H % depth) WT_FAIL("wt_wow_cube_scale: plan height %d is not a multiple of depth %d", p->g.H, depth);
+    if (plane < 0 || plane > p->max_level) WT_FAIL("wt_wow_cube_scale: plane %d is not a coefficient plane", plane);
+    WT_TRY(check_scale(p, s, "wt_wow_cube_scale"));
+    const int spare = WT_PLANE_SCRATCH(3), sq = WT_PLANE_SCRATCH(6), pw = WT_PLANE_SCRATCH(7), tmp = WT_PLANE_SCRATCH(15);
+    for (int op : {noise_plane, gamma_plane}) {
+        if (op == WT_PLANE_NONE) continue;
+        if (op == plane || op == spare || op == sq || op == pw || op == tmp)
+            WT_FAIL("wt_wow_cube_scale: operand plane %d aliases the plane or scratch 3 / 6 / 7 / 15, which are used internally", op);
+    }
+    if (noise_plane != WT_PLANE_NONE && noise_plane == gamma_plane) WT_FAIL("wt_wow_cube_scale: the noise map and the gamma plane alias");
+    float *c = nullptr, *t = nullptr, *nz = nullptr, *gm = nullptr;
+    WT_TRY(plane_base(p, plane, &c));
+    if (noise_plane != WT_PLANE_NONE) WT_TRY(plane_base(p, noise_plane, &nz));
+    if (gamma_plane != WT_PLANE_NONE) WT_TRY(plane_base(p, gamma_plane, &gm));
+    CubeWowArgsT<float> a{};
+    dim3 grid;
+    const int forced = cube_forced();
+    bool fused = forced != 0 && cube_geometry_t<float>(p->g, p->ctx->num_cus, family_taps(p->family), s, depth, a.c, grid);
+    if (fused && forced < 0 && (a.c.Z + a.c.d - 1) / a.c.d < WT_CUBE_MIN_STEPS) fused = false;
+    if (!fused) {
+        WT_TRY(wt_binary(p, WT_OP_MUL, plane, plane, sq));
+        WT_TRY(wt_smooth3d(p, sq, pw, s, depth));
+        return wt_wow_update(p, plane, pw, tau, soft, noise_plane, factor, gamma_plane);
+    }
+    WT_TRY(plane_base(p, spare, &t));
+    a.c.in = c; a.c.out_c = t; a.c.out_w = nullptr;
+    a.noise = nz; a.gamma = gm; a.tau = tau; a.factor = factor; a.soft = soft;
+    {
+        ProfScope ps(p->ctx, "wt_cube_wow_kernel");
+        if (!nz && !gm) cube_wow_launch<true>(p, a, grid);
+        else cube_wow_launch<false>(p, a, grid);
+        WT_HIP(hipGetLastError());
+    }
+    std::swap(p->coef[plane], p->scratch[3]);     // both are "first margin row" pointers (wt_wow_scale)
     return 0;
 }

@@ -2,7 +2,8 @@
 // branch of convolution() (watroo/wavelets.py:46-64) and the detail subtraction (wavelets.py:442).  The cube is
 // stored as everywhere in the library, a (Z*Y) x X image with pitch P.  One text for both element types (WtVec<T>):
 // T = float - a lane owns a float4 group - or T = double - a double2 group; 16 bytes per access and the same
-// registers and LDS either way.  gfx950 only.
+// registers and LDS either way.  The same march over the SQUARES of a detail plane, with the pointwise update of wow as
+// its epilogue, is the whitening of one scale of wow on a cube (wt_cube_wow_kernel, below).  gfx950 only.
 //
 // A workgroup of 4 waves owns 64 PX columns (64 lanes x one group: 256 float / 128 double columns), TY = 8 rows of
 // one polyphase row class y = q_y + d (r0 + i) and a chunk of one polyphase chain along z, z = q_z + d t.  Per chain
@@ -46,8 +47,13 @@ struct CubeArgsT {
 typedef CubeArgsT<float> CubeArgs;
 
 // grid: x = blocks of 64 PX columns, y = row class + ycls * row group, z = z chain + zcls * chunk
-template <typename T, int K, bool SMALL_D>
-__global__ __launch_bounds__(256) void wt_cube_scale_kernel(CubeArgsT<T> a)
+// The march of both kernels of this file.  HMODE is the mode of the row filter: MODE_SMOOTH, or MODE_SMOOTH_SQ - the
+// rows are the SQUARES of the loaded samples, v * v rounded once in T as wt_binary(MUL) / wt64_binary(mul) store it,
+// while the centre kept for the epilogue is the sample itself.  emit(off, x, lane_ok, cen, o) stores one lane's group
+// of output row `off` (element offset of the row start): o = the z-filter result, cen = the centre sample that
+// entered hw steps earlier.
+template <typename T, int K, bool SMALL_D, int HMODE, typename Emit>
+__device__ __forceinline__ void wt_cube_march(const CubeArgsT<T> &a, Emit emit)
 {
     typedef typename WtVec<T>::V V;
     constexpr int PX = WtVec<T>::PX;
@@ -101,7 +107,7 @@ __global__ __launch_bounds__(256) void wt_cube_scale_kernel(CubeArgsT<T> a)
             if (rr < NR) {
                 V raw[K], h = wt_vzero<V>(), h2 = wt_vzero<V>(), c;
                 wt_hrow_load<T, K, SMALL_D>(slice + (int64_t)yrow[m] * a.P, x, d, a.W, raw, 0);
-                wt_hrow_filter<T, K, MODE_SMOOTH, SMALL_D>(raw, d, h, h2, c);
+                wt_hrow_filter<T, K, HMODE, SMALL_D>(raw, d, h, h2, c);
                 xf[buf][rr][lane] = h;
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
@@ -126,9 +132,74 @@ __global__ __launch_bounds__(256) void wt_cube_scale_kernel(CubeArgsT<T> a)
 #pragma unroll
                 for (int j = 1; j < K; ++j) o = f4_fma(wt_tap_s<K, T>(j), ring[mi][j], o);
                 const int64_t off = ((int64_t)zc * a.Y + (qy + d * (r0 + i))) * a.P;
-                wt_storev<T, V>(a.out_c + off, x, a.P, o, a.nt, lane_ok);
-                wt_storev<T, V>(a.out_w + off, x, a.P, f4_sub(cen[mi][0], o), a.nt, lane_ok);
+                emit(off, x, lane_ok, cen[mi][0], o);
             }
         }
     }
+}
+
+template <typename T, int K, bool SMALL_D>
+__global__ __launch_bounds__(256) void wt_cube_scale_kernel(CubeArgsT<T> a)
+{
+    typedef typename WtVec<T>::V V;
+    wt_cube_march<T, K, SMALL_D, MODE_SMOOTH>(a, [=](int64_t off, int x, bool lane_ok, V cen, V o) {
+        wt_storev<T, V>(a.out_c + off, x, a.P, o, a.nt, lane_ok);
+        wt_storev<T, V>(a.out_w + off, x, a.P, f4_sub(cen, o), a.nt, lane_ok);
+    });
+}
+
+// One scale of the whitening loop of wow on a cube (watroo/utils.py:193-203 over the 3-D branch of convolution(),
+// wavelets.py:46-64) in ONE launch: the same march over the squares of w_s gives the local power conv_s(w_s^2), and
+// the epilogue is the shared pointwise update wt_wow_point (wt_stencil.h) of the centre sample w_s - significance,
+// gamma sum, factor * rsq(clip(power)).  One plane is stored, c.out_c, which must not be the input: neighbouring
+// workgroups still read the old values (the host writes a spare plane and swaps the plane pointers).  c.out_w is unused.
+// Bit contract: the squares are those of wt_binary(MUL), the power is that of wt_smooth3d / smooth64(depth) (x, y, z;
+// every K-tap sum in ascending tap order) and the update is wt_wow_point's, so the plane equals the one
+// mul + smooth3d + wow_update leave.
+// PLAIN: no per-voxel noise map and no gamma accumulator - the march has no conditional loads (MODE_WOW_PLAIN,
+// wt_stencil.h).  Otherwise `noise` and `gamma` may each be null; the gamma plane is read, added to and written at the
+// same voxel only.
+template <typename T>
+struct CubeWowArgsT {
+    CubeArgsT<T> c;
+    const T *noise;    // per-voxel noise map or nullptr
+    T *gamma;          // gamma accumulator or nullptr
+    double tau;        // significance threshold (<= 0: none)
+    T factor;          // w * power_norm
+    int soft;
+};
+
+template <typename T, int K, bool SMALL_D, bool PLAIN>
+__global__ __launch_bounds__(256) void wt_cube_wow_kernel(CubeWowArgsT<T> a)
+{
+    typedef typename WtVec<T>::V V;
+    constexpr int PX = WtVec<T>::PX;
+    wt_cube_march<T, K, SMALL_D, MODE_SMOOTH_SQ>(a.c, [&](int64_t off, int x, bool lane_ok, V cen, V o) {
+        T cc[PX], pw[PX], nn[PX], gg[PX], r[PX];
+        wt_vunpack(cen, cc);
+        wt_vunpack(o, pw);
+#pragma unroll
+        for (int k = 0; k < PX; ++k) {
+            nn[k] = (T)1;
+            gg[k] = (T)0;
+        }
+        if constexpr (!PLAIN) {
+            const bool full = x + PX - 1 < a.c.W;
+            if (a.noise && lane_ok) {
+#pragma unroll
+                for (int k = 0; k < PX; ++k) if (full || x + k < a.c.W) nn[k] = a.noise[off + x + k];
+            }
+            if (a.gamma && lane_ok) {
+#pragma unroll
+                for (int k = 0; k < PX; ++k) if (full || x + k < a.c.W) gg[k] = a.gamma[off + x + k];
+            }
+        }
+        const T tauf = (T)a.tau;
+#pragma unroll
+        for (int k = 0; k < PX; ++k) r[k] = wt_wow_point(cc[k], pw[k], true, nn[k], a.tau, tauf, a.soft, a.factor, gg[k]);
+        wt_storev<T, V>(a.c.out_c + off, x, a.c.P, wt_vpack(r), a.c.nt, lane_ok);
+        if constexpr (!PLAIN) {
+            if (a.gamma) wt_storev<T, V>(a.gamma + off, x, a.c.P, wt_vpack(gg), a.c.nt, lane_ok);
+        }
+    });
 }

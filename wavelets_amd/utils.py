@@ -365,10 +365,11 @@ def _gamma_range(gamma_min, gamma_max, moments):
 
 
 def _wow_device(coefficients, n_scales, weights, whitening, denoise_coefficients, soft_threshold,
-                preserve_variance, gamma, gamma_min, gamma_max, h):
+                preserve_variance, gamma, gamma_min, gamma_max, h, cube_kernel=False):
     """The device-resident part of wow (ref:157-217): per-scale loop, plane sum, gamma blend.
     Leaves the whitened planes on the plan and the image in PLANE_OUT; returns the plan.
-    (bench.py --config cfg5 times exactly this behind the transform, without the PCIe legs.)"""
+    (bench.py --config cfg5 times exactly this behind the transform, without the PCIe legs.)
+    cube_kernel: _wow_scales' keyword (cubes.wow_cube)."""
     plan = coefficients._device()
     coefficients._sum_valid = False
     npix = float(plan.H) * float(plan.W)
@@ -385,7 +386,7 @@ def _wow_device(coefficients, n_scales, weights, whitening, denoise_coefficients
         plan.set_border(2)        # the 1-D branch filters with scipy's 'mirror' border (ref:65-69)
     try:
         early = _wow_scales(plan, coefficients, n_scales, nplanes, recomposition_weights, sdc, npix,
-                            preserve_variance, whitening, h, soft_threshold, gplane)
+                            preserve_variance, whitening, h, soft_threshold, gplane, cube_kernel=cube_kernel)
     finally:
         plan.set_border(0)
 
@@ -403,11 +404,13 @@ def _wow_device(coefficients, n_scales, weights, whitening, denoise_coefficients
 
 
 def _wow_scales(plan, coefficients, n_scales, nplanes, recomposition_weights, sdc, npix,
-                preserve_variance, whitening, h, soft_threshold, gplane):
+                preserve_variance, whitening, h, soft_threshold, gplane, cube_kernel=False):
     """The per-scale loop of wow (ref:174-203).  Returns the number of leading planes whose sum (ref:205) is
     already queued into PLANE_OUT (0: none) - behind a bilateral transform the planes of the first scales are
     final while the transform's last scales still run, and their share of the sum goes beside those
-    (Plan.plane_sum_early; identical bits, the additions keep their order)."""
+    (Plan.plane_sum_early; identical bits, the additions keep their order).
+    cube_kernel (cubes.wow_cube; off: wow's own routing): the whitening of a cube's detail scales runs as one launch
+    per scale (plan.wow_cube_scale) instead of mul + smooth3d + wow_update - identical bits."""
     ft = np.float64 if isinstance(plan, _lib.Plan64) else np.float32      # the data's compute type
     tail = _SUM_TAIL_PLANES_F64 if ft is np.float64 else _SUM_TAIL_PLANES
     early, early_at = 0, (nplanes - tail if nplanes >= 2 * tail else 0)
@@ -424,7 +427,10 @@ def _wow_scales(plan, coefficients, n_scales, nplanes, recomposition_weights, sd
         else:
             t = coefficients._tau(d, s, soft_threshold)                   # ref:199
             tau, noise_plane = (0.0, PLANE_NONE) if t is None else t
-            if whitening and h < 1 and coefficients._ndim == 3:           # ref:193-196 on a cube
+            if whitening and h < 1 and coefficients._ndim == 3 and cube_kernel:
+                # local power, significance, gamma sum and whitening of the cube in one kernel (wt_cube_wow_kernel)
+                plan.wow_cube_scale(s, s, coefficients._shape[0], tau, soft_threshold, noise_plane, factor, gplane)
+            elif whitening and h < 1 and coefficients._ndim == 3:         # ref:193-196 on a cube
                 # local power = 3-D conv_s(c^2): per-slice 2-D filter + axis-0 filter
                 plan.binary("mul", s, s, _SQ_PLANE)
                 plan.smooth3d(_SQ_PLANE, _POW_PLANE, s, coefficients._shape[0])
