@@ -291,9 +291,19 @@ def test_lanes_shared_by_concurrent_callers(L):
             cs = W.transform_many(frames[:20], 4, W.Triangle, lanes=2)
             if any(not np.array_equal(c.data, r) for c, r in zip(cs, ref_t)):
                 bad.append(("transform", rep))
-    ts = [threading.Thread(target=f) for f in (t1, t2, t3)]
+    raised = []             # a bare Thread that raises prints a traceback and dies: the test would not see it
+
+    def guarded(f):
+        def run():
+            try:
+                f()
+            except BaseException as e:             # noqa: BLE001 - reported on the test's thread
+                raised.append((f.__name__, repr(e)))
+        return run
+    ts = [threading.Thread(target=guarded(f)) for f in (t1, t2, t3)]
     for t in ts:
         t.start()
     for t in ts:
         t.join()
+    assert not raised, f"worker threads raised: {raised}"
     assert not bad, bad

@@ -77,6 +77,45 @@ def test_out_target_one_lane_and_exceptions(fake_lanes):
     assert threading.active_count() < 10                     # the lanes have stopped
 
 
+def test_the_first_lane_exception_reaches_the_caller_the_lanes_drain_and_every_thread_ends(fake_lanes):
+    """fn raises in one lane while the other lanes are inside fn: map_frames re-raises THAT exception (the first one
+    recorded, not a later lane's) on the caller's thread, the frames already queued are drained without being run, the
+    frames behind them are never taken from the iterable, and no lane thread is left alive."""
+    before = set(threading.enumerate())
+    caller = threading.current_thread()
+    started, ran, taken, lane_threads = threading.Barrier(3), [], [], set()
+    first_failed = threading.Event()
+
+    def frames():
+        for i in range(1000):
+            taken.append(i)
+            yield i
+
+    def fn(x):
+        lane_threads.add(threading.current_thread())
+        ran.append(x)
+        if x < 3:
+            started.wait(5)                              # the three lanes are inside fn together
+            if x == 1:
+                try:
+                    raise KeyError("frame 1")
+                finally:
+                    first_failed.set()
+            first_failed.wait(5)
+            time.sleep(0.01)                             # frame 1's exception is recorded by now
+            raise ValueError(f"frame {x}, later")
+        return x
+    with pytest.raises(KeyError, match="frame 1") as info:
+        sequence.map_frames(fn, frames(), lanes=3)
+    assert threading.current_thread() is caller and info.value.args == ("frame 1",)
+    assert len(lane_threads) == 3 and caller not in lane_threads
+    assert not any(t.is_alive() for t in lane_threads)
+    assert set(threading.enumerate()) == before          # nothing else was left running either
+    assert sorted(ran)[:3] == [0, 1, 2] and len(ran) <= 3 + 3     # at most the frames in flight when the error was recorded
+    assert len(taken) <= 3 + 2 * 3 + 1                   # the generator was not consumed past the lanes' queue
+    assert getattr(_lib._tls, "ctx", None) is None
+
+
 def test_use_context_nests_and_restores():
     a, b = FakeCtx(), FakeCtx()
     with _lib.use_context(a):

@@ -80,7 +80,7 @@ extern "C" int wt_plane_sum_early(wt_plan *p, int count, int dst, int *done)
     *done = 0;
     if (count < 1 || count > WT_MAX_SUM_PLANES || count - 1 > p->max_level) WT_FAIL("wt_plane_sum_early: %d planes outside [1,%d]", count, p->max_level + 1);
     if (dst >= 0) WT_FAIL("wt_plane_sum_early: dst must not be a coefficient plane");
-    const bool side = g_opt_wow_overlap && p->overlap_ok && count <= p->overlap_scales && p->nranks == 1 && p->ctx->side_pending;
+    const bool side = g_opt_wow_overlap && wt_side_ok(p) && count <= p->overlap_scales && p->nranks == 1 && p->ctx->side_pending;
     if (!side) return 0;
     WtSideScope side_scope(p->ctx, p->scale_ev[count - 1], true);
     if (!side_scope.ok()) return 2;
@@ -225,7 +225,7 @@ extern "C" int wt_wow_scale(wt_plan *p, int plane, int s, double tau, int soft, 
     const int spare = WT_PLANE_SCRATCH(3);
     // Right behind a bilateral transform the update of w_s only needs scale s of it (its event): it runs on the
     // side stream, beside the bilateral kernels of the later scales (plain mode: no maps to order against)
-    const bool side = g_opt_wow_overlap && p->overlap_ok && plane < p->overlap_scales && noise_plane == WT_PLANE_NONE &&
+    const bool side = g_opt_wow_overlap && wt_side_ok(p) && plane < p->overlap_scales && noise_plane == WT_PLANE_NONE &&
                       gamma_plane == WT_PLANE_NONE && p->nranks == 1 && !p->ntaps;
     WtSideScope side_scope(p->ctx, side ? p->scale_ev[plane] : nullptr, side);
     if (!side_scope.ok()) return 2;
@@ -752,7 +752,7 @@ extern "C" int wt_abs_median(wt_plan *p, int plane, float *median)
     if (!p || !median) WT_FAIL("wt_abs_median: null pointer");
     wt_ctx *c = p->ctx;
     // MAD of a detail plane right behind a bilateral transform: beside the scales still queued (side stream)
-    const bool side = g_opt_wow_overlap && p->overlap_ok && plane >= 0 && plane < p->overlap_scales && p->nranks == 1;
+    const bool side = g_opt_wow_overlap && wt_side_ok(p) && plane >= 0 && plane < p->overlap_scales && p->nranks == 1;
     WtSideScope side_scope(c, side ? p->scale_ev[plane] : nullptr, side);
     if (!side_scope.ok()) return 2;
     // a fused pass has histogrammed the first level of this plane (flag bit4 of wt_decompose /

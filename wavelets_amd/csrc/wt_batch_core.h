@@ -70,6 +70,7 @@ static int batch_plane(WtBatchCore<T> *b, int id, T **out)
         WT_FAIL("%s: plane %d is not a plane of a batch (0..%d, input, out, scratch 0/1/3/4/5%s)", b->name, id, b->max_level,
                 b->extra_planes.c_str());
     if (!*slot) WT_HIP(hipMalloc((void **)slot, (size_t)b->n * (size_t)b->fstride * sizeof(T)));
+    b->ctx->overlap_plan = nullptr;      // a batch's launches are main-stream work: no plan keeps the side route (wt_ctx)
     *out = *slot;
     return 0;
 }

@@ -226,9 +226,11 @@ extern "C" int wt_ctx_device_info(wt_ctx *c, char *buf, int cap)
 int g_opt_wow_overlap = getenv("WT_NO_WOW_OVERLAP") ? 0 : 1;   // wt_set_option("wow_overlap", 0/1)
 bool wt_wow_overlap_enabled() { return g_opt_wow_overlap != 0; }
 
-int wt_side_join(wt_ctx *c)
+int wt_side_join(wt_ctx *c, bool main_work)
 {
-    if (!c->side_pending || c->in_side) return 0;
+    if (c->in_side) return 0;
+    if (main_work) c->overlap_plan = nullptr;     // whoever queues main-stream work ends every plan's overlapped state
+    if (!c->side_pending) return 0;
     WT_HIP(hipEventRecord(c->ev_side_done, c->side_stream));
     WT_HIP(hipStreamWaitEvent(c->stream, c->ev_side_done, 0));
     c->side_pending = false;
@@ -444,7 +446,7 @@ extern "C" int wt_ctx_sync(wt_ctx *c)
 {
     WtGuard guard_(ctx_of(c));
     if (!c) WT_FAIL("wt_ctx_sync: null context");
-    WT_TRY(wt_side_join(c));
+    WT_TRY(wt_side_join(c, false));
     WT_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -461,7 +463,7 @@ extern "C" int wt_timer_stop(wt_ctx *c, float *ms)
 {
     WtGuard guard_(ctx_of(c));
     if (!c || !ms) WT_FAIL("wt_timer_stop: null pointer");
-    WT_TRY(wt_side_join(c));
+    WT_TRY(wt_side_join(c, false));
     WT_HIP(hipEventRecord(c->t1, c->stream));
     WT_HIP(hipEventSynchronize(c->t1));
     WT_HIP(hipEventElapsedTime(ms, c->t0, c->t1));

@@ -639,7 +639,7 @@ extern "C" int wt64_plane_sum_early(wt_plan64 *p, int count, int dst, int *done)
     *done = 0;
     if (count < 1 || count > 32 || count - 1 > p->max_level) WT_FAIL("wt64_plane_sum_early: %d planes outside [1,%d]", count, p->max_level + 1);
     if (dst >= 0) WT_FAIL("wt64_plane_sum_early: dst must not be a coefficient plane");
-    const bool side = wt_wow_overlap_enabled() && p->overlap_ok && count <= p->overlap_scales && p->ctx->side_pending;
+    const bool side = wt_wow_overlap_enabled() && wt_side_ok(p) && count <= p->overlap_scales && p->ctx->side_pending;
     if (!side) return 0;
     WtSideScope side_scope(p->ctx, p->scale_ev[count - 1], true);
     if (!side_scope.ok()) return 2;
@@ -716,7 +716,7 @@ extern "C" int wt64_abs_median(wt_plan64 *p, int plane, double *median)
     WtGuard guard_(ctx_of(p));
     if (!p || !median) WT_FAIL("wt64_abs_median: null pointer");
     wt_ctx *c = p->ctx;
-    const bool side = wt_wow_overlap_enabled() && p->overlap_ok && plane >= 0 && plane < p->overlap_scales;   // as wt_abs_median
+    const bool side = wt_wow_overlap_enabled() && wt_side_ok(p) && plane >= 0 && plane < p->overlap_scales;   // as wt_abs_median
     WtSideScope side_scope(c, side ? p->scale_ev[plane] : nullptr, side);
     if (!side_scope.ok()) return 2;
     const bool pre = c->prehist_plan == p && c->prehist_plane == plane;
@@ -865,7 +865,7 @@ extern "C" int wt64_wow_scale(wt_plan64 *p, int plane, int s, double tau, int so
     if (s < 0 || s > 24) WT_FAIL("wt64_wow_scale: scale %d out of range", s);
     if (p->g.border != 0) WT_FAIL("wt64_wow_scale: images under the symmetric border only");
     // (as wt_wow_scale: behind a bilateral transform the update of w_s runs beside the later scales)
-    const bool side = wt_wow_overlap_enabled() && p->overlap_ok && plane >= 0 && plane < p->overlap_scales &&
+    const bool side = wt_wow_overlap_enabled() && wt_side_ok(p) && plane >= 0 && plane < p->overlap_scales &&
                       noise_plane == WT_PLANE_NONE && gamma_plane == WT_PLANE_NONE && stencil64_ok(p);
     WtSideScope side_scope(p->ctx, side ? p->scale_ev[plane] : nullptr, side);
     if (!side_scope.ok()) return 2;
@@ -1030,6 +1030,7 @@ extern "C" int wt64_decompose_bilateral(wt_plan64 *p, int src, int level, const 
     // the per-scale work on w_s that follows (wt64_wow_scale, wt64_abs_median) may run beside the scales still queued
     p->overlap_scales = overlap ? level : 0;
     p->overlap_ok = overlap;
+    if (overlap) p->ctx->overlap_plan = p;          // ... as long as no other plan queues work on this context (wt_side_ok)
     return 0;
 }
 

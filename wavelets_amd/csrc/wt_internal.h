@@ -105,10 +105,21 @@ struct wt_ctx {
     // point that reaches plane data or the context scratch some other way (cached pointers, FFT state) must call
     // wt_side_join(ctx) first; wt_plane_sum_early additionally assumes that planes [0, count) were all updated on
     // the side stream since the transform (overlap_ok && side_pending).
+    // SEVERAL PLANS ON ONE CONTEXT (the lanes of sequence.map_frames shared by concurrent callers: the lock serialises
+    // calls, not call sequences): the invariant above is one plan's view of its own sequence.  Another plan's transform
+    // whose first pass rides the median's histogram queues a memset of d_hist and the histogram kernel on the main
+    // stream and returns; a side-stream select of this plan would then run beside them on the same bins (seen as
+    // "rank not found" and as wrong medians).  So the side route belongs to ONE plan at a time:
+    // overlap_plan is the plan whose bilateral transform was the last main-stream work queued on this context.
+    // wt_side_join - which every main-stream access of every plan, batch and resident entry goes through - clears it;
+    // the transform sets it when it returns; an entry takes the side route only while it still names its plan
+    // (wt_side_ok), else it runs on the main stream behind the join like any other access.  A plan alone on its
+    // context never sees the difference: its own main-stream accesses ended its overlap (overlap_ok) already.
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_side_done = nullptr;
     bool side_pending = false;
     int in_side = 0;
+    const void *overlap_plan = nullptr;          // a wt_plan or a wt_plan64
     // transfer streams of the pipelined host-to-host call (wt_decompose_sum_host), created on first use
     hipStream_t xfer_in = nullptr, xfer_out = nullptr;
     // small device/host scratch for selects & reductions
@@ -223,7 +234,12 @@ struct wt_plan64 {
 };
 
 // ------------------------------------------------------------------ side stream (wt_core.hip)
-int wt_side_join(wt_ctx *c);                        // main stream waits for everything queued on the side stream
+// main stream waits for everything queued on the side stream.  main_work: the caller is about to queue main-stream
+// work or touch the context scratch (every caller but a bare synchronisation): no plan keeps the side route
+int wt_side_join(wt_ctx *c, bool main_work = true);
+// whether an entry on plan p may take the side route: p's bilateral transform is current (overlap_ok) and nothing else
+// has queued main-stream work on the context since (wt_ctx::overlap_plan)
+template <typename Plan> static inline bool wt_side_ok(const Plan *p) { return p->overlap_ok && p->ctx->overlap_plan == p; }
 int wt_side_begin(wt_ctx *c, hipEvent_t after);     // route the context's launches to the side stream, behind `after`
 void wt_side_end(wt_ctx *c);
 struct WtSideScope {                                // RAII form (on = false: nothing); ok() is false when the streams could not be set up

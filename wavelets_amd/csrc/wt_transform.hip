@@ -751,6 +751,7 @@ extern "C" int wt_decompose_bilateral(wt_plan *p, int src, int level, const doub
     // the per-scale work on w_s that follows (wt_wow_scale, wt_abs_median) may run beside the scales still queued
     p->overlap_scales = overlap ? level : 0;
     p->overlap_ok = overlap;
+    if (overlap) p->ctx->overlap_plan = p;          // ... as long as no other plan queues work on this context (wt_side_ok)
     return 0;
 }
 
